@@ -14,13 +14,20 @@ plane-regularised covariance rows and reuse certificates (sp_gicp_target_create)
 N = 1: 1M-vs-1M clouds (config 4). N > 1: config 5 generalised — N x 1M source points sharded 1M per GPU,
 target (N x 1M points, same density) replicated on every GPU: weak scaling.
 
-The block of --steps steps is timed --repeats times (each block bracketed by a barrier + synchronize on both sides);
-`ms_per_step` / `value` come from the MEDIAN block, so a 20-step run is not one 0.7 ms sample.
+A plain run sets up, warms up, times ONE block of exactly --steps steps (bracketed by a barrier + synchronize on both
+sides), writes what the last step computed if --dump-outputs is given, and prints the line. With --full the block is
+timed --repeats times (31 by default: `ms_per_step` / `value` then come from the MEDIAN block) and everything else is
+measured and checked after it.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel,
-`launch_classes` (the launches of one alignment split into searching / steady, each with its algorithmic and
+Prints ONE JSON line on rank 0 (contract in the task statement). With --full it also holds `roofline` for the dominant
+kernel, `launch_classes` (the launches of one alignment split into searching / steady, each with its algorithmic and
 measured-traffic fraction of the HBM peak), `until_converged` (an alignment with the reference's default criteria
-1e-3: what a caller of align() gets) and `cpu_baseline` (the CPU oracle timed on the same workload, rank 0, N = 1 only).
+1e-3: what a caller of align() gets), the pose of a verification alignment against the ground truth, the `stages` block
+and `cpu_baseline` (the CPU oracle timed on the same workload, rank 0, N = 1 only); without it those entries are null.
+
+--dump-outputs DIR writes the arrays a caller of the timed path receives after its last timed step (pose, linear system,
+last pose update, iterations applied) as DIR/<name>.npy; the inputs are generated from fixed seeds, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -47,8 +54,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=31,
-                    help="the block of --steps steps is timed this many times; the median block is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel times and roofline, launch profile, until-converged, the pose check, "
+                         "reuse-off / p2d / hard-init / LM legs, the stages block, the example and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the block of --steps steps is timed this many times; the median block is reported (default: 1, "
+                         "with --full 31)")
     ap.add_argument("--points", type=int, default=PER_GPU_POINTS, help="source points per GPU (default: the config)")
     ap.add_argument("--path", choices=["fused", "generic"], default="fused",
                     help="fused: GridKNN + prepared covariances, NN+K11 in one kernel; generic: KNNBase search + K11")
@@ -87,19 +100,22 @@ def parse():
     ap.add_argument("--internal", action="append", default=[], metavar="NAME=VALUE",
                     help="measurement only: a per-handle switch of csrc/sp_internal.h on the prepared source, e.g. reuse=0 "
                          "(every launch searches every point); such a line is not a benchmark result")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only what the timed region launches (alignments of 20 iterations, criteria 0): no per-launch profile, "
-                         "no until-converged / reuse-off / stage legs — the run profiles/collect_traffic.py wraps, so that every "
-                         "dispatch of the dominant kernel it sees belongs to the timed mix of launches")
+                    help="--full: only what the timed region launches (alignments of 20 iterations, criteria 0): no per-launch "
+                         "profile, no until-converged / reuse-off / stage legs — the run profiles/collect_traffic.py wraps, so "
+                         "that every dispatch of the dominant kernel it sees belongs to the timed mix of launches")
     ap.add_argument("--no-stages", action="store_true",
-                    help="skip the `stages` block (BASELINE configs 2 and 3 and the pre-loop of config 4, timed after the GICP "
-                         "region) and the reuse-off comparison")
-    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="points in the CPU-baseline workload")
+                    help="--full: skip the `stages` block (BASELINE configs 2 and 3 and the pre-loop of config 4, timed after "
+                         "the GICP region) and the reuse-off comparison")
+    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="--full: points in the CPU-baseline workload")
     ap.add_argument("--no-example", action="store_true",
-                    help="skip stages.example_registration_config1 (a child process: a profiler wrapped around this command "
-                         "would trace it too)")
-    return ap.parse_args()
+                    help="--full: skip stages.example_registration_config1 (a child process: a profiler wrapped around this "
+                         "command would trace it too)")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 31 if args.full else 1
+    return args
 
 
 def _free_port():
@@ -233,7 +249,7 @@ def main():
         Tg.covs = g6.covariances_sharded(20, rank, world, lambda send, recv: dist.all_gather_into_tensor(recv, send))
     else:
         Tg.covs = g6.self_knn(20, want_knn=False, want_covs=True)[1]
-        if shards > 1:  # rehearsal: what ONE rank of the N-rank run would spend on its share of the pre-loop
+        if shards > 1 and args.full:  # rehearsal: what ONE rank of the N-rank run would spend on its share of the pre-loop
             preloop = preloop_times(sp, _lib, torch, g6, Tg.covs, args.emulate_rank, shards)
     del g6
     tile = torch.from_numpy(shard_indices(n_total, rank if shards == world else args.emulate_rank, shards,
@@ -388,23 +404,27 @@ def main():
         if c is not None:
             rccl_ranks = int(_lib.lib().sp_comm_world(c._h))  # what the communicator itself says
 
-    # ---- correctness of what was timed: pose after a full alignment vs the ground truth used to make the data
-    T_dev.copy_(T_ident)
-    align_chunk(ITERS_PER_ALIGN, True)
-    torch.cuda.synchronize()
-    T_final = reg.T_from_device(T_dev)
-    lin = reg._read_lin(reg._lin)
-    pose_err = float(np.abs(T_final - T_gt).max())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, reg, T_dev, delta)
 
-    # ---- per-kernel durations over one alignment, by HIP events on the launch stream (rank 0's numbers are reported)
-    kern = kernel_times(sp, _lib, torch, args, reg, S, Tg, knn, prep, T_dev, T_ident, delta, n_local, SORT_MODE)
-    launches = classes = converged = None
-    if args.path == "fused" and group is None and not args.timed_only:
+    pose_err = lin = kern = launches = classes = converged = None
+    stages = reuse0 = p2d = hard = lm = None
+    if args.full:
+        # ---- correctness of what was timed: pose after a full alignment vs the ground truth used to make the data
+        T_dev.copy_(T_ident)
+        align_chunk(ITERS_PER_ALIGN, True)
+        torch.cuda.synchronize()
+        T_final = reg.T_from_device(T_dev)
+        lin = reg._read_lin(reg._lin)
+        pose_err = float(np.abs(T_final - T_gt).max())
+
+        # ---- per-kernel durations over one alignment, by HIP events on the launch stream (rank 0's numbers are reported)
+        kern = kernel_times(sp, _lib, torch, args, reg, S, Tg, knn, prep, T_dev, T_ident, delta, n_local, SORT_MODE)
+    if args.full and args.path == "fused" and group is None and not args.timed_only:
         launches, classes = launch_profile(sp, _lib, torch, reg, prep, T_dev, T_ident, delta, n_local)
         converged = until_converged(sp, torch, S, prep, T_dev, T_ident, delta, n_local, SORT_MODE, REG_TYPE, internal=args.internal)
 
-    stages = reuse0 = p2d = hard = lm = None
-    if world == 1 and shards == 1 and not args.no_stages and not args.timed_only:
+    if args.full and world == 1 and shards == 1 and not args.no_stages and not args.timed_only:
         if args.path == "fused":
             reuse0 = reuse_off_comparison(sp, torch, args, S, prep, T_dev, T_ident, delta, SORT_MODE, REG_TYPE, n_local)
             if args.reg == "gicp":
@@ -419,7 +439,7 @@ def main():
             stages["example_registration_config1"] = example_block(cpu=not args.no_cpu_baseline)
     graphs_live = use_graph and any(not isinstance(v, (str, bool)) for v in getattr(reg, "_loop_graphs", {}).values())
     if rank == 0:
-        dom = max((k for k in kern if kern[k].get("per_iteration", True)), key=lambda k: kern[k]["ms"])
+        dom = max((k for k in kern if kern[k].get("per_iteration", True)), key=lambda k: kern[k]["ms"]) if kern else None
         out = {
             "metric": "gicp_correspondences_per_sec",
             "value": (n_gpu if shards != world else n_total) * args.steps / elapsed,  # (rehearsal: one tile only)
@@ -464,8 +484,9 @@ def main():
                                         else "one C call per alignment"))},
             "iterations_per_sec": args.steps / elapsed,
             "exchange_legs": timed_legs,
+            "full": args.full,
             "pose_max_abs_err_vs_ground_truth": pose_err,
-            "inliers_last_iteration": int(lin.inlier),
+            "inliers_last_iteration": int(lin.inlier) if lin is not None else None,
             "setup_s": t_setup,
             "preloop_per_rank": preloop,
             "kernels": kern,
@@ -477,7 +498,7 @@ def main():
             "hard_init": hard,
             "lm_geman_mcclure": lm,
             "stages": stages,
-            "roofline": roofline_block(dom, kern[dom]),
+            "roofline": roofline_block(dom, kern[dom]) if kern else None,
         }
         # beside `value` (which counts every source point of every iteration, as BASELINE.md 4 defines the metric): the same
         # alignment when every iteration searches every point, and what a caller of align() gets with the default criteria
@@ -485,13 +506,35 @@ def main():
             out["correspondences_per_s_every_iteration_searches"] = reuse0["correspondences_per_s"]
         if converged:
             out["correspondences_per_s_until_converged"] = converged["correspondences_per_s"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, REG_TYPE)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if world > 1 or args.force_sharded:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, reg, T_dev, delta):
+    """What a caller of the timed path holds after its last timed step, as <path>/<name>.npy: the pose T (4 x 4, row-major),
+    the linear system of the last iteration (H, b, error, inlier count), the last pose update `delta` (twist, converged
+    flag, spare) and the iterations the last call applied. Counts are stored as float64 (exact); under 1 KB in all."""
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    lin = reg._read_lin(reg._lin)
+    iters = getattr(reg, "_iters_dev", None)
+    arrays = {"T": reg.T_from_device(T_dev).astype(np.float32),
+              "H": np.array(lin.H, np.float32).reshape(6, 6),
+              "b": np.array(lin.b, np.float32),
+              "error": np.array([lin.error], np.float32),
+              "inlier": np.array([lin.inlier], np.float64),
+              "delta": delta.cpu().numpy().astype(np.float32)}
+    if iters is not None:
+        arrays["iterations"] = iters.cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 HBM_COPY_GBS = 6290.0  # measured float4 streaming copy of the part (MI355X_MICROARCH.md chip table)

@@ -12,10 +12,10 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err
+python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err
 echo "bench done"
 rm -rf /tmp/prof_$TAG
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- python3 $ROOT/bench.py --steps 20 --warmup 20 --no-cpu-baseline --no-example > $OUT/${TAG}_bench_line_under_rocprof.json 2> $OUT/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- python3 $ROOT/bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --no-example > $OUT/${TAG}_bench_line_under_rocprof.json 2> $OUT/rocprof.err
 cp $(grep -l gicp_align_kernel $(find /tmp/prof_$TAG -name "*kernel_stats.csv") | head -1) $OUT/${TAG}_kernel_stats_bench_n1.csv
 python3 - "$TAG" "$OUT" <<'PY'
 import csv, glob, sys

@@ -14,7 +14,7 @@ i=0
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU" "SQ_BUSY_CYCLES SQ_WAVES SQ_ACTIVE_INST_VMEM SQ_INSTS_LDS" "TA_BUSY_avr TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   rm -rf /tmp/sq_$TAG_p$i
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d /tmp/sq_${TAG}_p$i -- python3 $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 20 --repeats 3 "${@:2}" > $OUT/sq_p$i.log 2>&1 || echo "pass $i failed"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d /tmp/sq_${TAG}_p$i -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 20 --repeats 3 "${@:2}" > $OUT/sq_p$i.log 2>&1 || echo "pass $i failed"
 done
 python3 - "$TAG" "$OUT" <<'PY'
 import collections, csv, glob, sys

@@ -6,7 +6,7 @@ Run on the GPU box from the repository root:  python3 profiles/collect_traffic.p
 Method (MI355X_MICROARCH.md §HBM / cdna_hip_programming.md §7):
   * FETCH_SIZE and WRITE_SIZE are collected in SEPARATE passes (they do not fit one pass on gfx950), with --kernel-trace
     only; both are in KiB. rocprofv3 wraps `python3 bench.py ...` directly (no env / bash hop).
-  * The profiled command is `bench.py --timed-only`: every dispatch of gicp_align_kernel it makes belongs to an alignment of
+  * The profiled command is `bench.py --full --timed-only`: every dispatch of gicp_align_kernel it makes belongs to an alignment of
     20 launches from the identity guess with criteria 0 — the mix of launches the timed region runs (warm-up, timed blocks,
     the verification alignment and the HIP-event leg all launch exactly that). Dispatch i of the kernel is therefore launch
     i % 20 of an alignment; the mean over all dispatches is the mean over the timed mix.
@@ -61,7 +61,7 @@ def per_launch(counter, pattern, sub):
 
 
 def main():
-    bench = [os.path.join(ROOT, "bench.py"), "--timed-only", "--no-cpu-baseline", "--steps", "40", "--warmup", "20", "--repeats", "3"]
+    bench = [os.path.join(ROOT, "bench.py"), "--full", "--timed-only", "--no-cpu-baseline", "--steps", "40", "--warmup", "20", "--repeats", "3"]
     if "--reuse" not in sys.argv:  # otherwise recompute from CSVs already under gpurun_out/pmc_traffic (no GPU needed)
         run_pass("FETCH_SIZE", bench, "bench")
         run_pass("WRITE_SIZE", bench, "bench")

@@ -1,11 +1,13 @@
 #!/bin/bash
 # A/B on ONE box: bench.py with every lib under scratch/ab/*.so, interleaved twice; prints the figures that matter.
 # usage (on the GPU box, repo root): bash scratch/ab.sh [extra bench args]
-mkdir -p gpurun_out
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd $ROOT
+mkdir -p out
 for rep in 1 2; do
 for lib in scratch/ab/*.so; do
-  SP_AMD_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-stages "$@" > gpurun_out/ab_$(basename $lib .so).r$rep.log 2>&1
-  python - "$lib" "gpurun_out/ab_$(basename $lib .so).r$rep.log" <<'PY'
+  SP_AMD_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-stages "$@" > out/ab_$(basename $lib .so).r$rep.log 2>&1
+  python - "$lib" "out/ab_$(basename $lib .so).r$rep.log" <<'PY'
 import json, sys
 try:
     d = json.loads([x for x in open(sys.argv[2]) if x.startswith("{")][-1])

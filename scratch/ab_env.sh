@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B/... of scratch libraries on one box through SP_AMD_LIB (the shipped library is not touched), two rounds, alternating:
 #   bash scratch/ab_env.sh scratch/exp_libs/lib_0.so scratch/exp_libs/lib_1.so ...    (BENCH_FLAGS="..." for extra bench flags)
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/ab
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd $ROOT
+mkdir -p out/ab
 for round in 1 2; do
 for L in "$@"; do
   tag=$(basename $L .so)
-  SP_AMD_LIB=$GRAFT_REPO_ROOT/$L timeout -k 10 200 python bench.py --repeats 9 --no-cpu-baseline --no-stages $BENCH_FLAGS > gpurun_out/ab/$tag.json 2> gpurun_out/ab/$tag.err || { echo "$tag failed"; tail -3 gpurun_out/ab/$tag.err; exit 1; }
-  python - gpurun_out/ab/$tag.json $tag <<'PY'
+  SP_AMD_LIB=$ROOT/$L timeout -k 10 200 python bench.py --full --repeats 9 --no-cpu-baseline --no-stages $BENCH_FLAGS > out/ab/$tag.json 2> out/ab/$tag.err || { echo "$tag failed"; tail -3 out/ab/$tag.err; exit 1; }
+  python - out/ab/$tag.json $tag <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 l = d["launches_of_one_alignment"]

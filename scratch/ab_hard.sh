@@ -6,7 +6,7 @@ LIB=$1
 cp sycl_points_amd/lib/libsycl_points_amd.so /tmp/lib_keep.so
 for tag in A B A B; do
   if [ $tag = A ]; then cp /tmp/lib_keep.so sycl_points_amd/lib/libsycl_points_amd.so; else cp $LIB sycl_points_amd/lib/libsycl_points_amd.so; fi
-  timeout -k 10 200 python bench.py --repeats 7 --no-cpu-baseline > /tmp/ab_$tag.json 2> /tmp/ab_$tag.err || { echo "$tag failed"; tail -3 /tmp/ab_$tag.err; continue; }
+  timeout -k 10 200 python bench.py --full --repeats 7 --no-cpu-baseline > /tmp/ab_$tag.json 2> /tmp/ab_$tag.err || { echo "$tag failed"; tail -3 /tmp/ab_$tag.err; continue; }
   python - /tmp/ab_$tag.json $tag <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -1,11 +1,13 @@
 #!/bin/bash
 # A/B of an internal source option on ONE box: bash scratch/ab_opt.sh persistent 0 1
 opt=$1; shift
-mkdir -p gpurun_out
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd $ROOT
+mkdir -p out
 for rep in 1 2; do
 for v in "$@"; do
-  python bench.py --no-cpu-baseline --no-stages --internal $opt=$v > gpurun_out/abopt_${opt}_$v.r$rep.log 2>&1
-  python - "$opt=$v" "gpurun_out/abopt_${opt}_$v.r$rep.log" <<'PY'
+  python bench.py --full --no-cpu-baseline --no-stages --internal $opt=$v > out/abopt_${opt}_$v.r$rep.log 2>&1
+  python - "$opt=$v" "out/abopt_${opt}_$v.r$rep.log" <<'PY'
 import json, sys
 try:
     d = json.loads([x for x in open(sys.argv[2]) if x.startswith("{")][-1])

@@ -1,8 +1,11 @@
 #!/bin/bash
 # same box: per-launch kernel durations (rocprofv3 --kernel-trace) of round 2's library and of the working tree
+# needs scratch/old_r02/repo: a git worktree of 08b158f with its own build (git-ignored, not in a checkout)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+[ -f $ROOT/scratch/old_r02/repo/bench.py ] || { echo "needs round 2's tree, built: git worktree add scratch/old_r02/repo 08b158f, then its own build()"; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 for tag in old new old new; do
-  if [ $tag = old ]; then f=$GRAFT_REPO_ROOT/scratch/old_r02/repo/bench.py; extra=""; else f=$GRAFT_REPO_ROOT/bench.py; extra="--no-stages"; fi
+  if [ $tag = old ]; then f=$ROOT/scratch/old_r02/repo/bench.py; extra=""; else f=$ROOT/bench.py; extra="--full --no-stages"; fi
   rm -rf /tmp/abt
   rocprofv3 --kernel-trace --output-format csv -d /tmp/abt -- python3 $f --no-cpu-baseline $extra --steps 20 --warmup 20 > /tmp/abt.log 2>&1
   python3 - $tag <<'PY'

@@ -7,14 +7,14 @@ mkdir -p $OUT
 bash $ROOT/profiles/collect.sh $TAG > $OUT/collect.log 2>&1
 echo "collect.sh done"; tail -3 $OUT/collect.log
 for w in 2 4 8; do
-  python3 $ROOT/bench.py --emulate-world $w --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_emulated_rank_of_$w.json 2> $OUT/emu$w.err
+  python3 $ROOT/bench.py --full --emulate-world $w --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_emulated_rank_of_$w.json 2> $OUT/emu$w.err
   echo "emulated rank of $w done"
 done
 for x in direct rccl-row torch-row; do
-  RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 python3 $ROOT/bench.py --force-sharded --exchange $x --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_one_rank_$x.json 2> $OUT/onerank_$x.err
+  RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 python3 $ROOT/bench.py --full --force-sharded --exchange $x --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_one_rank_$x.json 2> $OUT/onerank_$x.err
   echo "one rank $x done"
 done
-python3 $ROOT/bench.py --reg p2d --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_p2d.json 2> $OUT/p2d.err
+python3 $ROOT/bench.py --full --reg p2d --no-cpu-baseline --no-stages > $OUT/${TAG}_bench_line_p2d.json 2> $OUT/p2d.err
 echo "p2d done"
 $ROOT/tests/cpp/example_registration $ROOT/tests/golden/source.ply $ROOT/tests/golden/target.ply 100 10 > $OUT/${TAG}_example_registration.txt 2>&1
 echo "example done"

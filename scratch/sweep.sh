@@ -3,7 +3,7 @@
 OUT=gpurun_out/$1; FLAG=$2; shift 2
 mkdir -p $OUT
 for v in "$@"; do
-  timeout -k 10 150 python bench.py --$FLAG $v --repeats 3 --no-cpu-baseline $SWEEP_EXTRA > $OUT/${FLAG}_$v.json 2> $OUT/${FLAG}_$v.err || { echo "$FLAG $v failed"; tail -3 $OUT/${FLAG}_$v.err; continue; }
+  timeout -k 10 150 python bench.py --full --$FLAG $v --repeats 3 --no-cpu-baseline $SWEEP_EXTRA > $OUT/${FLAG}_$v.json 2> $OUT/${FLAG}_$v.err || { echo "$FLAG $v failed"; tail -3 $OUT/${FLAG}_$v.err; continue; }
   python - $OUT/${FLAG}_$v.json "$FLAG $v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
