@@ -32,7 +32,8 @@ extern "C" {
 #define SP_ERR_RUNTIME 2          /* reference: std::runtime_error    */
 #define SP_ERR_HIP 3              /* reference: sycl::exception from wait_and_throw */
 
-#define SP_ABI_VERSION 6
+/* 7: sp_knn_tree_* — the accelerated KDTree's structures and its choice among them moved into the library from both front ends */
+#define SP_ABI_VERSION 7
 int sp_abi_version(void);
 /* The library keeps device buffers it no longer needs (temporaries of a build, the arrays of a destroyed grid / tree / target) in
  * a pool, tagged with the stream whose work may still use them: a later call on the SAME stream takes them without waiting (stream
@@ -221,6 +222,36 @@ int sp_bvh_remove_by_flags(sp_bvh* bvh, const uint8_t* flags, const int32_t* new
  * the reference's KDTree, so a caller that needs them again later (the facade builds the reference-topology KD-tree lazily,
  * for radius search / lazy delete) does not depend on the source cloud still being there. */
 int sp_bvh_export_points(const sp_bvh* bvh, float* points_out, void* stream);
+
+/* ------------------------------------------------------------------- accelerated KDTree (which structure answers) */
+
+/* KDTree (knn/kdtree.hpp:142-766) with the structure chosen per search: the one object behind the facade's KDTree and
+ * sycl_points_amd.api.KDTree(accelerate=True); csrc/knn_tree.hip states the rule. sp_knn_tree_create keeps a copy of the points
+ * (stream-ordered, no synchronisation); the reference's tree (below 1024 points: at once, synchronising), the hierarchy
+ * (sp_bvh_*) and a grid on the tree's own cloud are built on first need, allocating and synchronising as their creates do.
+ *   sp_knn_tree_backend  the structure (SP_KNN_*) sp_knn_tree_search answers the same arguments from; may build the grid.
+ *   sp_knn_tree_search   as sp_kdtree_search, k <= 100 (SP_ERR_RUNTIME). own_cloud != 0: the caller states that the queries are
+ *                        the points the tree was built on, unchanged since; it counts only while nothing was removed and
+ *                        without a transform. transT NULL or a host identity: no transform; a device transT always is one.
+ *   sp_knn_tree_radius_search / sp_knn_tree_remove_by_flags  as sp_kdtree_*; a removal reaches every structure, also one built
+ *                        later, ends the own-cloud, grid and brute-force shortcuts, and synchronises.
+ *   sp_knn_tree_set_reference_order  != 0: every search uses the reference's tree (its first-visited tie order).
+ *   sp_knn_tree_info     SP_KNN_TREE_*: point count, nothing removed yet, hierarchy built, grid built. */
+typedef struct sp_knn_tree sp_knn_tree;
+enum { SP_KNN_HOST_TREE = 0, SP_KNN_HIERARCHY = 1, SP_KNN_GRID = 2, SP_KNN_BRUTE_FORCE = 3 };
+enum { SP_KNN_TREE_SIZE = 0, SP_KNN_TREE_PRISTINE = 1, SP_KNN_TREE_HIERARCHY_BUILT = 2, SP_KNN_TREE_GRID_BUILT = 3 };
+int sp_knn_tree_create(const float* points, size_t n, size_t leaf_threshold, void* stream, sp_knn_tree** out);
+void sp_knn_tree_destroy(sp_knn_tree* tree);
+int sp_knn_tree_backend(sp_knn_tree* tree, size_t nq, size_t k, const float* transT, int transT_on_device, int own_cloud,
+                        void* stream, int* backend_out);
+int sp_knn_tree_search(sp_knn_tree* tree, const float* queries, size_t nq, size_t k, const float* transT, int transT_on_device,
+                       int own_cloud, int32_t* idx_out, float* d2_out, void* stream);
+int sp_knn_tree_radius_search(sp_knn_tree* tree, const float* queries, size_t nq, size_t max_k, float radius,
+                              const float* transT, int transT_on_device, int32_t* idx_out, float* d2_out, void* stream);
+int sp_knn_tree_remove_by_flags(sp_knn_tree* tree, const uint8_t* flags, const int32_t* new_indices, size_t n_flags,
+                                void* stream);
+int sp_knn_tree_set_reference_order(sp_knn_tree* tree, int enable);
+int sp_knn_tree_info(const sp_knn_tree* tree, int what, uint64_t* out);
 
 /* --------------------------------------------------------------------------------------- voxel grid */
 

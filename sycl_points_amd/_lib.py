@@ -130,6 +130,14 @@ SIGNATURES = {
     "sp_bvh_radius_search": (_i, [_vp, _vp, _sz, _sz, _f, _vp, _i, _vp, _vp, _vp]),
     "sp_bvh_remove_by_flags": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "sp_bvh_export_points": (_i, [_vp, _vp, _vp]),
+    "sp_knn_tree_create": (_i, [_vp, _sz, _sz, _vp, C.POINTER(_vp)]),
+    "sp_knn_tree_destroy": (None, [_vp]),
+    "sp_knn_tree_backend": (_i, [_vp, _sz, _sz, _vp, _i, _i, _vp, C.POINTER(_i)]),
+    "sp_knn_tree_search": (_i, [_vp, _vp, _sz, _sz, _vp, _i, _i, _vp, _vp, _vp]),
+    "sp_knn_tree_radius_search": (_i, [_vp, _vp, _sz, _sz, _f, _vp, _i, _vp, _vp, _vp]),
+    "sp_knn_tree_remove_by_flags": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "sp_knn_tree_set_reference_order": (_i, [_vp, _i]),
+    "sp_knn_tree_info": (_i, [_vp, _i, C.POINTER(C.c_uint64)]),
     "sp_voxel_keys": (_i, [_vp, _sz, _f, _vp, _vp]),
     "sp_voxel_downsample_workspace_bytes": (_sz, [_sz]),
     "sp_voxel_downsample": (_i, [_vp, _sz, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -256,7 +264,7 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.sp_abi_version() != 6:
+        if L.sp_abi_version() != 7:
             raise ImportError("libsycl_points_amd.so ABI version mismatch")
         _lib = L
     return _lib

@@ -8,6 +8,7 @@ Names, argument meaning and error behaviour follow the reference (paths relative
 device memory, streams and torch.distributed only — all compute goes through libsycl_points_amd.so.
 """
 import ctypes as C
+import weakref
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -173,113 +174,63 @@ def _trans_arg(transT):
 
 
 class KDTree(KNNBase):
-    """algorithms/knn/kdtree.hpp:142-766.
+    """algorithms/knn/kdtree.hpp:142-766. build(points) is the reference's tree (host build with its rule, device search).
+    build(points, accelerate=True) is the library's sp_knn_tree, which the C++ facade's KDTree wraps too: its own copy of the
+    points and, per search, the structure csrc/knn_tree.hip chooses (`backend_for`: that choice, without searching)."""
 
-    build(points) is the reference's tree (host build with its rule, device search). build(points, accelerate=True) mirrors the
-    C++ facade's KDTree (include/sycl_points/amd/knn.hpp): from 1024 points on the hierarchy is built on the device (BVH) and
-    knn_search answers from it for k <= 32; a search of the tree's OWN cloud with 8 <= k <= 20 on at least 32768 points of
-    near-uniform density (fullest cell of a 6-points-per-cell grid <= 48 points) is answered by that grid; radius search, lazy
-    delete, k > 32 use the reference's tree, built the first time it is needed. `backend_for` is the decision itself
-    (tests/test_gpu_facade.py holds it to the facade's on the same clouds)."""
+    _BACKENDS = ("kdtree", "bvh", "grid", "bruteforce")  # SP_KNN_HOST_TREE, SP_KNN_HIERARCHY, SP_KNN_GRID, SP_KNN_BRUTE_FORCE
+    _INFO = {"size": 0, "pristine": 1, "hierarchy_built": 2, "grid_built": 3}  # SP_KNN_TREE_*
 
-    DEVICE_BUILD_MIN_POINTS = 1024   # knn.hpp: KDTree::kDeviceBuildMinPoints
-    GRID_SELF_MIN_POINTS = 32768     # knn.hpp: KDTree::kGridSelfMinPoints
-    GRID_SELF_MAX_CELL = 48          # knn.hpp: KDTree::kGridSelfMaxCell
-    GRID_SELF_POINTS_PER_CELL = 6.0
-    BRUTE_FORCE_MAX_TARGETS = 16384  # knn.hpp: KDTree::kBruteForceMaxTargets
-    BRUTE_FORCE_MAX_QUERIES = 65536  # knn.hpp: KDTree::kBruteForceMaxQueries
-
-    def __init__(self, handle, n, device):
+    def __init__(self, handle, n, device, built_on=None):
         self._h = handle
         self.n = n
         self.device = device
-        self._hier = None         # the device-built hierarchy, built when a search first needs it (accelerate=True)
-        self._points_version = 0
-        self._accelerated = False
-        self._points = None       # ... the points it was built on (device tensor), for the lazily built reference tree / the grid
-        self._self_grid = None
-        self._self_grid_tried = False
-        self._removals = []       # lazy deletes the (not yet built) reference tree has to replay
-        self._pristine = True
-        self._leaf_threshold = 16
+        self._accelerated = built_on is not None
+        self._built_on = built_on  # accelerate=True: (weak reference to the points tensor, its _version at build())
 
     @staticmethod
     def build(points, leaf_threshold=16, accelerate=False):
         p = _points_of(points)
-        if accelerate and p.shape[0] >= KDTree.DEVICE_BUILD_MIN_POINTS:
+        h = C.c_void_p()
+        if accelerate:
             pd = _dev_f32(p, 4)
-            t = KDTree(None, pd.shape[0], pd.device)
-            t._accelerated = True  # (the hierarchy itself is built lazily, like the facade's: many trees never need it)
-            t._points = pd
-            t._points_version = pd._version  # (an in-place edit of the caller's tensor after build() ends the own-cloud shortcuts)
-            t._leaf_threshold = leaf_threshold
-            return t
+            check(_lib.lib().sp_knn_tree_create(_ptr(pd), pd.shape[0], leaf_threshold, _stream(), C.byref(h)))
+            return KDTree(h, pd.shape[0], pd.device, (weakref.ref(pd), pd._version))
         host = np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, np.float32)
         dev = p.device if isinstance(p, torch.Tensor) and p.is_cuda else torch.device("cuda")
-        h = C.c_void_p()
         check(_lib.lib().sp_kdtree_create(host.ctypes.data_as(C.c_void_p), host.shape[0], leaf_threshold, _stream(),
                                           C.byref(h)))
         return KDTree(h, host.shape[0], dev)
 
-    @property
-    def _bvh(self):
-        if self._accelerated and self._hier is None:
-            if self._points._version != self._points_version:
-                # (the facade's tree owns a copy of the points taken at build(); this mirror borrows the caller's tensor)
-                raise SpError(2, "[KDTree] the points tensor was modified in place after build() and before the first search: "
-                                 "build the tree again (or hand build() a clone)")
-            self._hier = BVH.build(self._points)
-        return self._hier
+    def _fn(self, name):
+        return getattr(_lib.lib(), ("sp_knn_tree_" if self._accelerated else "sp_kdtree_") + name)
 
-    def _host_tree(self):
-        if not self._h:
-            if self._points._version != self._points_version:
-                raise SpError(2, "[KDTree] the points tensor was modified in place after build() and before the reference tree was "
-                                 "needed: build the tree again (or hand build() a clone)")
-            host = np.ascontiguousarray(self._points.detach().cpu().numpy(), np.float32)
-            h = C.c_void_p()
-            check(_lib.lib().sp_kdtree_create(host.ctypes.data_as(C.c_void_p), host.shape[0], self._leaf_threshold, _stream(),
-                                              C.byref(h)))
-            self._h = h
-            # nodes removed while only the hierarchy existed: the same lazy deletes, in their order (KDTree::host_tree)
-            for flags, indices in self._removals:
-                check(_lib.lib().sp_kdtree_remove_by_flags(self._h, _ptr(flags), _ptr(indices), flags.shape[0], _stream()))
-            torch.cuda.current_stream().synchronize()
-            self._removals = []
-        return self._h
+    def _own_cloud(self, q):
+        """The queries are the tensor the tree was built on (same storage, length and version): sp_knn_tree's own_cloud."""
+        t = self._built_on[0]()
+        return int(t is not None and isinstance(q, torch.Tensor) and q.is_cuda and q.shape[0] == self.n and
+                   q.data_ptr() == t.data_ptr() and t._version == self._built_on[1])
 
-    def _uniform_grid(self):
-        if not self._self_grid_tried:
-            self._self_grid_tried = True
-            if self.n >= KDTree.GRID_SELF_MIN_POINTS:
-                g = GridKNN.build(self._points, points_per_cell=KDTree.GRID_SELF_POINTS_PER_CELL)
-                if g.max_cell_points() <= KDTree.GRID_SELF_MAX_CELL:
-                    self._self_grid = g
-        return self._self_grid
+    def _info(self, what):  # sp_knn_tree_info (accelerate=True), `what` a key of _INFO
+        v = C.c_uint64()
+        check(_lib.lib().sp_knn_tree_info(self._h, KDTree._INFO[what], C.byref(v)))
+        return int(v.value)
 
     def backend_for(self, queries, k, transT=None):
         """'kdtree' | 'bvh' | 'grid' | 'bruteforce': what knn_search_async(queries, k, ..., transT) answers from
-        (KDTree::backend_for)."""
-        if not self._accelerated or k > 32:
+        (sp_knn_tree_backend)."""
+        if not self._accelerated:
             return "kdtree"
         q = _points_of(queries)
-        unchanged = self._points is not None and self._points._version == self._points_version
-        own = (self._pristine and transT is None and isinstance(q, torch.Tensor) and q.is_cuda and q.shape[0] == self.n and
-               q.data_ptr() == self._points.data_ptr() and unchanged)
-        if own and 8 <= k <= 20 and self._uniform_grid() is not None:
-            return "grid"
-        # a small cloud (the reference example's 6 k-point downsampled scans): exact brute force beats building a hierarchy
-        # (up to 12 k targets and 8 * 10^7 pairs: one launch with the cloud in LDS; beyond, from 2048 targets: the bounded passes)
-        small = self.n <= 12032 and q.shape[0] * self.n <= 80_000_000
-        if (self._pristine and unchanged and transT is None and k <= 20 and q.shape[0] <= KDTree.BRUTE_FORCE_MAX_QUERIES and
-                (small or (2048 <= self.n <= KDTree.BRUTE_FORCE_MAX_TARGETS and self.n >= 256 * k))):
-            return "bruteforce"
-        return "bvh"
+        tp, on_dev, keep = _trans_arg(transT)
+        b = C.c_int()
+        check(_lib.lib().sp_knn_tree_backend(self._h, q.shape[0], k, tp, on_dev, self._own_cloud(q), _stream(), C.byref(b)))
+        return KDTree._BACKENDS[b.value]
 
     def __del__(self):
         try:
             if self._h:
-                _lib.lib().sp_kdtree_destroy(self._h)
+                self._fn("destroy")(self._h)
                 self._h = None
         except Exception:
             pass
@@ -288,30 +239,13 @@ class KDTree(KNNBase):
         q = _dev_f32(_points_of(queries), 4)
         if k > 100:
             raise SpError(2, "[KDTree::knn_search_async] `k` is too large. not support.")
-        backend = self.backend_for(queries, k, transT) if self._accelerated else "kdtree"
-        if backend == "bruteforce":
-            res = knn_search_bruteforce(q, self._points, k)
-            result.indices, result.distances, result.query_size, result.k = res.indices, res.distances, res.query_size, res.k
-            return
-        if backend == "grid":
-            res = self._uniform_grid().self_knn(k)[0]
-            result.indices, result.distances, result.query_size, result.k = res.indices, res.distances, res.query_size, res.k
-            return
-        if backend == "bvh":
-            own = (self._pristine and transT is None and q.shape[0] == self.n and q.data_ptr() == self._points.data_ptr() and
-                   self._points._version == self._points_version)
-            if own:
-                res = self._bvh.self_knn(k)
-                result.indices, result.distances, result.query_size, result.k = res.indices, res.distances, res.query_size, res.k
-            else:
-                self._bvh.knn_search_async(queries, k, result, transT)
-            return
         result.resize(q.shape[0], k, q.device)
         if q.shape[0] == 0:
             return
         tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_kdtree_search(self._host_tree(), _ptr(q), q.shape[0], k, tp, on_dev, _ptr(result.indices),
-                                          _ptr(result.distances), _stream()))
+        own = (self._own_cloud(q),) if self._accelerated else ()
+        check(self._fn("search")(self._h, _ptr(q), q.shape[0], k, tp, on_dev, *own, _ptr(result.indices),
+                                 _ptr(result.distances), _stream()))
 
     def radius_search_async(self, queries, max_k, radius, result, transT=None):
         q = _dev_f32(_points_of(queries), 4)
@@ -320,27 +254,16 @@ class KDTree(KNNBase):
         if q.shape[0] == 0 or max_k == 0:
             result.resize(0, 0, q.device)
             return
-        if self._accelerated and max_k <= 32:
-            self._bvh.radius_search_async(queries, max_k, radius, result, transT)
-            return
         result.resize(q.shape[0], max_k, q.device)
         tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_kdtree_radius_search(self._host_tree(), _ptr(q), q.shape[0], max_k, radius, tp, on_dev,
-                                                 _ptr(result.indices), _ptr(result.distances), _stream()))
+        check(self._fn("radius_search")(self._h, _ptr(q), q.shape[0], max_k, radius, tp, on_dev, _ptr(result.indices),
+                                        _ptr(result.distances), _stream()))
 
     def remove_nodes_by_flags(self, flags, indices):
         if flags.shape[0] != indices.shape[0]:
             raise SpError(2, "[KDTree::remove_nodes_by_flags_impl] flags and indices must have the same size.")
-        if self._accelerated:
-            self._bvh.remove_nodes_by_flags(flags, indices)
-        if self._h or not self._accelerated:
-            check(_lib.lib().sp_kdtree_remove_by_flags(self._host_tree(), _ptr(flags), _ptr(indices), flags.shape[0], _stream()))
-        else:  # (a reference tree built from here on starts from the original points: it replays these)
-            self._removals.append((flags.clone(), indices.clone()))
+        check(self._fn("remove_by_flags")(self._h, _ptr(flags), _ptr(indices), flags.shape[0], _stream()))
         torch.cuda.current_stream().synchronize()
-        self._pristine = False  # no own-cloud shortcut / grid any more: the points carry other indices now
-        self._self_grid = None
-        self._self_grid_tried = True
 
 
 class BVH(KNNBase):

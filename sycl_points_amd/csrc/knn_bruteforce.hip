@@ -967,11 +967,13 @@ __global__ __launch_bounds__(kSmallBlock) void knn_bf_small_kernel(const float4*
         __builtin_amdgcn_wave_barrier();
     }
 }
+}  // namespace
 bool small_applies(size_t nq, size_t nt) {
     // (measured, self-search: 6 k x 6 k, k = 10: 30 us against 108 for the bounded pipeline; 12 k x 12 k: 145 against 113 — the
     // matrix cores' bounding pass wins from about 10^8 pairs on)
     return nt >= kSmallMinTargets && nt <= kSmallMaxTargets && nq * nt <= (size_t)80 * 1000 * 1000;
 }
+namespace {
 int run_small(const float* queries, size_t nq, const float* targets, size_t nt, size_t k, int32_t* idx_out, float* d2_out,
               hipStream_t st) {
     auto set_lds = [](const void* f) {

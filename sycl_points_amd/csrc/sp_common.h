@@ -41,6 +41,9 @@ inline unsigned stream_grid(size_t n, int block = kBlock, int per_thread = 1) {
 // ticket counter; also the 64 KB row reset of the rows_all_reduced = 1 loop) not to be ordered before the kernel node that
 // follows it in the captured stream when the graph is replayed — eager launches and the first replay hide it.
 int zero_async(void* p, size_t bytes, hipStream_t st);  // capi_common.hip; returns SP_OK / SP_ERR_HIP
+// true when sp_knn_bruteforce answers nq queries against nt targets by its one launch that keeps the targets in LDS
+// (knn_bruteforce.hip; sp_knn_tree's backend rule asks it too).
+bool small_applies(size_t nq, size_t nt);
 
 // Device scratch for the structure builds (sp_grid_create and friends): the temporaries of a build (sort keys, rocPRIM
 // workspaces, a few counters) are idle again when the build returns (it synchronises its stream), so they are kept and

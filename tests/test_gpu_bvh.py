@@ -329,3 +329,26 @@ def test_kdtree_k_above_32_after_nodes_left_the_hierarchy(sp, orc):
     r = tree.knn_search(dev(qry), 33)
     oi, od = orc.kdtree_knn(nodes, qry, 33)
     assert np.array_equal(r.indices.cpu().numpy(), oi) and np.array_equal(r.distances.cpu().numpy(), od)
+
+
+def test_accelerated_kdtree_keeps_its_own_points(sp, orc):
+    """KDTree.build(points, accelerate=True) keeps a copy of the points (sp_knn_tree, as the facade's KDTree does): the caller's
+    tensor edited in place after build() and before the first search changes nothing the tree answers — the brute-force
+    search, the hierarchy and the reference's tree, the last two built after the edit, all search the points as they were at
+    build(). The edited tensor as queries is no longer the tree's own cloud."""
+    qry = orc.rng(7).uniform_points(300, 5.0)
+    for n, backend in ((6000, "bruteforce"), (20000, "bvh")):
+        pts = orc.rng(99).uniform_points(n, 5.0)
+        p = dev(pts)
+        tree = sp.KDTree.build(p, accelerate=True)
+        p[:, :3] += 1.0
+        assert tree.backend_for(dev(qry), 10) == backend
+        r = tree.knn_search(dev(qry), 10)
+        bi, bd = orc.knn_bruteforce(qry, pts, 10)
+        assert np.array_equal(r.indices.cpu().numpy(), bi) and np.array_equal(r.distances.cpu().numpy(), bd)
+        r = tree.knn_search(p, 10)
+        bi, bd = orc.knn_bruteforce(p.cpu().numpy(), pts, 10)
+        assert np.array_equal(r.indices.cpu().numpy(), bi) and np.array_equal(r.distances.cpu().numpy(), bd)
+    r = tree.knn_search(dev(qry), 40)  # the reference's tree, built now from the copy
+    oi, od = orc.kdtree_knn(orc.kdtree_build(pts), qry, 40)
+    assert np.array_equal(r.indices.cpu().numpy(), oi) and np.array_equal(r.distances.cpu().numpy(), od)

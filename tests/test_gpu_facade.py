@@ -78,12 +78,13 @@ def test_example_registration_config1(orc, knn):
     assert np.abs(T[:3, 3] - T_gt[:3, 3]).max() < 0.05 and np.abs(T[:3, :3] - T_gt[:3, :3]).max() < 0.01
 
 
-def test_python_kdtree_takes_the_facades_decisions(orc):
-    """sycl_points_amd.api.KDTree.build(points, accelerate=True) mirrors the facade's KDTree (knn.hpp): the same structure
-    answers the same query on the same cloud as in tests/cpp/test_facade.cpp (kdtree_backend_on_the_bundled_scan,
-    kdtree_self_knn_large_clouds) — the raw scan of surfaces goes to the device-built hierarchy, a large cloud of uniform
-    density to the grid for 8 <= k <= 20, small clouds / k > 32 / a tree with removed nodes to the reference's tree — and the
-    lists are the exact ones (oracle brute force) whichever structure answers."""
+def test_python_kdtree_is_the_facades_sp_knn_tree(orc):
+    """sycl_points_amd.api.KDTree.build(points, accelerate=True) is the library object behind the facade's KDTree
+    (sp_knn_tree): the same structure answers the same query on the same cloud as in tests/cpp/test_facade.cpp
+    (kdtree_backend_on_the_bundled_scan, kdtree_self_knn_large_clouds) — the raw scan of surfaces goes to the device-built
+    hierarchy, a large cloud of uniform density to the grid for 8 <= k <= 20, small clouds / k > 32 to the reference's tree,
+    a tree with removed nodes back to the hierarchy — and the lists are the exact ones (oracle brute force) whichever
+    structure answers."""
     import torch
 
     import sycl_points_amd.api as sp
@@ -113,10 +114,13 @@ def test_python_kdtree_takes_the_facades_decisions(orc):
     mid = dev(orc.rng(6).uniform_points(6000, 10.0))
     tm = sp.KDTree.build(mid, accelerate=True)
     assert tm.backend_for(mid, 10) == "bruteforce" and tm.backend_for(mid, 20) == "bruteforce" and tm.backend_for(mid, 24) == "bvh"
-    assert tm.backend_for(mid, 10, np.eye(4, dtype=np.float32)) == "bvh"
+    Tm = np.eye(4, dtype=np.float32)
+    Tm[0, 3] = 0.5
+    assert tm.backend_for(mid, 10, Tm) == "bvh"  # (a transform ends the shortcut: test_facade.cpp, the same matrix)
+    assert tm.backend_for(mid, 10, np.eye(4, dtype=np.float32)) == tm.backend_for(mid, 10)  # (an identity is no transform)
     oi, od = orc.knn_bruteforce(mid.cpu().numpy(), mid.cpu().numpy(), 10)
     r = tm.knn_search(mid, 10)
-    assert tm._hier is None  # (never built)
+    assert tm._info("hierarchy_built") == 0  # (never built)
     assert np.array_equal(r.indices.cpu().numpy(), oi) and np.array_equal(r.distances.cpu().numpy(), od)
     # after a lazy delete the hierarchy keeps answering (sp_bvh_remove_by_flags); the grid shortcut for the own cloud is gone
     flags = np.ones(40000, np.uint8)
