@@ -1,6 +1,8 @@
 // sycl_points facade for MI355X — covariance / normals, voxel grid, pre-filters, transform.
 //   algorithms/feature/covariance.hpp            : covariance::estimate_async, estimate_normals_async, extract_normals(_async)
 //   algorithms/filter/voxel_downsampling.hpp     : filter::VoxelGrid
+//   algorithms/filter/polar_downsampling.hpp     : filter::PolarGrid
+//   algorithms/common/coordinate_system.hpp      : CoordinateSystem, coordinate_system_from_string
 //   algorithms/filter/preprocess_filter.hpp      : filter::PreprocessFilter (box_filter, random_sampling)
 //   algorithms/common/filter_by_flags.hpp        : filter::FilterByFlags
 //   algorithms/common/transform.hpp              : transform::transform, transform_copy
@@ -101,7 +103,102 @@ inline uint32_t read_u32(const void* dev, hipStream_t st) {
     hip_check(hipStreamSynchronize(st), "sync");
     return *v;
 }
+/// The protocol of VoxelGrid::run and PolarGrid::run around one sp_voxel_downsample_report / sp_polar_downsample_report call
+/// (run(): key_box(box6_dev) computes a cloud's key box on the device, report(box6_host, report8, workspace, workspace_bytes)
+/// enqueues the call). Returns the call's record {voxels, points outside the box, this cloud's key box lo xyz, hi xyz}.
+class KeyBoxMemory {
+public:
+    void forget() { have_key_box_ = false; }
+    template <class KeyBoxFn, class ReportFn>
+    std::array<int32_t, 8> run(size_t N, hipStream_t st, KeyBoxFn&& key_box, ReportFn&& report) {
+        const size_t ws_bytes = sp_voxel_downsample_workspace_bytes(N);
+        // voxel count | boxed-path status | key box of the key-box call (6 ints) | this cloud's key box, sharded
+        constexpr int kInfoInts = 32 + SP_VOXEL_BOX_SHARD_STRIDE * SP_VOXEL_BOX_SHARDS;
+        DeviceScratch ws(ws_bytes, st), info(kInfoInts * 4, st);
+        uint32_t* info_dev = static_cast<uint32_t*>(info.p);
+        static_assert(kInfoInts * 4 <= 4096, "pinned block");
+        int32_t h_own[kInfoInts];
+        int32_t* const h = pinned_block_4k() ? static_cast<int32_t*>(pinned_block_4k()) : h_own;  // (read-backs by DMA)
+        // The sort runs on keys compressed to the (widened) key box of the PREVIOUS cloud — scans of one sensor have similar
+        // extents; the device verifies that this cloud fits, and the key kernel finds this cloud's own box on the way (next
+        // call's guess; the exact box of the redo when the cloud did not fit). The first call has no guess and computes the
+        // box first: every call sorts compressed keys (the 64-bit sort is left for boxes of >= 2^32 cells).
+        // The call reports {voxels, points outside the box, this cloud's key box} in ONE record (sp_voxel_downsample_report): through
+        // host-mapped words the last kernel stores to and this thread spins on when they are to be had — no copy, no
+        // synchronisation: the scratch then goes back behind the stream's work — else through a copy and a wait.
+        const MappedWord& mapped = MappedWord::mine();
+        const bool poll = mapped.usable();
+        auto launch = [&](const int32_t* box) {
+            uint32_t* const rep = poll ? mapped.dev : info_dev;
+            if (poll) mapped.arm();
+            report(box, rep, ws.p, ws_bytes);
+            if (poll) {
+                h[0] = static_cast<int32_t>(mapped.wait(st));
+                std::atomic_thread_fence(std::memory_order_acquire);
+                for (int j = 1; j < 8; ++j) h[j] = static_cast<int32_t>(mapped.host[j]);
+                ws.stream_ordered = true;  // (kernels of the call may still be running: not idle, but ordered on st)
+                info.stream_ordered = true;
+            } else {
+                hip_check(hipMemcpyAsync(h, info.p, 32, hipMemcpyDeviceToHost, st), "D2H");
+                hip_check(hipStreamSynchronize(st), "sync");
+            }
+        };
+        if (!have_key_box_) {
+            key_box(reinterpret_cast<int32_t*>(info_dev + 2));
+            hip_check(hipMemcpyAsync(h, info.p, 32, hipMemcpyDeviceToHost, st), "D2H");
+            hip_check(hipStreamSynchronize(st), "sync");
+            have_key_box_ = h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7];
+            for (int a = 0; a < 6; ++a) key_box_[a] = h[2 + a];
+        }
+        launch(have_key_box_ ? key_box_ : nullptr);
+        if (h[1] != 0) {  // the cloud left the remembered box: again, with its own
+            int32_t exact[6] = {h[2], h[3], h[4], h[5], h[6], h[7]};
+            launch(exact);
+        }
+        const bool had_box = have_key_box_;
+        have_key_box_ = h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7];
+        if (have_key_box_) {
+            // Keep what earlier clouds needed as well (one VoxelGrid usually serves several scans in turn — source and target of
+            // a registration —, and a guess that forgets the other scan is redone every call), unless that has grown to more
+            // than 8x the cells this cloud needs.
+            int32_t lo[3], hi[3], ulo[3], uhi[3];
+            double cells = 1.0, ucells = 1.0;
+            for (int a = 0; a < 3; ++a) {
+                const int32_t margin = std::max<int32_t>(2, (h[5 + a] - h[2 + a] + 1) / 8);
+                lo[a] = std::max<int32_t>(h[2 + a] - margin, 0);
+                hi[a] = std::min<int32_t>(h[5 + a] + margin, (1 << 21) - 1);
+                ulo[a] = had_box ? std::min(lo[a], key_box_[a]) : lo[a];
+                uhi[a] = had_box ? std::max(hi[a], key_box_[3 + a]) : hi[a];
+                cells *= double(hi[a] - lo[a] + 1);
+                ucells *= double(uhi[a] - ulo[a] + 1);
+            }
+            const bool keep = ucells <= 8.0 * cells;
+            for (int a = 0; a < 3; ++a) {
+                key_box_[a] = keep ? ulo[a] : lo[a];
+                key_box_[3 + a] = keep ? uhi[a] : hi[a];
+            }
+        }
+        std::array<int32_t, 8> rec;
+        for (int j = 0; j < 8; ++j) rec[j] = h[j];
+        return rec;
+    }
+
+private:
+    int32_t key_box_[6] = {0, 0, 0, 0, 0, 0};
+    bool have_key_box_ = false;
+};
 }  // namespace detail
+
+// ================================================================================================ coordinate system
+/// common/coordinate_system.hpp:11-26 (REP-103): the frame PolarGrid measures its angles in.
+enum class CoordinateSystem : std::uint8_t { LIDAR = 0, CAMERA = 1 };
+inline CoordinateSystem coordinate_system_from_string(const std::string& str) {
+    std::string upper = str;
+    for (auto& c : upper) c = (char)std::toupper((unsigned char)c);
+    if (upper == "LIDAR") return CoordinateSystem::LIDAR;
+    if (upper == "CAMERA") return CoordinateSystem::CAMERA;
+    throw std::invalid_argument("Invalid coordinate system: " + str);
+}
 
 // ================================================================================================ robust loss tags
 namespace robust {
@@ -232,7 +329,7 @@ public:
         if (voxel_size <= 0.0f) throw std::invalid_argument("voxel_size must be positive");
         voxel_size_ = voxel_size;
         voxel_size_inv_ = 1.0f / voxel_size_;
-        have_key_box_ = false;  // the remembered key box is in units of the old voxel size
+        boxes_.forget();  // the remembered key box is in units of the old voxel size
     }
     float get_voxel_size() const { return voxel_size_; }
     void set_min_voxel_count(const size_t n) { min_voxel_count_ = n; }
@@ -270,80 +367,18 @@ private:
     void run(const float* pts, size_t N, const RGBContainerShared* rgb, const IntensityContainerShared* inten,
              const TimestampContainerShared* ts, PointContainerShared& out_pts, RGBContainerShared* out_rgb,
              IntensityContainerShared* out_inten, TimestampContainerShared* out_ts) {
-        const size_t ws_bytes = sp_voxel_downsample_workspace_bytes(N);
-        // voxel count | boxed-path status | key box of sp_voxel_key_box (6 ints) | this cloud's key box, sharded
-        constexpr int kInfoInts = 32 + SP_VOXEL_BOX_SHARD_STRIDE * SP_VOXEL_BOX_SHARDS;
         hipStream_t st = queue_.stream();
-        detail::DeviceScratch ws(ws_bytes, st), info(kInfoInts * 4, st);
-        uint32_t* info_dev = static_cast<uint32_t*>(info.p);
-        static_assert(kInfoInts * 4 <= 4096, "pinned block");
-        int32_t h_own[kInfoInts];
-        int32_t* const h = detail::pinned_block_4k() ? static_cast<int32_t*>(detail::pinned_block_4k()) : h_own;  // (read-backs by DMA)
-        // The sort runs on keys compressed to the (widened) key box of the PREVIOUS cloud — scans of one sensor have similar
-        // extents; the device verifies that this cloud fits, and the key kernel finds this cloud's own box on the way (next
-        // call's guess; the exact box of the redo when the cloud did not fit). The first call has no guess and computes the
-        // box first: every call sorts compressed keys (the 64-bit sort is left for boxes of >= 2^32 cells).
-        // The call reports {voxels, points outside the box, this cloud's key box} in ONE record (sp_voxel_downsample_report): through
-        // host-mapped words the last kernel stores to and this thread spins on when they are to be had — no copy, no
-        // synchronisation: the scratch then goes back behind the stream's work — else through a copy and a wait.
-        const detail::MappedWord& mapped = detail::MappedWord::mine();
-        const bool poll = mapped.usable();
-        auto launch = [&](const int32_t* box) {
-            uint32_t* const report = poll ? mapped.dev : info_dev;
-            if (poll) mapped.arm();
-            throw_on_error(sp_voxel_downsample_report(
-                pts, N, voxel_size_inv_, min_voxel_count_, rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr,
-                inten ? inten->device_data() : nullptr, ts ? ts->device_data() : nullptr,
-                reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
-                rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
-                inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr, nullptr,
-                nullptr, box, report, ws.p, ws_bytes, st));
-            if (poll) {
-                h[0] = static_cast<int32_t>(mapped.wait(st));
-                std::atomic_thread_fence(std::memory_order_acquire);
-                for (int j = 1; j < 8; ++j) h[j] = static_cast<int32_t>(mapped.host[j]);
-                ws.stream_ordered = true;  // (kernels of the call may still be running: not idle, but ordered on st)
-                info.stream_ordered = true;
-            } else {
-                hip_check(hipMemcpyAsync(h, info.p, 32, hipMemcpyDeviceToHost, st), "D2H");
-                hip_check(hipStreamSynchronize(st), "sync");
-            }
-        };
-        if (!have_key_box_) {
-            throw_on_error(sp_voxel_key_box(pts, N, voxel_size_inv_, reinterpret_cast<int32_t*>(info_dev + 2), st));
-            hip_check(hipMemcpyAsync(h, info.p, 32, hipMemcpyDeviceToHost, st), "D2H");
-            hip_check(hipStreamSynchronize(st), "sync");
-            have_key_box_ = h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7];
-            for (int a = 0; a < 6; ++a) key_box_[a] = h[2 + a];
-        }
-        launch(have_key_box_ ? key_box_ : nullptr);
-        if (h[1] != 0) {  // the cloud left the remembered box: again, with its own
-            int32_t exact[6] = {h[2], h[3], h[4], h[5], h[6], h[7]};
-            launch(exact);
-        }
-        const bool had_box = have_key_box_;
-        have_key_box_ = h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7];
-        if (have_key_box_) {
-            // Keep what earlier clouds needed as well (one VoxelGrid usually serves several scans in turn — source and target of
-            // a registration —, and a guess that forgets the other scan is redone every call), unless that has grown to more
-            // than 8x the cells this cloud needs.
-            int32_t lo[3], hi[3], ulo[3], uhi[3];
-            double cells = 1.0, ucells = 1.0;
-            for (int a = 0; a < 3; ++a) {
-                const int32_t margin = std::max<int32_t>(2, (h[5 + a] - h[2 + a] + 1) / 8);
-                lo[a] = std::max<int32_t>(h[2 + a] - margin, 0);
-                hi[a] = std::min<int32_t>(h[5 + a] + margin, (1 << 21) - 1);
-                ulo[a] = had_box ? std::min(lo[a], key_box_[a]) : lo[a];
-                uhi[a] = had_box ? std::max(hi[a], key_box_[3 + a]) : hi[a];
-                cells *= double(hi[a] - lo[a] + 1);
-                ucells *= double(uhi[a] - ulo[a] + 1);
-            }
-            const bool keep = ucells <= 8.0 * cells;
-            for (int a = 0; a < 3; ++a) {
-                key_box_[a] = keep ? ulo[a] : lo[a];
-                key_box_[3 + a] = keep ? uhi[a] : hi[a];
-            }
-        }
+        const std::array<int32_t, 8> h = boxes_.run(
+            N, st, [&](int32_t* box6_dev) { throw_on_error(sp_voxel_key_box(pts, N, voxel_size_inv_, box6_dev, st)); },
+            [&](const int32_t* box, uint32_t* report, void* ws, size_t ws_bytes) {
+                throw_on_error(sp_voxel_downsample_report(
+                    pts, N, voxel_size_inv_, min_voxel_count_, rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr,
+                    inten ? inten->device_data() : nullptr, ts ? ts->device_data() : nullptr,
+                    reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
+                    rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
+                    inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr, nullptr,
+                    nullptr, box, report, ws, ws_bytes, st));
+            });
         const size_t V = static_cast<uint32_t>(h[0]);
         out_pts.set_device_size(V);
         if (V > 0 && h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7]) {
@@ -364,8 +399,127 @@ private:
     sycl_utils::DeviceQueue queue_;
     float voxel_size_ = 1.0f, voxel_size_inv_ = 1.0f;
     size_t min_voxel_count_ = 1;
-    int32_t key_box_[6] = {0, 0, 0, 0, 0, 0};  // widened key box of the previous cloud (the compressed sort's guess)
-    bool have_key_box_ = false;
+    detail::KeyBoxMemory boxes_;  // widened key box of the previous clouds (the compressed sort's guess)
+};
+
+/// filter/polar_downsampling.hpp:104-452. VoxelGrid's device path with the polar key (sp_polar_downsample_report): keys, sort and
+/// aggregation all on the device, where the reference sorts and walks the keys on the host. No bounds hint is left for the
+/// output (a box of polar key fields is not a Cartesian box): a grid built on it measures its own bounds.
+class PolarGrid {
+public:
+    using Ptr = std::shared_ptr<PolarGrid>;
+    PolarGrid(const sycl_utils::DeviceQueue& queue, float distance_voxel_size, float elevation_voxel_size, float azimuth_voxel_size,
+              CoordinateSystem coord = CoordinateSystem::LIDAR)
+        : queue_(queue), coord_(coord) {
+        if (distance_voxel_size <= 0.0f || elevation_voxel_size <= 0.0f || azimuth_voxel_size <= 0.0f)
+            throw std::invalid_argument("voxel sizes must be positive");
+        set_distance_voxel_size(distance_voxel_size);
+        set_elevation_voxel_size(elevation_voxel_size);
+        set_azimuth_voxel_size(azimuth_voxel_size);
+    }
+    void set_distance_voxel_size(const float size) {
+        if (size <= 0.0f) throw std::invalid_argument("distance_voxel_size must be positive");
+        distance_voxel_size_ = size;
+        distance_voxel_size_inv_ = 1.0f / size;
+        boxes_.forget();  // (the remembered key box is in units of the old size)
+    }
+    float get_distance_voxel_size() const { return distance_voxel_size_; }
+    void set_elevation_voxel_size(const float size) {
+        if (size <= 0.0f) throw std::invalid_argument("elevation_voxel_size must be positive");
+        elevation_voxel_size_ = size;
+        elevation_voxel_size_inv_ = 1.0f / size;
+        boxes_.forget();
+    }
+    float get_elevation_voxel_size() const { return elevation_voxel_size_; }
+    void set_azimuth_voxel_size(const float size) {
+        if (size <= 0.0f) throw std::invalid_argument("azimuth_voxel_size must be positive");
+        azimuth_voxel_size_ = size;
+        azimuth_voxel_size_inv_ = 1.0f / size;
+        boxes_.forget();
+    }
+    float get_azimuth_voxel_size() const { return azimuth_voxel_size_; }
+    void set_min_voxel_count(const size_t min_voxel_count) { min_voxel_count_ = min_voxel_count; }
+    size_t get_min_voxel_count() const { return min_voxel_count_; }
+    void set_coordinate_system(const CoordinateSystem coord) {
+        coord_ = coord;
+        boxes_.forget();
+    }
+    CoordinateSystem get_coordinate_system() const { return coord_; }
+
+    /// polar_downsampling.hpp:200-209 (in place allowed)
+    void downsampling(const PointContainerShared& points, PointContainerShared& result) {
+        const size_t N = points.size();
+        if (N == 0) { result.resize(0); return; }
+        // in place: the points are read again by a redo (a scan that left the remembered key box), so they are read from a copy
+        const bool in_place = &points == &result;
+        hipStream_t st = queue_.stream();
+        detail::DeviceScratch copy(in_place ? N * sizeof(PointType) : 0, st);
+        const float* src = reinterpret_cast<const float*>(points.device_data());
+        if (in_place) {
+            hip_check(hipMemcpyAsync(copy.p, src, N * sizeof(PointType), hipMemcpyDeviceToDevice, st), "D2D");
+            copy.stream_ordered = true;
+            src = static_cast<const float*>(copy.p);
+        }
+        run(src, N, nullptr, nullptr, nullptr, result, nullptr, nullptr, nullptr);
+    }
+    /// polar_downsampling.hpp:217-236 (in place allowed; start / end time kept when the cloud has timestamps)
+    void downsampling(const PointCloudShared& cloud, PointCloudShared& result) {
+        const size_t N = cloud.size();
+        if (N == 0) { result.resize_points(0); return; }
+        const bool in_place = (&cloud == &result) || (cloud.points == result.points);
+        PointCloudShared tmp(queue_);
+        PointCloudShared& out = in_place ? tmp : result;
+        run(cloud.points_device(), N, cloud.has_rgb() ? cloud.rgb.get() : nullptr,
+            cloud.has_intensity() ? cloud.intensities.get() : nullptr,
+            cloud.has_timestamps() ? cloud.timestamp_offsets.get() : nullptr, *out.points, out.rgb.get(), out.intensities.get(),
+            out.timestamp_offsets.get());
+        if (!cloud.has_rgb()) out.rgb->clear();
+        if (!cloud.has_intensity()) out.intensities->clear();
+        if (!cloud.has_timestamps()) out.timestamp_offsets->clear();
+        out.covs->clear();
+        out.normals->clear();
+        const double t0 = cloud.start_time_ms, t1 = cloud.end_time_ms;
+        const bool ts = cloud.has_timestamps();
+        if (in_place) {
+            result.points = tmp.points; result.rgb = tmp.rgb; result.intensities = tmp.intensities;
+            result.timestamp_offsets = tmp.timestamp_offsets; result.covs = tmp.covs; result.normals = tmp.normals;
+        }
+        if (ts) { result.start_time_ms = t0; result.end_time_ms = t1; }
+    }
+
+private:
+    void run(const float* pts, size_t N, const RGBContainerShared* rgb, const IntensityContainerShared* inten,
+             const TimestampContainerShared* ts, PointContainerShared& out_pts, RGBContainerShared* out_rgb,
+             IntensityContainerShared* out_inten, TimestampContainerShared* out_ts) {
+        hipStream_t st = queue_.stream();
+        const int coord = static_cast<int>(coord_);
+        const std::array<int32_t, 8> h = boxes_.run(
+            N, st,
+            [&](int32_t* box6_dev) {
+                throw_on_error(sp_polar_key_box(pts, N, coord, distance_voxel_size_inv_, elevation_voxel_size_inv_,
+                                                azimuth_voxel_size_inv_, box6_dev, st));
+            },
+            [&](const int32_t* box, uint32_t* report, void* ws, size_t ws_bytes) {
+                throw_on_error(sp_polar_downsample_report(
+                    pts, N, coord, distance_voxel_size_inv_, elevation_voxel_size_inv_, azimuth_voxel_size_inv_, min_voxel_count_,
+                    rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr, inten ? inten->device_data() : nullptr,
+                    ts ? ts->device_data() : nullptr, reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
+                    rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
+                    inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr, nullptr,
+                    nullptr, box, report, ws, ws_bytes, st));
+            });
+        const size_t V = static_cast<uint32_t>(h[0]);
+        out_pts.set_device_size(V);
+        if (rgb) out_rgb->set_device_size(V);
+        if (inten) out_inten->set_device_size(V);
+        if (ts) out_ts->set_device_size(V);
+    }
+    sycl_utils::DeviceQueue queue_;
+    float distance_voxel_size_ = 1.0f, elevation_voxel_size_ = 1.0f, azimuth_voxel_size_ = 1.0f;
+    float distance_voxel_size_inv_ = 1.0f, elevation_voxel_size_inv_ = 1.0f, azimuth_voxel_size_inv_ = 1.0f;
+    size_t min_voxel_count_ = 1;
+    CoordinateSystem coord_;
+    detail::KeyBoxMemory boxes_;  // widened key box of the previous clouds (the compressed sort's guess)
 };
 
 /// common/filter_by_flags.hpp:15-99 — stable compaction on the device (sp_compact_by_flags).

@@ -309,6 +309,37 @@ int sp_voxel_downsample_report(const float* points, size_t n, float inv_voxel_si
                                uint32_t* n_out_dev_opt, const int32_t* box6_host, uint32_t* report8, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* --------------------------------------------------------------------------------------- polar grid */
+
+/* PolarGrid (filter/polar_downsampling.hpp:104-452): VoxelGrid's device path with the polar key in place of the Cartesian one.
+ * coord: SP_COORD_LIDAR (azimuth = atan2(y, x), elevation = atan2(z, sqrt(x^2 + y^2))) or SP_COORD_CAMERA (azimuth = atan2(x, z),
+ * elevation = atan2(-y, sqrt(x^2 + z^2))), algorithms/common/coordinate_system.hpp. d_inv, e_inv, a_inv: 1.0f / the distance,
+ * elevation and azimuth voxel sizes (radians for the angles), computed once on the host (polar_downsampling.hpp:116-118).
+ * An invalid coord or an inverse size that is not positive and finite: SP_ERR_INVALID_ARGUMENT. */
+enum { SP_COORD_LIDAR = 0, SP_COORD_CAMERA = 1 };
+
+/* kernel::compute_polar_bit<coord> (polar_downsampling.hpp:30-100): DISTANCE in bits 0-20, POLAR (elevation) in 21-41, AZIMUTH
+ * in 42-62; ~0 for a non-finite point, r == 0, a zero horizontal term or a field outside [0, 2^21). The angles come from the
+ * library's own atan2f (within 2 ulp of the correctly rounded value), not the device's: sp_polar_keys_host computes the same
+ * keys bit for bit on the host (points_host, keys_out_host: host memory). */
+int sp_polar_keys(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv, uint64_t* keys_out,
+                  void* stream);
+int sp_polar_keys_host(const float* points_host, size_t n, int coord, float d_inv, float e_inv, float a_inv,
+                       uint64_t* keys_out_host);
+/* sp_voxel_key_box for the polar key: box6 = min, max of the distance, elevation and azimuth fields. */
+int sp_polar_key_box(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv, int32_t* box6_dev,
+                     void* stream);
+/* PolarGrid::downsampling (polar_downsampling.hpp:200-236, 316-440): sp_voxel_downsample_report with the polar key — the same
+ * 8-word report record (box6_host and report8[2..7] are boxes of the polar fields), the same outputs per voxel (mean of points,
+ * rgb and timestamps, median of intensities; point_sum.w < min_voxel_count dropped; ascending key order; within a voxel points
+ * summed in ascending index order), the same workspace: sp_voxel_downsample_workspace_bytes(n). The key host std::sort and
+ * sequential walk of the reference are replaced by the device radix sort and segmented reduction. */
+int sp_polar_downsample_report(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv,
+                               size_t min_voxel_count, const float* rgb, const float* intensities, const float* timestamps,
+                               float* points_out, float* rgb_out, float* intensities_out, float* timestamps_out,
+                               uint64_t* keys_out_opt, uint32_t* n_out_dev_opt, const int32_t* box6_host, uint32_t* report8,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------- transform */
 
 /* transform::transform_async (algorithms/common/transform.hpp:14-37, 45-94, kernel K14); in place allowed;

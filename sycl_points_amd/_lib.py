@@ -144,6 +144,11 @@ SIGNATURES = {
     "sp_voxel_key_box": (_i, [_vp, _sz, _f, _vp, _vp]),
     "sp_voxel_downsample_boxed": (_i, [_vp, _sz, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_voxel_downsample_report": (_i, [_vp, _sz, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_polar_keys": (_i, [_vp, _sz, _i, _f, _f, _f, _vp, _vp]),
+    "sp_polar_keys_host": (_i, [_vp, _sz, _i, _f, _f, _f, _vp]),
+    "sp_polar_key_box": (_i, [_vp, _sz, _i, _f, _f, _f, _vp, _vp]),
+    "sp_polar_downsample_report": (_i, [_vp, _sz, _i, _f, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _sz, _vp]),
     "sp_transform": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sp_box_filter_flags": (_i, [_vp, _sz, _f, _f, _vp, _vp]),
     "sp_compact_workspace_bytes": (_sz, [_sz]),
@@ -229,8 +234,10 @@ INTERNAL_SIGNATURES = {
     "sp_internal_align_searched_log": (_vp, [_vp, _vp]),
     "sp_internal_radix_sort_workspace_bytes": (_sz, [_sz]),
     "sp_internal_radix_sort_u32": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]),
+    "sp_internal_atan2f_host": (None, [_vp, _vp, _sz, _vp]),
 }
 VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOXEL_BOX_SHARD_STRIDE
+COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA
 INTERNAL_OPTION = {"stage_mask": 0, "reuse": 1, "fast_nn": 2, "self_knn_mode": 3, "persistent": 4, "persistent_from": 5,
                    "bvh_self_heap": 6, "bvh_sort_queries": 7, "grid_sort_queries": 8, "opt_wave_query": 9, "opt_fuse_trials": 10}
 

@@ -3,7 +3,8 @@
 Names, argument meaning and error behaviour follow the reference (paths relative to
 /root/reference/cpp/include/sycl_points/): PointCloudShared (points/point_cloud.hpp:73-476), KNNResult
 (algorithms/knn/result.hpp), KNNBase / KDTree / knn_search_bruteforce (algorithms/knn/), covariance::estimate*
-(algorithms/feature/covariance.hpp), VoxelGrid (algorithms/filter/voxel_downsampling.hpp), Registration
+(algorithms/feature/covariance.hpp), VoxelGrid (algorithms/filter/voxel_downsampling.hpp), PolarGrid
+(algorithms/filter/polar_downsampling.hpp), Registration
 (algorithms/registration/registration.hpp). Every array is a torch CUDA tensor resident in HBM; torch is used for
 device memory, streams and torch.distributed only — all compute goes through libsycl_points_amd.so.
 """
@@ -596,68 +597,150 @@ class VoxelGrid:
         reference's host aggregation does. boxed=True sorts keys compressed to the (widened) bounding box of the PREVIOUS
         cloud's voxel coordinates — scans of one sensor have similar extents — verifies on the device that the cloud fits,
         and falls back to the 64-bit sort when it does not: identical results either way."""
-        pc = cloud if isinstance(cloud, PointCloudShared) else PointCloudShared(cloud)
-        p = _dev_f32(pc.points, 4)
-        n = p.shape[0]
-        out = PointCloudShared(device=p.device)
-        if n == 0:
-            return (out, torch.empty(0, dtype=torch.int64, device=p.device)) if return_keys else out
         L = _lib.lib()
-        nbytes = L.sp_voxel_downsample_workspace_bytes(n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
-        o_p = torch.empty((n, 4), dtype=torch.float32, device=p.device)
-        rgb = pc.rgb if pc.has_rgb() else None
-        inten = pc.intensities if pc.has_intensity() else None
-        ts = pc.timestamp_offsets if pc.has_timestamps() else None
-        o_c = torch.empty((n, 4), dtype=torch.float32, device=p.device) if rgb is not None else None
-        o_i = torch.empty(n, dtype=torch.float32, device=p.device) if inten is not None else None
-        o_t = torch.empty(n, dtype=torch.float32, device=p.device) if ts is not None else None
-        o_k = torch.empty(n, dtype=torch.int64, device=p.device) if return_keys else None
-        # One read-back at the end: voxel count, boxed-path status, and this cloud's key box (sharded, found by the key
-        # kernel on the way), which the NEXT call uses, widened by a margin, to sort keys compressed to that box. A cloud that
-        # leaves the remembered box is detected (status != 0) and redone with its own exact box, so results never depend on
-        # the guess. The first call of a VoxelGrid has no guess: it computes the box first (sp_voxel_key_box, one small
-        # read-back) — every call sorts compressed keys; the 64-bit sort is left for boxes of >= 2^32 cells.
-        # (sp_voxel_downsample_report: all of it in ONE 8-word record the call's last kernel stores — no status word and sharded
-        # box to initialise and fold)
-        info = torch.zeros(16, dtype=torch.int32, device=p.device)
-        base = info.data_ptr()
-        args = (_ptr(p), n, self.voxel_size_inv, self.min_voxel_count, _ptr(rgb), _ptr(inten), _ptr(ts), _ptr(o_p), _ptr(o_c),
-                _ptr(o_i), _ptr(o_t), _ptr(o_k), None)
+        return _boxed_downsampling(self, cloud, return_keys, boxed,
+                                   lambda p, n, box6: L.sp_voxel_key_box(p, n, self.voxel_size_inv, box6, _stream()),
+                                   lambda p, n, rest: L.sp_voxel_downsample_report(p, n, self.voxel_size_inv, self.min_voxel_count,
+                                                                                   *rest))
 
-        def run(box):
-            check(L.sp_voxel_downsample_report(*args, None if box is None else box.ctypes.data_as(C.c_void_p),
-                                               C.c_void_p(base), _ptr(ws), nbytes, _stream()))
-            c = info.cpu().numpy()
-            return c, c[2:8].astype(np.int64)
 
-        guess = getattr(self, "_key_box", None) if boxed else None
-        if guess is None and boxed:
-            check(L.sp_voxel_key_box(_ptr(p), n, self.voxel_size_inv, C.c_void_p(base + 32), _stream()))
-            b0 = info[8:14].cpu().numpy().astype(np.int64)
-            guess = np.ascontiguousarray(b0.astype(np.int32)) if (b0[:3] <= b0[3:]).all() else None
-        counts, box = run(guess)
-        if counts[1] != 0:  # the cloud left the remembered box: again, with its own
-            counts, box = run(np.ascontiguousarray(box.astype(np.int32)))
-        if boxed and (box[:3] <= box[3:]).all():
-            margin = np.maximum(2, (box[3:] - box[:3] + 1) // 8)
-            lo = np.maximum(box[:3] - margin, 0)
-            hi = np.minimum(box[3:] + margin, (1 << 21) - 1)
-            # Keep what earlier clouds needed as well (one VoxelGrid usually serves several scans in turn — source and target
-            # of a registration —, and a guess that forgets the other scan is redone every call), unless that has grown to
-            # more than 8x the cells this cloud needs.
-            prev = getattr(self, "_key_box", None)
-            if prev is not None:
-                ulo, uhi = np.minimum(lo, prev[:3]), np.maximum(hi, prev[3:])
-                if np.prod((uhi - ulo + 1).astype(np.float64)) <= 8.0 * np.prod((hi - lo + 1).astype(np.float64)):
-                    lo, hi = ulo, uhi
-            self._key_box = np.ascontiguousarray(np.concatenate([lo, hi]).astype(np.int32))
-        v = int(counts[0])
-        out.points = o_p[:v]
-        out.rgb = None if o_c is None else o_c[:v]
-        out.intensities = None if o_i is None else o_i[:v]
-        out.timestamp_offsets = None if o_t is None else o_t[:v]
-        return (out, o_k[:v]) if return_keys else out
+def _boxed_downsampling(grid, cloud, return_keys, boxed, key_box, report):
+    """VoxelGrid / PolarGrid.downsampling over sp_voxel_downsample_report / sp_polar_downsample_report. key_box(points, n, box6)
+    and report(points, n, rest) call the C entry points with the grid's own key arguments; grid._key_box is the remembered box."""
+    pc = cloud if isinstance(cloud, PointCloudShared) else PointCloudShared(cloud)
+    p = _dev_f32(pc.points, 4)
+    n = p.shape[0]
+    out = PointCloudShared(device=p.device)
+    if n == 0:
+        return (out, torch.empty(0, dtype=torch.int64, device=p.device)) if return_keys else out
+    L = _lib.lib()
+    nbytes = L.sp_voxel_downsample_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    o_p = torch.empty((n, 4), dtype=torch.float32, device=p.device)
+    rgb = pc.rgb if pc.has_rgb() else None
+    inten = pc.intensities if pc.has_intensity() else None
+    ts = pc.timestamp_offsets if pc.has_timestamps() else None
+    o_c = torch.empty((n, 4), dtype=torch.float32, device=p.device) if rgb is not None else None
+    o_i = torch.empty(n, dtype=torch.float32, device=p.device) if inten is not None else None
+    o_t = torch.empty(n, dtype=torch.float32, device=p.device) if ts is not None else None
+    o_k = torch.empty(n, dtype=torch.int64, device=p.device) if return_keys else None
+    # One read-back at the end: voxel count, boxed-path status, and this cloud's key box (sharded, found by the key
+    # kernel on the way), which the NEXT call uses, widened by a margin, to sort keys compressed to that box. A cloud that
+    # leaves the remembered box is detected (status != 0) and redone with its own exact box, so results never depend on
+    # the guess. The first call of a grid has no guess: it computes the box first (the key-box call, one small
+    # read-back) — every call sorts compressed keys; the 64-bit sort is left for boxes of >= 2^32 cells.
+    # (the report call: all of it in ONE 8-word record the call's last kernel stores — no status word and sharded
+    # box to initialise and fold)
+    info = torch.zeros(16, dtype=torch.int32, device=p.device)
+    base = info.data_ptr()
+    args = (_ptr(rgb), _ptr(inten), _ptr(ts), _ptr(o_p), _ptr(o_c), _ptr(o_i), _ptr(o_t), _ptr(o_k), None)
+
+    def run(box):
+        check(report(_ptr(p), n, args + (None if box is None else box.ctypes.data_as(C.c_void_p), C.c_void_p(base), _ptr(ws),
+                                         nbytes, _stream())))
+        c = info.cpu().numpy()
+        return c, c[2:8].astype(np.int64)
+
+    guess = getattr(grid, "_key_box", None) if boxed else None
+    if guess is None and boxed:
+        check(key_box(_ptr(p), n, C.c_void_p(base + 32)))
+        b0 = info[8:14].cpu().numpy().astype(np.int64)
+        guess = np.ascontiguousarray(b0.astype(np.int32)) if (b0[:3] <= b0[3:]).all() else None
+    counts, box = run(guess)
+    if counts[1] != 0:  # the cloud left the remembered box: again, with its own
+        counts, box = run(np.ascontiguousarray(box.astype(np.int32)))
+    if boxed and (box[:3] <= box[3:]).all():
+        margin = np.maximum(2, (box[3:] - box[:3] + 1) // 8)
+        lo = np.maximum(box[:3] - margin, 0)
+        hi = np.minimum(box[3:] + margin, (1 << 21) - 1)
+        # Keep what earlier clouds needed as well (one grid usually serves several scans in turn — source and target
+        # of a registration —, and a guess that forgets the other scan is redone every call), unless that has grown to
+        # more than 8x the cells this cloud needs.
+        prev = getattr(grid, "_key_box", None)
+        if prev is not None:
+            ulo, uhi = np.minimum(lo, prev[:3]), np.maximum(hi, prev[3:])
+            if np.prod((uhi - ulo + 1).astype(np.float64)) <= 8.0 * np.prod((hi - lo + 1).astype(np.float64)):
+                lo, hi = ulo, uhi
+        grid._key_box = np.ascontiguousarray(np.concatenate([lo, hi]).astype(np.int32))
+    v = int(counts[0])
+    out.points = o_p[:v]
+    out.rgb = None if o_c is None else o_c[:v]
+    out.intensities = None if o_i is None else o_i[:v]
+    out.timestamp_offsets = None if o_t is None else o_t[:v]
+    return (out, o_k[:v]) if return_keys else out
+
+
+# ------------------------------------------------------------------ polar grid
+COORDINATE_SYSTEMS = ("LIDAR", "CAMERA")  # algorithms/common/coordinate_system.hpp:11
+
+
+def coordinate_system_from_string(s):
+    """coordinate_system.hpp:13-24: "lidar" / "camera" in any case; anything else raises."""
+    u = str(s).upper()
+    if u not in _lib.COORD:
+        raise SpError(1, f"Invalid coordinate system: {s}")
+    return u
+
+
+class PolarGrid:
+    """algorithms/filter/polar_downsampling.hpp:104-452: VoxelGrid's device path with the polar key (distance, elevation,
+    azimuth). coord: "LIDAR" (default) or "CAMERA"; the angle sizes are in radians."""
+
+    def __init__(self, distance_voxel_size, elevation_voxel_size, azimuth_voxel_size, coord="LIDAR"):
+        if distance_voxel_size <= 0.0 or elevation_voxel_size <= 0.0 or azimuth_voxel_size <= 0.0:
+            raise SpError(1, "voxel sizes must be positive")
+        self.coord = coordinate_system_from_string(coord)
+        self.set_distance_voxel_size(distance_voxel_size)
+        self.set_elevation_voxel_size(elevation_voxel_size)
+        self.set_azimuth_voxel_size(azimuth_voxel_size)
+        self.min_voxel_count = 1
+
+    def _size(self, name, v):
+        if v <= 0.0:
+            raise SpError(1, f"{name}_voxel_size must be positive")
+        setattr(self, f"{name}_voxel_size", float(v))
+        setattr(self, f"{name}_voxel_size_inv", float(np.float32(1.0) / np.float32(v)))
+        self._key_box = None  # the remembered key box is in units of the old size
+
+    def set_distance_voxel_size(self, v): self._size("distance", v)  # noqa: E704
+    def get_distance_voxel_size(self): return self.distance_voxel_size  # noqa: E704
+    def set_elevation_voxel_size(self, v): self._size("elevation", v)  # noqa: E704
+    def get_elevation_voxel_size(self): return self.elevation_voxel_size  # noqa: E704
+    def set_azimuth_voxel_size(self, v): self._size("azimuth", v)  # noqa: E704
+    def get_azimuth_voxel_size(self): return self.azimuth_voxel_size  # noqa: E704
+
+    def set_min_voxel_count(self, n):
+        self.min_voxel_count = int(n)
+
+    def get_min_voxel_count(self):
+        return self.min_voxel_count
+
+    def set_coordinate_system(self, coord):
+        self.coord = coordinate_system_from_string(coord)
+        self._key_box = None
+
+    def get_coordinate_system(self):
+        return self.coord
+
+    def _key_args(self):
+        return (_lib.COORD[self.coord], self.distance_voxel_size_inv, self.elevation_voxel_size_inv, self.azimuth_voxel_size_inv)
+
+    def compute_polar_bit(self, points):
+        """kernel::compute_polar_bit (polar_downsampling.hpp:30-100) of every point, on the device: int64 tensor holding the
+        bit patterns of the uint64 keys (~0: invalid)."""
+        p = _dev_f32(_points_of(points), 4)
+        keys = torch.empty(p.shape[0], dtype=torch.int64, device=p.device)
+        check(_lib.lib().sp_polar_keys(_ptr(p), p.shape[0], *self._key_args(), _ptr(keys), _stream()))
+        return keys
+
+    def downsampling(self, cloud, return_keys=False, boxed=True):
+        """downsampling(cloud, result) (polar_downsampling.hpp:200-236), with VoxelGrid.downsampling's calling shape and
+        protocol (keys compressed to the remembered box of the previous clouds' polar fields; a redo when a cloud leaves it)."""
+        L = _lib.lib()
+        k = self._key_args()
+        return _boxed_downsampling(self, cloud, return_keys, boxed,
+                                   lambda p, n, box6: L.sp_polar_key_box(p, n, *k, box6, _stream()),
+                                   lambda p, n, rest: L.sp_polar_downsample_report(p, n, *k, self.min_voxel_count, *rest))
 
 
 # ------------------------------------------------------------------ transform / filters

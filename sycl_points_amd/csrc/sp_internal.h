@@ -65,6 +65,8 @@ const uint32_t* sp_internal_align_searched_log(void* workspace, size_t* n_entrie
 size_t sp_internal_radix_sort_workspace_bytes(size_t n);
 int sp_internal_radix_sort_u32(uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
                                unsigned bits, void* workspace, size_t workspace_bytes, int* result_in_b_out, void* stream);
+/* sp_math.h's atan2f (the one the polar keys are made of) on the host, element by element: out[i] = atan2(y[i], x[i]). */
+void sp_internal_atan2f_host(const float* y, const float* x, size_t n, float* out);
 
 #ifdef __cplusplus
 }

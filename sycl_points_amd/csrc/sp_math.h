@@ -578,4 +578,71 @@ SP_HD DoglegStep6 dogleg_step6(const float* H, const float* g, float radius, Ldl
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------- polar coordinates
+// atan2f of this library's own, for filter/polar_downsampling.hpp:30-100 (compute_polar_bit). The device's atan2f (ocml) and
+// the host's (glibc) are different algorithms and cannot be made to agree bit for bit; this one uses only operations that are
+// correctly rounded in both builds (+, -, *, /, explicit fmaf), so a key computed on the host equals the key the device computes.
+// |x| and |y| are ordered so that t = min / max lies in [0, 1]; atan(t) = t + t s P(s), s = t^2, P a degree-8 minimax
+// polynomial (relative error 2.6e-9 in exact arithmetic) evaluated by Horner with fmaf; the octant is restored with pi / 2 and pi
+// split into a float and its remainder. Measured error <= 2 ulp of the correctly rounded result over finite inputs
+// (tests/test_polar_grid_cpu.py). C99 rules for signed zeros: atan2(+-0, +0) = +-0, atan2(+-0, -0) = +-pi, atan2(+-0, x < 0) = +-pi,
+// atan2(y, +-0) = +-pi / 2.
+SP_HD float sp_atan2f(float y, float x) {
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool swap = ay > ax;
+    const float mx = swap ? ay : ax, mn = swap ? ax : ay;
+    const float t = mx > 0.0f ? mn / mx : 0.0f;
+    const float s = t * t;
+    float p = -0x1.d62fecp-10f;
+    p = fmaf(p, s, 0x1.65a65ap-7f);
+    p = fmaf(p, s, -0x1.fed15ep-6f);
+    p = fmaf(p, s, 0x1.dac9e2p-5f);
+    p = fmaf(p, s, -0x1.583490p-4f);
+    p = fmaf(p, s, 0x1.c099fep-4f);
+    p = fmaf(p, s, -0x1.2421b6p-3f);
+    p = fmaf(p, s, 0x1.9991fep-3f);
+    p = fmaf(p, s, -0x1.55553ep-2f);
+    const float r = fmaf(t * s, p, t);  // atan(t), t in [0, 1]
+    constexpr float kPio2Hi = 0x1.921fb6p+0f, kPio2Lo = -0x1.777a5cp-25f;  // pi / 2 = hi + lo
+    constexpr float kPiHi = 0x1.921fb6p+1f, kPiLo = -0x1.777a5cp-24f;
+    const bool neg = (__builtin_bit_cast(uint32_t, x) >> 31) != 0u;  // -0 counts as negative (atan2(+-0, -0) = +-pi)
+    float a = r;
+    if (swap) a = kPio2Hi + (neg ? kPio2Lo + r : kPio2Lo - r);
+    else if (neg) a = kPiHi + (kPiLo - r);
+    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, a) | (__builtin_bit_cast(uint32_t, y) & 0x80000000u));
+}
+
+enum : int { kCoordLidar = 0, kCoordCamera = 1 };  // algorithms/common/coordinate_system.hpp (REP-103)
+
+// The three fields of kernel::compute_polar_bit<COORD> (polar_downsampling.hpp:30-100) before the 2^20 offset is added:
+// c0 distance, c1 elevation, c2 azimuth; false when the key is invalid (a non-finite coordinate, r == 0, a zero horizontal
+// term, a field outside [0, 2^21)). The products are compared with the field range as floats BEFORE they are converted, so an
+// overflow (x^2 = inf: r = inf) makes the key invalid instead of an out-of-range conversion.
+template <int COORD>
+SP_HD bool polar_coords(float x, float y, float z, float d_inv, float e_inv, float a_inv, int& c0, int& c1, int& c2) {
+    if (!(fabsf(x) <= FLT_MAX) || !(fabsf(y) <= FLT_MAX) || !(fabsf(z) <= FLT_MAX)) return false;
+    const float xx = x * x, yy = y * y, zz = z * z;
+    const float r = sqrtf(xx + yy + zz);  // (x^2 + y^2) + z^2, the reference's order
+    if (r == 0.0f) return false;
+    const float h2 = COORD == kCoordLidar ? xx + yy : xx + zz;
+    if (h2 == 0.0f) return false;
+    const float h = sqrtf(h2);
+    const float az = COORD == kCoordLidar ? sp_atan2f(y, x) : sp_atan2f(x, z);
+    const float el = COORD == kCoordLidar ? sp_atan2f(z, h) : sp_atan2f(-y, h);
+    const float q0 = r * d_inv, q1 = el * e_inv, q2 = az * a_inv;
+    constexpr float lim = 1048576.0f;  // floor(q) + 2^20 in [0, 2^21)  <=>  q in [-2^20, 2^20)
+    if (!(q0 >= -lim && q0 < lim && q1 >= -lim && q1 < lim && q2 >= -lim && q2 < lim)) return false;
+    c0 = (int)floorf(q0) + (1 << 20);
+    c1 = (int)floorf(q1) + (1 << 20);
+    c2 = (int)floorf(q2) + (1 << 20);
+    return true;
+}
+// The 63-bit key: DISTANCE in bits 0-20, POLAR (elevation) in 21-41, AZIMUTH in 42-62 (voxel_constants.hpp:27-31); ~0 invalid.
+template <int COORD>
+SP_HD uint64_t polar_key(float x, float y, float z, float d_inv, float e_inv, float a_inv) {
+    int c0, c1, c2;
+    if (!polar_coords<COORD>(x, y, z, d_inv, e_inv, a_inv, c0, c1, c2)) return ~0ull;
+    return (uint64_t)c0 | ((uint64_t)c1 << 21) | ((uint64_t)c2 << 42);
+}
+
 }  // namespace sp

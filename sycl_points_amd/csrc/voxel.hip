@@ -10,10 +10,12 @@
 // Sort and scan are this library's own (radix_sort.hip: stable LSD radix sort of 32- or 64-bit keys, look-back scan); the
 // key, aggregation and scatter kernels are written here. Headline algorithmic bytes: 40 B/pt (key kernel + one
 // aggregation pass).
+#include <cstdio>
 #include <cstring>
 
 #include "radix_sort.h"
 #include "sp_common.h"
+#include "sp_internal.h"
 #include "sp_math.h"
 #include "sp_wave_select.h"
 
@@ -36,10 +38,28 @@ __device__ __forceinline__ uint64_t voxel_key(const float4 p, float inv) {
     return ((uint64_t)(c0 & mask)) | ((uint64_t)(c1 & mask) << 21) | ((uint64_t)(c2 & mask) << 42);
 }
 
-__global__ __launch_bounds__(kBlock) void key_kernel(const float4* __restrict__ pts, unsigned n, float inv,
+// Coordinate policies of the key kernels below (key_kernel, key_box_kernel, key32_kernel, key32_tiles_kernel): the 63-bit key
+// of a point and its three 21-bit fields c0 | c1 << 21 | c2 << 42 (false: the key is invalid). Everything after the keys — the
+// sort, the aggregation, the scatter, the report — sees only keys and is shared.
+struct CartesianKey {  // compute_voxel_bit: x, y, z
+    float inv;
+    __device__ __forceinline__ uint64_t key(const float4 p) const { return voxel_key(p, inv); }
+    __device__ __forceinline__ bool coords(const float4 p, int& c0, int& c1, int& c2) const;
+};
+template <int COORD>
+struct PolarKey {  // compute_polar_bit<COORD>: distance, elevation, azimuth (sp_math.h)
+    float d_inv, e_inv, a_inv;
+    __device__ __forceinline__ uint64_t key(const float4 p) const { return polar_key<COORD>(p.x, p.y, p.z, d_inv, e_inv, a_inv); }
+    __device__ __forceinline__ bool coords(const float4 p, int& c0, int& c1, int& c2) const {
+        return polar_coords<COORD>(p.x, p.y, p.z, d_inv, e_inv, a_inv, c0, c1, c2);
+    }
+};
+
+template <class POL>
+__global__ __launch_bounds__(kBlock) void key_kernel(const float4* __restrict__ pts, unsigned n, const POL pol,
                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        keys[i] = voxel_key(pts[i], inv);
+        keys[i] = pol.key(pts[i]);
         if (vals) vals[i] = i;
     }
 }
@@ -55,6 +75,9 @@ __device__ __forceinline__ bool voxel_coords(const float4 p, float inv, int& c0,
     c0 = (int)a; c1 = (int)b; c2 = (int)c;
     return true;
 }
+__device__ __forceinline__ bool CartesianKey::coords(const float4 p, int& c0, int& c1, int& c2) const {
+    return voxel_coords(p, inv, c0, c1, c2);
+}
 
 // Bounding box of the voxel coordinates (integer atomics: order-independent). box = {min x,y,z, max x,y,z}.
 __global__ void box_init_kernel(int32_t* box, bool eight = false) {  // eight: a whole record of voxel_report (no point outside)
@@ -62,7 +85,8 @@ __global__ void box_init_kernel(int32_t* box, bool eight = false) {  // eight: a
     else if (threadIdx.x < 6) box[threadIdx.x] = INT32_MIN;
     else if (eight && threadIdx.x < 8) box[threadIdx.x] = 0;
 }
-__global__ __launch_bounds__(kBlock) void key_box_kernel(const float4* __restrict__ pts, unsigned n, float inv,
+template <class POL>
+__global__ __launch_bounds__(kBlock) void key_box_kernel(const float4* __restrict__ pts, unsigned n, const POL pol,
                                                          int32_t* __restrict__ box) {
     int lo0 = INT32_MAX, lo1 = INT32_MAX, lo2 = INT32_MAX, hi0 = INT32_MIN, hi1 = INT32_MIN, hi2 = INT32_MIN;
     // four independent loads per trip (the loop is a latency chain otherwise: 13.8 us per 1M points with one)
@@ -74,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void key_box_kernel(const float4* __restric
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             int c0, c1, c2;
-            if (i + u * stride < n && voxel_coords(p[u], inv, c0, c1, c2)) {
+            if (i + u * stride < n && pol.coords(p[u], c0, c1, c2)) {
                 lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
                 hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
             }
@@ -119,7 +143,8 @@ __global__ __launch_bounds__(kBlock) void voxel_init_kernel(uint32_t* status, in
 // way (the next call's guess; the exact box for a redo when the cloud left the one it was given) — a separate pass over the
 // points cost 13.8 us per 1M. Sharded, every shard on a 128-byte line of its own: atomics on one LINE queue up at the L2
 // (two thousand workgroups on sixteen shards packed into six lines took 12 us); the caller folds the shards.
-__global__ __launch_bounds__(kBlock) void key32_kernel(const float4* __restrict__ pts, unsigned n, float inv, KeyBox b,
+template <class POL>
+__global__ __launch_bounds__(kBlock) void key32_kernel(const float4* __restrict__ pts, unsigned n, const POL pol, KeyBox b,
                                                        uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                        uint32_t* __restrict__ status, int32_t* __restrict__ box_shards,
                                                        int32_t* __restrict__ wg_records = nullptr) {
@@ -140,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void key32_kernel(const float4* __restrict_
             if (i >= n) continue;
             int c0, c1, c2;
             uint32_t key = b.invalid;
-            if (voxel_coords(p[u], inv, c0, c1, c2)) {
+            if (pol.coords(p[u], c0, c1, c2)) {
                 lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
                 hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
                 const unsigned x = (unsigned)(c0 - b.x0), y = (unsigned)(c1 - b.y0), z = (unsigned)(c2 - b.z0);
@@ -225,8 +250,8 @@ __global__ __launch_bounds__(kBlock) void voxel_report_kernel(const int32_t* __r
 // key32_kernel for sp_voxel_downsample_report, tile by tile of the sort that follows (radix_sort.h, RadixFirstPass): the keys are
 // in registers here, so the sort's first count — a launch and a read of every key — is this kernel's by-product:
 // tile_hist[digit * tiles + tile] for every digit of the first pass. One record per workgroup as in key32_kernel.
-template <int BINS>
-__global__ __launch_bounds__(kBlock) void key32_tiles_kernel(const float4* __restrict__ pts, unsigned n, float inv, KeyBox b,
+template <class POL, int BINS>
+__global__ __launch_bounds__(kBlock) void key32_tiles_kernel(const float4* __restrict__ pts, unsigned n, const POL pol, KeyBox b,
                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                              int32_t* __restrict__ wg_records, unsigned tiles, unsigned tile_keys,
                                                              unsigned mask, unsigned* __restrict__ tile_hist) {
@@ -249,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void key32_tiles_kernel(const float4* __res
             if (i >= n) continue;
             int c0, c1, c2;
             uint32_t key = b.invalid;
-            if (voxel_coords(p[c], inv, c0, c1, c2)) {
+            if (pol.coords(p[c], c0, c1, c2)) {
                 lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
                 hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
                 const unsigned x = (unsigned)(c0 - b.x0), y = (unsigned)(c1 - b.y0), z = (unsigned)(c2 - b.z0);
@@ -616,7 +641,7 @@ extern "C" int sp_voxel_keys(const float* points, size_t n, float inv_voxel_size
     using namespace sp;
     if (n == 0) return SP_OK;
     key_kernel<<<stream_grid(n), kBlock, 0, as_stream(stream)>>>(reinterpret_cast<const float4*>(points), (unsigned)n,
-                                                                 inv_voxel_size, keys_out, nullptr);
+                                                                 CartesianKey{inv_voxel_size}, keys_out, nullptr);
     return launch_status();
 }
 
@@ -624,27 +649,29 @@ extern "C" size_t sp_voxel_downsample_workspace_bytes(size_t n) { return n ? sp:
 
 namespace sp {
 namespace {
-int voxel_downsample_impl(const float* points, size_t n, float inv_voxel_size, size_t min_voxel_count, const float* rgb,
+// VoxelGrid::downsampling with POL = CartesianKey, PolarGrid::downsampling with POL = PolarKey<COORD> (the caller has checked the
+// policy's arguments); `who` names the operation in error messages.
+template <class POL>
+int voxel_downsample_impl(const POL pol, const char* who, const float* points, size_t n, size_t min_voxel_count, const float* rgb,
                           const float* intensities, const float* timestamps, float* points_out, float* rgb_out,
                           float* intensities_out, float* timestamps_out, uint64_t* keys_out_opt, uint32_t* n_out_dev,
                           const int32_t* box6_host, uint32_t* status_dev, int32_t* box_shards_dev, void* workspace,
                           size_t workspace_bytes, hipStream_t st, uint32_t* report8 = nullptr) {
-    if (!(inv_voxel_size > 0.0f)) {
-        sp_set_error("voxel_size must be positive");  // voxel_downsampling.hpp:23-25
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    char msg[128];
     if (status_dev || box_shards_dev) voxel_init_kernel<<<1, kBlock, 0, st>>>(status_dev, box_shards_dev);
     if (n == 0) {
         if (report8) voxel_report_kernel<<<1, kBlock, 0, st>>>(nullptr, 0u, nullptr, report8);  // {0, 0, empty box}
         return n_out_dev ? zero_async(n_out_dev, 4, st) : launch_status();
     }
     if (n >= (1ull << 32)) {
-        sp_set_error("[VoxelGrid::downsampling] more than 2^32 points");
+        snprintf(msg, sizeof(msg), "[%s] more than 2^32 points", who);
+        sp_set_error(msg);
         return SP_ERR_INVALID_ARGUMENT;
     }
     const VoxelWs w = voxel_ws(n);
     if (!workspace || workspace_bytes < w.total) {
-        sp_set_error("[VoxelGrid::downsampling] workspace too small (sp_voxel_downsample_workspace_bytes)");
+        snprintf(msg, sizeof(msg), "[%s] workspace too small (sp_voxel_downsample_workspace_bytes)", who);
+        sp_set_error(msg);
         return SP_ERR_INVALID_ARGUMENT;
     }
     char* base = static_cast<char*>(workspace);
@@ -689,18 +716,19 @@ int voxel_downsample_impl(const float* points, size_t n, float inv_voxel_size, s
             key_grid = std::min(fp.tiles, kKeyGridMax);
             unsigned* const hist = reinterpret_cast<unsigned*>(base + w.prim);
             if (fp.digit_bits == 9u)
-                key32_tiles_kernel<512><<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, kb, k_in, vals_in, records, fp.tiles,
+                key32_tiles_kernel<POL, 512><<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, pol, kb, k_in, vals_in, records, fp.tiles,
                                                                      fp.tile_keys, fp.mask, hist);
             else
-                key32_tiles_kernel<256><<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, kb, k_in, vals_in, records, fp.tiles,
+                key32_tiles_kernel<POL, 256><<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, pol, kb, k_in, vals_in, records, fp.tiles,
                                                                      fp.tile_keys, fp.mask, hist);
         } else {
-            key32_kernel<<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, kb, k_in, vals_in, status_dev, box_shards_dev,
+            key32_kernel<POL><<<key_grid, kBlock, 0, st>>>(pts, (unsigned)n, pol, kb, k_in, vals_in, status_dev, box_shards_dev,
                                                       records);
         }
         bool in_b = false;  // the hand-written sort (radix_sort.hip) ping-pongs between the two buffer pairs
         if (radix_sort_pairs_u32(k_in, k_sorted, vals_in, vals_sorted, n, end_bit, base + w.prim, w.prim_bytes, &in_b, st, 0, counted) != SP_OK) {
-            sp_set_error("[VoxelGrid::downsampling] radix sort failed");
+            snprintf(msg, sizeof(msg), "[%s] radix sort failed", who);
+        sp_set_error(msg);
             return SP_ERR_HIP;
         }
         if (!in_b) { uint32_t* t = k_in; k_in = k_sorted; k_sorted = t; t = vals_in; vals_in = vals_sorted; vals_sorted = t; }
@@ -723,21 +751,22 @@ int voxel_downsample_impl(const float* points, size_t n, float inv_voxel_size, s
     uint64_t* keys_in = (uint64_t*)(base + w.keys_in);
     uint64_t* keys_sorted = (uint64_t*)(base + w.keys_out);
     // no usable box (none given, or one of >= 2^32 cells): the 63-bit keys themselves, eight passes of the same sort
-    key_kernel<<<stream_grid(n), kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, keys_in, vals_in);
+    key_kernel<POL><<<stream_grid(n), kBlock, 0, st>>>(pts, (unsigned)n, pol, keys_in, vals_in);
     if (records) {  // this cloud's box for the report: one record, by integer atomics (no point is "outside": there is no box)
         unsigned grid = div_up(n, kBlock * 16);
         if (grid > 256u) grid = 256u;
         box_init_kernel<<<1, 64, 0, st>>>(records, true);
-        key_box_kernel<<<grid ? grid : 1u, kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, records);
+        key_box_kernel<POL><<<grid ? grid : 1u, kBlock, 0, st>>>(pts, (unsigned)n, pol, records);
     }
     if (box_shards_dev) {  // this cloud's box for the caller, as on the boxed path
         unsigned grid = div_up(n, kBlock * 16);
         if (grid > 256u) grid = 256u;
-        key_box_kernel<<<grid ? grid : 1u, kBlock, 0, st>>>(pts, (unsigned)n, inv_voxel_size, box_shards_dev);
+        key_box_kernel<POL><<<grid ? grid : 1u, kBlock, 0, st>>>(pts, (unsigned)n, pol, box_shards_dev);
     }
     bool in_b64 = false;
     if (radix_sort_pairs_u64(keys_in, keys_sorted, vals_in, vals_sorted, n, 64, base + w.prim, w.prim_bytes, &in_b64, st) != SP_OK) {
-        sp_set_error("[VoxelGrid::downsampling] radix sort failed");
+        snprintf(msg, sizeof(msg), "[%s] radix sort failed", who);
+        sp_set_error(msg);
         return SP_ERR_HIP;
     }
     if (!in_b64) { uint64_t* t = keys_in; keys_in = keys_sorted; keys_sorted = t; uint32_t* tv = vals_in; vals_in = vals_sorted; vals_sorted = tv; }
@@ -757,6 +786,38 @@ int voxel_downsample_impl(const float* points, size_t n, float inv_voxel_size, s
     if (report8) voxel_report_kernel<<<1, kBlock, 0, st>>>(records, 1u, total, report8);
     return launch_status();
 }
+// sp_voxel_key_box / sp_polar_key_box: the key box of a cloud by integer atomics on box6_dev
+template <class POL>
+int key_box_impl(const float* points, size_t n, const POL pol, int32_t* box6_dev, hipStream_t st) {
+    box_init_kernel<<<1, 64, 0, st>>>(box6_dev);
+    if (n) {
+        unsigned grid = div_up(n, kBlock * 16);  // few workgroups: their six atomics each meet on the same six words
+        if (grid > 256u) grid = 256u;            // (977 workgroups: 25.8 us per 1M points; 245 with one load per trip: 13.8)
+        key_box_kernel<POL><<<grid ? grid : 1u, kBlock, 0, st>>>(reinterpret_cast<const float4*>(points), (unsigned)n, pol, box6_dev);
+    }
+    return launch_status();
+}
+
+bool voxel_size_ok(float inv_voxel_size) {
+    if (inv_voxel_size > 0.0f) return true;
+    sp_set_error("voxel_size must be positive");  // voxel_downsampling.hpp:23-25
+    return false;
+}
+
+// The polar twins' arguments: the coordinate system (coordinate_system.hpp) and three positive, finite inverse sizes
+// (polar_downsampling.hpp:116-118: the constructor and every setter throw on a size <= 0).
+bool polar_args_ok(int coord, float d_inv, float e_inv, float a_inv) {
+    if (coord != kCoordLidar && coord != kCoordCamera) {
+        sp_set_error("[PolarGrid] coordinate system must be 0 (LIDAR) or 1 (CAMERA)");
+        return false;
+    }
+    const auto ok = [](float v) { return v > 0.0f && v <= FLT_MAX; };
+    if (!ok(d_inv) || !ok(e_inv) || !ok(a_inv)) {
+        sp_set_error("[PolarGrid] voxel sizes must be positive");
+        return false;
+    }
+    return true;
+}
 }  // namespace
 }  // namespace sp
 
@@ -765,23 +826,15 @@ extern "C" int sp_voxel_downsample(const float* points, size_t n, float inv_voxe
                                    float* points_out, float* rgb_out, float* intensities_out, float* timestamps_out,
                                    uint64_t* keys_out_opt, uint32_t* n_out_dev, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    return sp::voxel_downsample_impl(points, n, inv_voxel_size, min_voxel_count, rgb, intensities, timestamps, points_out,
-                                     rgb_out, intensities_out, timestamps_out, keys_out_opt, n_out_dev, nullptr, nullptr, nullptr,
-                                     workspace, workspace_bytes, sp::as_stream(stream));
+    if (!sp::voxel_size_ok(inv_voxel_size)) return SP_ERR_INVALID_ARGUMENT;
+    return sp::voxel_downsample_impl(sp::CartesianKey{inv_voxel_size}, "VoxelGrid::downsampling", points, n, min_voxel_count, rgb,
+                                     intensities, timestamps, points_out, rgb_out, intensities_out, timestamps_out, keys_out_opt,
+                                     n_out_dev, nullptr, nullptr, nullptr, workspace, workspace_bytes, sp::as_stream(stream));
 }
 
 extern "C" int sp_voxel_key_box(const float* points, size_t n, float inv_voxel_size, int32_t* box6_dev, void* stream) {
-    using namespace sp;
     if (!box6_dev) return SP_ERR_INVALID_ARGUMENT;
-    hipStream_t st = as_stream(stream);
-    box_init_kernel<<<1, 64, 0, st>>>(box6_dev);
-    if (n) {
-        unsigned grid = div_up(n, kBlock * 16);  // few workgroups: their six atomics each meet on the same six words
-        if (grid > 256u) grid = 256u;            // (977 workgroups: 25.8 us per 1M points; 245 with one load per trip: 13.8)
-        key_box_kernel<<<grid ? grid : 1u, kBlock, 0, st>>>(reinterpret_cast<const float4*>(points), (unsigned)n,
-                                                            inv_voxel_size, box6_dev);
-    }
-    return launch_status();
+    return sp::key_box_impl(points, n, sp::CartesianKey{inv_voxel_size}, box6_dev, sp::as_stream(stream));
 }
 
 extern "C" int sp_voxel_downsample_boxed(const float* points, size_t n, float inv_voxel_size, size_t min_voxel_count,
@@ -790,9 +843,11 @@ extern "C" int sp_voxel_downsample_boxed(const float* points, size_t n, float in
                                          float* timestamps_out, uint64_t* keys_out_opt, uint32_t* n_out_dev,
                                          const int32_t* box6_host, uint32_t* status_dev_opt, int32_t* box_shards_dev_opt,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-    return sp::voxel_downsample_impl(points, n, inv_voxel_size, min_voxel_count, rgb, intensities, timestamps, points_out,
-                                     rgb_out, intensities_out, timestamps_out, keys_out_opt, n_out_dev, box6_host,
-                                     status_dev_opt, box_shards_dev_opt, workspace, workspace_bytes, sp::as_stream(stream));
+    if (!sp::voxel_size_ok(inv_voxel_size)) return SP_ERR_INVALID_ARGUMENT;
+    return sp::voxel_downsample_impl(sp::CartesianKey{inv_voxel_size}, "VoxelGrid::downsampling", points, n, min_voxel_count, rgb,
+                                     intensities, timestamps, points_out, rgb_out, intensities_out, timestamps_out, keys_out_opt,
+                                     n_out_dev, box6_host, status_dev_opt, box_shards_dev_opt, workspace, workspace_bytes,
+                                     sp::as_stream(stream));
 }
 
 extern "C" int sp_voxel_downsample_report(const float* points, size_t n, float inv_voxel_size, size_t min_voxel_count,
@@ -802,9 +857,69 @@ extern "C" int sp_voxel_downsample_report(const float* points, size_t n, float i
                                           const int32_t* box6_host, uint32_t* report8, void* workspace, size_t workspace_bytes,
                                           void* stream) {
     if (!report8) return SP_ERR_INVALID_ARGUMENT;
-    return sp::voxel_downsample_impl(points, n, inv_voxel_size, min_voxel_count, rgb, intensities, timestamps, points_out,
-                                     rgb_out, intensities_out, timestamps_out, keys_out_opt, n_out_dev_opt, box6_host, nullptr,
-                                     nullptr, workspace, workspace_bytes, sp::as_stream(stream), report8);
+    if (!sp::voxel_size_ok(inv_voxel_size)) return SP_ERR_INVALID_ARGUMENT;
+    return sp::voxel_downsample_impl(sp::CartesianKey{inv_voxel_size}, "VoxelGrid::downsampling", points, n, min_voxel_count, rgb,
+                                     intensities, timestamps, points_out, rgb_out, intensities_out, timestamps_out, keys_out_opt,
+                                     n_out_dev_opt, box6_host, nullptr, nullptr, workspace, workspace_bytes, sp::as_stream(stream),
+                                     report8);
+}
+
+// ---- polar grid: the same path with the polar key (filter/polar_downsampling.hpp)
+extern "C" int sp_polar_keys(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv, uint64_t* keys_out,
+                             void* stream) {
+    using namespace sp;
+    if (!polar_args_ok(coord, d_inv, e_inv, a_inv)) return SP_ERR_INVALID_ARGUMENT;
+    if (n == 0) return SP_OK;
+    const float4* pts = reinterpret_cast<const float4*>(points);
+    if (coord == kCoordLidar)
+        key_kernel<<<stream_grid(n), kBlock, 0, as_stream(stream)>>>(pts, (unsigned)n, PolarKey<kCoordLidar>{d_inv, e_inv, a_inv}, keys_out, nullptr);
+    else
+        key_kernel<<<stream_grid(n), kBlock, 0, as_stream(stream)>>>(pts, (unsigned)n, PolarKey<kCoordCamera>{d_inv, e_inv, a_inv}, keys_out, nullptr);
+    return launch_status();
+}
+
+extern "C" int sp_polar_keys_host(const float* points_host, size_t n, int coord, float d_inv, float e_inv, float a_inv,
+                                  uint64_t* keys_out_host) {
+    using namespace sp;
+    if (!polar_args_ok(coord, d_inv, e_inv, a_inv)) return SP_ERR_INVALID_ARGUMENT;
+    if (n && (!points_host || !keys_out_host)) return SP_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = points_host + 4 * i;
+        keys_out_host[i] = coord == kCoordLidar ? polar_key<kCoordLidar>(p[0], p[1], p[2], d_inv, e_inv, a_inv)
+                                                : polar_key<kCoordCamera>(p[0], p[1], p[2], d_inv, e_inv, a_inv);
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_polar_key_box(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv, int32_t* box6_dev,
+                                void* stream) {
+    using namespace sp;
+    if (!box6_dev) return SP_ERR_INVALID_ARGUMENT;
+    if (!polar_args_ok(coord, d_inv, e_inv, a_inv)) return SP_ERR_INVALID_ARGUMENT;
+    if (coord == kCoordLidar) return key_box_impl(points, n, PolarKey<kCoordLidar>{d_inv, e_inv, a_inv}, box6_dev, as_stream(stream));
+    return key_box_impl(points, n, PolarKey<kCoordCamera>{d_inv, e_inv, a_inv}, box6_dev, as_stream(stream));
+}
+
+extern "C" int sp_polar_downsample_report(const float* points, size_t n, int coord, float d_inv, float e_inv, float a_inv,
+                                          size_t min_voxel_count, const float* rgb, const float* intensities, const float* timestamps,
+                                          float* points_out, float* rgb_out, float* intensities_out, float* timestamps_out,
+                                          uint64_t* keys_out_opt, uint32_t* n_out_dev_opt, const int32_t* box6_host, uint32_t* report8,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace sp;
+    if (!report8) return SP_ERR_INVALID_ARGUMENT;
+    if (!polar_args_ok(coord, d_inv, e_inv, a_inv)) return SP_ERR_INVALID_ARGUMENT;
+    if (coord == kCoordLidar)
+        return voxel_downsample_impl(PolarKey<kCoordLidar>{d_inv, e_inv, a_inv}, "PolarGrid::downsampling", points, n, min_voxel_count,
+                                     rgb, intensities, timestamps, points_out, rgb_out, intensities_out, timestamps_out, keys_out_opt,
+                                     n_out_dev_opt, box6_host, nullptr, nullptr, workspace, workspace_bytes, as_stream(stream), report8);
+    return voxel_downsample_impl(PolarKey<kCoordCamera>{d_inv, e_inv, a_inv}, "PolarGrid::downsampling", points, n, min_voxel_count,
+                                 rgb, intensities, timestamps, points_out, rgb_out, intensities_out, timestamps_out, keys_out_opt,
+                                 n_out_dev_opt, box6_host, nullptr, nullptr, workspace, workspace_bytes, as_stream(stream), report8);
+}
+
+// the function sp_polar_keys_host's keys are made of, for its accuracy test (sp_internal.h)
+extern "C" void sp_internal_atan2f_host(const float* y, const float* x, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = sp::sp_atan2f(y[i], x[i]);
 }
 
 extern "C" int sp_box_filter_flags(const float* points, size_t n, float min_distance, float max_distance,
