@@ -561,14 +561,15 @@ private:
     sycl_utils::DeviceQueue queue_;
 };
 
-/// filter/preprocess_filter.hpp — the two operators the hot path's callers use (box filter, random sampling).
+/// filter/preprocess_filter.hpp — the operators the hot path's callers use (box filter, random sampling, farthest point sampling).
 class PreprocessFilter {
 public:
     using Ptr = std::shared_ptr<PreprocessFilter>;
-    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), by_flags_(queue), mt_(1234) {
+    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), by_flags_(queue), mt_(1234), fps_mt_(1234) {
         flags_ = std::make_shared<shared_vector<uint8_t>>(queue);
     }
-    void set_random_seed(uint_fast32_t seed) { mt_.seed(seed); }
+    /// preprocess_filter.hpp:46-51: every sampling operator has a generator of its own; the call seeds them all
+    void set_random_seed(uint_fast32_t seed) { mt_.seed(seed); fps_mt_.seed(seed); }
 
     /// preprocess_operator/box_filter_operator.hpp:24-54 (K10 on the device, compaction on the device)
     void box_filter(const PointCloudShared& source, PointCloudShared& output, float min_distance = 1.0f,
@@ -605,6 +606,47 @@ public:
         gather_rows(source, output, picked);
     }
     void random_sampling(PointCloudShared& data, size_t sampling_num) { random_sampling(data, data, sampling_num); }
+    /// preprocess_operator/farthest_point_sampling_operator.hpp:27-91. The first index is the reference's draw from the
+    /// operator's own mt19937 (fps_mt_); the chain of argmax decisions runs on the device (sp_farthest_point_sampling: the
+    /// reference goes back to the host once per sample); the kept rows, in the cloud's own order, move through the flags path.
+    /// Kept from the reference: N <= sampling_num copies the source (an empty one too); sampling_num == 0 keeps the one random
+    /// first point; duplicates and NaN points select an index again, so fewer than sampling_num points may come out. Time
+    /// stamps follow filter_by_flags (preprocess_filter.hpp:198-227): end = start + the largest kept offset; a cloud without
+    /// offsets gets start = end = 0.
+    void farthest_point_sampling(const PointCloudShared& source, PointCloudShared& output, size_t sampling_num) {
+        const size_t N = source.size();
+        if (N <= sampling_num) {
+            if (&source != &output) output = PointCloudShared(source);
+            return;
+        }
+        std::uniform_int_distribution<size_t> dist(0, N - 1);
+        const uint32_t first = static_cast<uint32_t>(dist(fps_mt_));
+        const size_t S = std::max<size_t>(sampling_num, 1);  // (the reference's loop starts at 1: sampling_num 0 keeps the first)
+        hipStream_t st = queue_.stream();
+        const size_t ws_bytes = sp_fps_workspace_bytes(N, S);
+        detail::DeviceScratch ws(ws_bytes, st), order(S * sizeof(uint32_t), st);
+        ws.stream_ordered = order.stream_ordered = true;  // (used on st only)
+        auto run = [&] {
+            throw_on_error(sp_farthest_point_sampling(reinterpret_cast<const float*>(source.points->device_data()), N, S, first,
+                                                      static_cast<uint32_t*>(order.p), flags_->device_data_for_write(N), nullptr,
+                                                      ws.p, ws_bytes, st));
+            return sp_fps_status(ws.p, st);
+        };
+        // a persistent launch whose bounded wait ran out leaves the sample incomplete: the library then takes the per-sample form
+        int rc = run();
+        if (rc == SP_ERR_RUNTIME) rc = run();
+        throw_on_error(rc);
+        apply_flags(source, output);
+        if (output.has_timestamps()) {
+            const auto& off = *output.timestamp_offsets;
+            output.end_time_ms = off.empty() ? output.start_time_ms
+                                             : output.start_time_ms + static_cast<double>(*std::max_element(off.begin(), off.end()));
+        } else {
+            output.start_time_ms = 0.0;
+            output.end_time_ms = 0.0;
+        }
+    }
+    void farthest_point_sampling(PointCloudShared& data, size_t sampling_num) { farthest_point_sampling(data, data, sampling_num); }
 
 private:
     /// output = the rows `picked` of every attribute of source (sp_gather_rows_multi)
@@ -717,6 +759,7 @@ private:
     FilterByFlags by_flags_;
     shared_vector_ptr<uint8_t> flags_;
     std::mt19937 mt_;
+    std::mt19937 fps_mt_;  // farthest point sampling's own generator (preprocess_filter.hpp:46-51)
 };
 
 }  // namespace filter

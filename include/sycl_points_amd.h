@@ -383,6 +383,29 @@ int sp_box_filter_compact_multi(const float* points, size_t n, float min_distanc
 int sp_gather_rows_multi(const void* const* rows, const size_t* row_bytes, void* const* rows_out, int n_arrays,
                          const uint32_t* indices, size_t m, void* stream);
 
+/* Farthest point sampling (filter/preprocess_operator/farthest_point_sampling_operator.hpp:27-91), the chain of argmax
+ * decisions on the device: the reference runs a parallel_for, a wait and a host std::max_element over all n distances per
+ * sample; here no sample goes back to the host. points: float4[n]; d[] starts at FLT_MAX; sample 0 is first_index (the
+ * reference draws it from the operator's own std::mt19937, :51-53), then sampling_num - 1 steps of
+ *   d[i] = sycl::min(d[i], |p[i] - p[sel]|^2)   (the fma chain over x, y, z AND w, eigen_utils.hpp:245-253, :333-335; the
+ *                                                min is (y < x) ? y : x, so a NaN distance leaves d[i] as it was)
+ *   sel  = the FIRST index of max d             (std::max_element: the lowest index wins a tie)
+ * order_out[i] = the i-th selected index, repeats included (a cloud whose remaining distances are all 0 selects the same
+ * index again); flags_out_opt[i] = 1 when i was selected, else 0; min_d2_out_opt = d after the last step. Bit-identical to
+ * the reference. n == 0 or >= 2^32, a null points / order_out / workspace, first_index >= n, sampling_num == 0 or > n ->
+ * SP_ERR_INVALID_ARGUMENT before any HIP call. Only enqueues (graph-capturable: under capture it takes a form whose
+ * workgroups never wait for each other). workspace: sp_fps_workspace_bytes(n, sampling_num).
+ *   sp_fps_status   clouds of 16 k to 2 M points may run as ONE persistent launch whose workgroups wait for each other; every
+ *                   wait is bounded, and one that runs out (another process holding compute units) leaves the sample
+ *                   incomplete and sets a status word in the workspace. This call reads it (it synchronises the stream):
+ *                   SP_OK, or SP_ERR_RUNTIME, after which the next sp_farthest_point_sampling on the device takes a form
+ *                   without waits: call it again. */
+size_t sp_fps_workspace_bytes(size_t n, size_t sampling_num);
+int sp_farthest_point_sampling(const float* points, size_t n, size_t sampling_num, uint32_t first_index, uint32_t* order_out,
+                               uint8_t* flags_out_opt, float* min_d2_out_opt, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int sp_fps_status(const void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------- registration */
 
 /* RegType (algorithms/registration/factor.hpp:18-32) and RobustLossType (algorithms/robust/robust.hpp:13-19). */

@@ -155,6 +155,9 @@ SIGNATURES = {
     "sp_compact_by_flags": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_compact_by_flags_multi": (_i, [_vp, _vp, _vp, _i, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_gather_rows_multi": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "sp_fps_workspace_bytes": (_sz, [_sz, _sz]),
+    "sp_farthest_point_sampling": (_i, [_vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_fps_status": (_i, [_vp, _vp]),
     "sp_box_filter_compact_multi": (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_gicp_workspace_bytes": (_sz, [_sz]),
     "sp_gicp_linearize": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FactorParams), _vp, _vp, _sz, _vp]),
@@ -235,9 +238,11 @@ INTERNAL_SIGNATURES = {
     "sp_internal_radix_sort_workspace_bytes": (_sz, [_sz]),
     "sp_internal_radix_sort_u32": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]),
     "sp_internal_atan2f_host": (None, [_vp, _vp, _sz, _vp]),
+    "sp_internal_fps": (_i, [_i, _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOXEL_BOX_SHARD_STRIDE
 COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA
+FPS_FORM = {"auto": 0, "one_workgroup": 1, "per_sample": 2, "persistent": 3}  # sp_internal_fps's form
 INTERNAL_OPTION = {"stage_mask": 0, "reuse": 1, "fast_nn": 2, "self_knn_mode": 3, "persistent": 4, "persistent_from": 5,
                    "bvh_self_heap": 6, "bvh_sort_queries": 7, "grid_sort_queries": 8, "opt_wave_query": 9, "opt_fuse_trials": 10}
 

@@ -794,6 +794,39 @@ def compact_by_flags(rows, flags, want_indices=False):
     return (out[:v], idx) if want_indices else out[:v]
 
 
+@dataclass
+class FpsResult:
+    order: torch.Tensor   # int32 [S]: the i-th selected index, repeats included
+    flags: torch.Tensor   # uint8 [N]: 1 selected, 0 not
+    min_d2: torch.Tensor  # float32 [N]: each point's squared distance to the nearest selected point (before the last selection)
+
+
+def farthest_point_sampling(points, sampling_num, first_index, form=None):
+    """FarthestPointSamplingOperator::apply's chain of argmax decisions (filter/preprocess_operator/
+    farthest_point_sampling_operator.hpp:27-91) on the device, from `first_index` (the reference draws it from the operator's
+    own std::mt19937: PreprocessFilter.farthest_point_sampling in the C++ facade does that draw). Bit-identical to the
+    reference. `form` ("one_workgroup" / "persistent" / "per_sample") forces one of the library's forms (sp_internal_fps),
+    for tests and timing; None lets the library choose. A persistent launch whose bounded wait ran out (sp_fps_status) is
+    run again at once; the library then takes the per-sample form."""
+    L = _lib.lib()
+    p = _dev_f32(_points_of(points), 4)
+    n = p.shape[0]
+    order = torch.empty(max(int(sampling_num), 1), dtype=torch.int32, device=p.device)
+    flags = torch.empty(n, dtype=torch.uint8, device=p.device)
+    d = torch.empty(n, dtype=torch.float32, device=p.device)
+    nbytes = L.sp_fps_workspace_bytes(n, sampling_num)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    args = (_ptr(p), n, sampling_num, first_index, _ptr(order), _ptr(flags), _ptr(d), _ptr(ws), nbytes, _stream())
+    if form is None:
+        check(L.sp_farthest_point_sampling(*args))
+        if L.sp_fps_status(_ptr(ws), _stream()) == _lib.SP_ERR_RUNTIME:
+            check(L.sp_farthest_point_sampling(*args))
+    else:
+        check(L.sp_internal_fps(_lib.FPS_FORM[form], *args))
+    check(L.sp_fps_status(_ptr(ws), _stream()))
+    return FpsResult(order, flags, d)
+
+
 class Communicator:
     """sp_comm: the library's own RCCL communicator (one process per GPU). The 128-byte unique id is made by rank 0
     (sp_comm_unique_id) and handed to the other ranks through whatever channel the application has — here a

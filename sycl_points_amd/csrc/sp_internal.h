@@ -67,6 +67,12 @@ int sp_internal_radix_sort_u32(uint32_t* keys_a, uint32_t* keys_b, uint32_t* val
                                unsigned bits, void* workspace, size_t workspace_bytes, int* result_in_b_out, void* stream);
 /* sp_math.h's atan2f (the one the polar keys are made of) on the host, element by element: out[i] = atan2(y[i], x[i]). */
 void sp_internal_atan2f_host(const float* y, const float* x, size_t n, float* out);
+/* sp_farthest_point_sampling in a form of the caller's choice (low byte): 0 the library's choice (what the public entry does),
+ * 1 one workgroup (n <= 16384, else SP_ERR_INVALID_ARGUMENT), 2 a launch per sample, 3 persistent (n <= 2^21; SP_ERR_RUNTIME
+ * when the guard is not to be had). Second byte, for the timing script's sweeps: form 2's grid cap in units of 256 workgroups,
+ * form 3's points per lane (1, 2, 4, 8); 0 the library's choice. Same order, flags and distances in every form. */
+int sp_internal_fps(int form, const float* points, size_t n, size_t sampling_num, uint32_t first_index, uint32_t* order_out,
+                    uint8_t* flags_out_opt, float* min_d2_out_opt, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
