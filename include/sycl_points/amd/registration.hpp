@@ -12,6 +12,7 @@
 #include <cctype>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <optional>
 #include <vector>
 #include <iostream>
@@ -240,8 +241,6 @@ public:
         rotation_robust_scale_ = options.rotation_robust_scale > 0.0f ? options.rotation_robust_scale
                                                                       : params_.rotation_constraint.robust.default_scale;
         const bool pose_terms = params_.degenerate_reg.type != DegenerateRegularizationType::none || prior_active();
-        float lm_lambda = params_.lm.init_lambda;
-        float trust_region_radius = params_.dogleg.initial_trust_region_radius;
         const auto* grid = dynamic_cast<const knn::GridKNN*>(&target_knn);
         // A caller that still hands over the reference's KDTree gets the same correspondences (exact nearest neighbours;
         // only the order of exactly equidistant points can differ) from a GridKNN built on the target once per tree.
@@ -283,25 +282,42 @@ public:
             throw std::runtime_error("[Registration::align] a communicator is set: only the device-resident Gauss-Newton loop "
                                      "(GICP / POINT_TO_DISTRIBUTION on a GridKNN, no host-side pose terms) is sharded");
 
-        for (size_t iter = 0; iter < params_.max_iterations; ++iter) {
-            LinearizedResult lin = fused ? linearize_fused(source.size(), result.T.matrix(), robust_scale)
-                                         : linearize_generic(source, target, nn, result.T.matrix(), robust_scale);
-            result.H_raw = lin.H; result.b_raw = lin.b; result.error_raw = lin.error;
-            if (pose_terms) apply_pose_terms(lin, result.T.matrix(), initial_guess);  // registration.hpp:249-253
-            switch (params_.optimization_method) {
-                case OptimizationMethod::LEVENBERG_MARQUARDT:
-                    optimize_levenberg_marquardt(source, target, result, lin, lm_lambda, iter, robust_scale);
-                    break;
-                case OptimizationMethod::GAUSS_NEWTON:
-                    optimize_gauss_newton(result, lin, iter);
-                    break;
-                case OptimizationMethod::POWELL_DOGLEG:
-                    optimize_powell_dogleg(source, target, result, lin, trust_region_radius, iter, robust_scale);
-                    break;
+        // The host-driven loop: every decision of the optimiser (:803-964) is the library's stepper's — the state machine the
+        // device-resident launch runs (csrc/sp_optimizer.h); this loop linearises and evaluates trials where it asks for them.
+        const sp_opt_params op = opt_params();
+        sp_opt_stepper* st = nullptr;
+        throw_on_error(sp_opt_stepper_create(&op, initial_guess.data(), &robust_scale, 1, &st));
+        const std::unique_ptr<sp_opt_stepper, void (*)(sp_opt_stepper*)> owner(st, sp_opt_stepper_destroy);
+        for (;;) {
+            sp_opt_request req;
+            throw_on_error(sp_opt_stepper_next(st, &req));
+            if (req.want == SP_OPT_WANT_DONE) break;
+            TransformMatrix T;
+            std::memcpy(T.data(), req.T, sizeof req.T);
+            if (req.want == SP_OPT_WANT_LINEARIZE) {
+                LinearizedResult lin = fused ? linearize_fused(source.size(), T, robust_scale)
+                                             : linearize_generic(source, target, nn, T, robust_scale);
+                result.H_raw = lin.H; result.b_raw = lin.b; result.error_raw = lin.error;
+                if (pose_terms) apply_pose_terms(lin, T, initial_guess);  // registration.hpp:249-253
+                const sp_linearized h = to_linearized(lin);
+                throw_on_error(sp_opt_stepper_linearized(st, &h));
+                if (params_.verbose && params_.optimization_method == OptimizationMethod::GAUSS_NEWTON)
+                    std::cout << "iter [" << req.iteration << "] error: " << lin.error << ", inlier: " << lin.inlier << std::endl;
+            } else {
+                const auto [icp_error, inlier] = compute_error(source, target, T, robust_scale);
+                const float new_error = icp_error + prior_error(T);  // registration.hpp:854, :933
+                float rho = 0.0f;
+                throw_on_error(sp_opt_stepper_trial(st, new_error, inlier, &rho));
+                if (params_.verbose && params_.optimization_method == OptimizationMethod::POWELL_DOGLEG)
+                    std::cout << "iter [" << req.iteration << "] radius: " << req.damping << ", rho: " << rho
+                              << ", error: " << new_error << ", inlier: " << inlier << std::endl;
             }
-            if (result.converged) break;
         }
-        return result;
+        sp_align_result r;
+        throw_on_error(sp_opt_stepper_result(st, &r));
+        RegistrationResult out = to_registration_result(r);
+        out.H_raw = result.H_raw; out.b_raw = result.b_raw; out.error_raw = result.error_raw;
+        return out;
     }
 
     /// MI355X extension: pipeline::RobustAligner's annealing loop (pipeline/robust.hpp:100-111) — one align() per robust scale,
@@ -433,31 +449,17 @@ private:
         const sp_degenerate_reg_params dr{int(params_.degenerate_reg.type), params_.degenerate_reg.rot_eigenvalue_threshold,
                                           params_.degenerate_reg.trans_eigenvalue_threshold,
                                           params_.degenerate_reg.base_factor};
-        float H36[36], b6[6];
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) H36[i * 6 + j] = lin.H(i, j);
-            b6[i] = lin.b(i);
-        }
-        throw_on_error(sp_degenerate_regularize_host(&dr, H36, b6, lin.inlier, T.data(), T_initial.data()));
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) lin.H(i, j) = H36[i * 6 + j];
-            lin.b(i) = b6[i];
-        }
+        sp_linearized h = to_linearized(lin);
+        throw_on_error(sp_degenerate_regularize_host(&dr, h.H, h.b, h.inlier, T.data(), T_initial.data()));
+        lin = to_result(h);
     }
     /// DegenerateRegularization::regularize then MapPrior::apply on the reduced system (registration.hpp:249-253)
     void apply_pose_terms(LinearizedResult& lin, const TransformMatrix& T, const TransformMatrix& T_initial) const {
         regularize(lin, T, T_initial);
         if (!prior_active()) return;
-        float H36[36], b6[6];
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) H36[i * 6 + j] = lin.H(i, j);
-            b6[i] = lin.b(i);
-        }
-        sp_map_prior_apply_host(&map_prior_, T.data(), H36, b6, &lin.error);
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) lin.H(i, j) = H36[i * 6 + j];
-            lin.b(i) = b6[i];
-        }
+        sp_linearized h = to_linearized(lin);
+        sp_map_prior_apply_host(&map_prior_, T.data(), h.H, h.b, &h.error);
+        lin = to_result(h);
     }
     static LinearizedResult to_result(const sp_linearized& h) {
         LinearizedResult r;
@@ -468,6 +470,32 @@ private:
         r.error = h.error;
         r.inlier = h.inlier;
         return r;
+    }
+    static sp_linearized to_linearized(const LinearizedResult& lin) {
+        sp_linearized h{};
+        for (int i = 0; i < 6; ++i) {
+            for (int j = 0; j < 6; ++j) h.H[i * 6 + j] = lin.H(i, j);
+            h.b[i] = lin.b(i);
+        }
+        h.error = lin.error;
+        h.inlier = lin.inlier;
+        return h;
+    }
+    /// sp_align_result (the device-resident optimiser's result block, the host stepper's read-out) as a RegistrationResult;
+    /// H_raw / b_raw / error_raw as they are without host-side pose terms
+    static RegistrationResult to_registration_result(const sp_align_result& h) {
+        RegistrationResult result;
+        for (int i = 0; i < 16; ++i) result.T.matrix().data()[i] = h.T[i];
+        result.iterations = h.iterations;
+        result.converged = h.converged != 0;
+        for (int i = 0; i < 6; ++i) {
+            for (int j = 0; j < 6; ++j) result.H(i, j) = h.H[i * 6 + j];
+            result.b(i) = h.b[i];
+        }
+        result.error = h.error;
+        result.inlier = h.inlier;
+        result.H_raw = result.H; result.b_raw = result.b; result.error_raw = h.error_raw;
+        return result;
     }
     sp_linearized read_lin() const {  // the reference's wait_and_throw + toCPU(0) (registration.hpp:674-675)
         sp_linearized* const h = static_cast<sp_linearized*>(pin_);
@@ -614,23 +642,11 @@ private:
             throw_on_error(sp_gicp_source_set_persistent(psrc_, 0));  // this source: per-step launches from now on
             return std::nullopt;
         }
-        RegistrationResult result;
-        TransformMatrix T;
-        for (int i = 0; i < 16; ++i) { T.data()[i] = h->T[i]; lin_T_.data()[i] = h->T_lin[i]; }
+        for (int i = 0; i < 16; ++i) lin_T_.data()[i] = h->T_lin[i];
         last_lin_fused_ = true;
-        result.T.matrix() = T;
-        result.iterations = h->iterations;
-        result.converged = h->converged != 0;
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) result.H(i, j) = h->H[i * 6 + j];
-            result.b(i) = h->b[i];
-        }
-        result.error = h->error;
-        result.inlier = h->inlier;
-        result.H_raw = result.H; result.b_raw = result.b; result.error_raw = h->error_raw;
         last_opt_linearizations_ = h->linearizations;
         last_opt_trials_ = h->trials;
-        return result;
+        return to_registration_result(*h);
     }
     RegistrationResult align_on_device(size_t N, const TransformMatrix& initial_guess, float robust_scale) {
         const sp_factor_params fp = factor_params(robust_scale);
@@ -709,102 +725,6 @@ private:
                                      queue_.stream()));
         const sp_linearized h = read_lin();
         return {h.error, h.inlier};
-    }
-    /// solve_linear_system + is_converged + pose update (registration.hpp:791-801, 407-410, 814): the host twin of the
-    /// device solver; returns {delta, converged}.
-    std::pair<Eigen::Matrix<float, 6, 1>, bool> gn_step(const LinearizedResult& lin, float lambda, TransformMatrix& T) const {
-        sp_linearized h{};
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) h.H[i * 6 + j] = lin.H(i, j);
-            h.b[i] = lin.b(i);
-        }
-        float d8[8];
-        sp_gn_update_host(&h, T.data(), lambda, params_.criteria.rotation, params_.criteria.translation, d8);
-        Eigen::Matrix<float, 6, 1> delta;
-        for (int i = 0; i < 6; ++i) delta(i) = d8[i];
-        return {delta, d8[6] > 0.5f};
-    }
-    void optimize_gauss_newton(RegistrationResult& result, const LinearizedResult& lin, size_t iter) const {  // :803-828
-        TransformMatrix T = result.T.matrix();
-        const auto [delta, conv] = gn_step(lin, params_.gn.lambda, T);
-        result.converged = conv;
-        result.T.matrix() = T;
-        result.iterations = iter;
-        result.H = lin.H; result.b = lin.b; result.error = lin.error; result.inlier = lin.inlier;
-        if (params_.verbose)
-            std::cout << "iter [" << iter << "] error: " << result.error << ", inlier: " << result.inlier << std::endl;
-        (void)delta;
-    }
-    bool optimize_levenberg_marquardt(const PointCloudShared& source, const PointCloudShared& target,
-                                      RegistrationResult& result, const LinearizedResult& lin, float& lambda, size_t iter,
-                                      float robust_scale) const {  // registration.hpp:830-895
-        const float current_error = lin.error;
-        bool updated = false;
-        float last_error = std::numeric_limits<float>::max();
-        for (size_t i = 0; i < params_.lm.max_inner_iterations; ++i) {
-            TransformMatrix new_T = result.T.matrix();
-            const auto [delta, conv] = gn_step(lin, lambda, new_T);
-            (void)delta;
-            result.converged = conv;
-            const auto [new_icp_error, inlier] = compute_error(source, target, new_T, robust_scale);
-            const float new_error = new_icp_error + prior_error(new_T);  // registration.hpp:854
-            if (new_error <= current_error) {
-                result.T.matrix() = new_T; result.error = new_error; result.inlier = inlier; updated = true;
-                lambda = std::clamp(lambda / params_.lm.lambda_factor, params_.lm.min_lambda, params_.lm.max_lambda);
-                break;
-            } else if (std::fabs(new_error - last_error) <= 1e-6f) {
-                result.T.matrix() = new_T; result.error = new_error; result.inlier = inlier;
-                break;
-            } else {
-                lambda = std::clamp(lambda * params_.lm.lambda_factor, params_.lm.min_lambda, params_.lm.max_lambda);
-            }
-            last_error = new_error;
-        }
-        result.iterations = iter;
-        result.H = lin.H; result.b = lin.b;
-        return updated;
-    }
-
-    bool optimize_powell_dogleg(const PointCloudShared& source, const PointCloudShared& target, RegistrationResult& result,
-                                const LinearizedResult& lin, float& trust_region_radius, size_t iter,
-                                float robust_scale) const {  // registration.hpp:897-965
-        result.H = lin.H; result.b = lin.b; result.error = lin.error; result.inlier = lin.inlier; result.iterations = iter;
-        const auto& dl = params_.dogleg;
-        const auto clamp_radius = [&](float r) { return std::clamp(r, dl.min_trust_region_radius, dl.max_trust_region_radius); };
-        trust_region_radius = clamp_radius(trust_region_radius);
-        float H36[36], g6[6], p6[6], step_norm = 0.0f, predicted = 0.0f;
-        for (int i = 0; i < 6; ++i) {
-            for (int j = 0; j < 6; ++j) H36[i * 6 + j] = lin.H(i, j);
-            g6[i] = lin.b(i);
-        }
-        sp_dogleg_step_host(H36, g6, trust_region_radius, p6, &step_norm, &predicted);  // dogleg_step.hpp:35-101
-        if (predicted <= 0.0f) {
-            trust_region_radius = clamp_radius(trust_region_radius * dl.gamma_decrease);
-            return false;
-        }
-        TransformMatrix E, new_T;
-        sp_se3_exp_host(p6, E.data());
-        const TransformMatrix cur = result.T.matrix();
-        sp_rigid_mul_host(cur.data(), E.data(), new_T.data());
-        const auto [new_icp_error, inlier] = compute_error(source, target, new_T, robust_scale);
-        const float new_error = new_icp_error + prior_error(new_T);  // registration.hpp:933
-        const float rho = (lin.error - new_error) / predicted;
-        if (params_.verbose)
-            std::cout << "iter [" << iter << "] radius: " << trust_region_radius << ", rho: " << rho << ", error: " << new_error
-                      << ", inlier: " << inlier << std::endl;
-        if (rho < dl.eta1) {
-            trust_region_radius = clamp_radius(trust_region_radius * dl.gamma_decrease);
-            return false;
-        }
-        const float nr = std::sqrt(p6[0] * p6[0] + p6[1] * p6[1] + p6[2] * p6[2]);
-        const float nt = std::sqrt(p6[3] * p6[3] + p6[4] * p6[4] + p6[5] * p6[5]);
-        result.converged = nr < params_.criteria.rotation && nt < params_.criteria.translation;  // is_converged (:407-410)
-        result.T.matrix() = new_T;
-        result.error = new_error;
-        result.inlier = inlier;
-        if (rho > dl.eta2 && step_norm >= trust_region_radius * 0.99f)
-            trust_region_radius = clamp_radius(trust_region_radius * dl.gamma_increase);
-        return true;
     }
 
     RegistrationParams params_;

@@ -674,6 +674,42 @@ int sp_gicp_source_set_persistent(sp_gicp_source* source, int enable);
  * target whose cells are crowded (sp_grid_max_cell_points in the hundreds or thousands: a raw LiDAR scan), where a lane's walk
  * through its block of cells is thousands of candidates long. Same correspondences in every mode. */
 int sp_gicp_source_set_wave_per_point(sp_gicp_source* source, int mode);
+/* The same optimiser for a HOST-driven loop (registration.hpp:201-276 around optimize_gauss_newton :803-828,
+ * optimize_levenberg_marquardt :830-895, optimize_powell_dogleg :897-964, and pipeline/robust.hpp:100-111 for n_levels > 1): the
+ * state machine one lane of sp_gicp_align_optimize's launch runs (csrc/sp_optimizer.h), compiled for the host from the same
+ * source, fed by a caller that linearises and evaluates trials itself (any factor, pose terms on the host, a device that cannot
+ * hold the launch resident). Host memory only: nothing is allocated on a device, no stream is touched.
+ *   sp_opt_stepper_create      robust_scales[n_levels] (1 <= n_levels <= SP_OPT_MAX_LEVELS) as for sp_gicp_align_optimize: the
+ *                              stepper hands the scale of the level in force back with every request. max_iterations 0: done at
+ *                              once, the result is the initial guess (the reference's loop does not run, :227); no upper limit
+ *                              (the log's 16-bit iteration field wraps; only the first SP_OPT_LOG_ENTRIES iterations are logged)
+ *   sp_opt_stepper_next        what is wanted now: SP_OPT_WANT_LINEARIZE the reduced system at pose T with robust_scale;
+ *                              SP_OPT_WANT_TRIAL the frozen-correspondence error and inlier count at the trial pose T over the
+ *                              correspondences of the linearisation at T_lin; SP_OPT_WANT_DONE nothing (T: the final pose)
+ *   sp_opt_stepper_linearized  the answer to LINEARIZE, after the caller has applied degenerate regularisation and the MAP prior
+ *                              to it (registration.hpp:249-253)
+ *   sp_opt_stepper_trial       the answer to TRIAL, the MAP prior's error added (:854, :933); rho_out (may be null): the gain
+ *                              ratio of a dog-leg trial (:936, what the reference prints under verbose), 0 for LM
+ *   sp_opt_stepper_result      the state as sp_gicp_align_optimize reports it (any time; pad[0] = SP_ALIGN_RESULT_DONE once done;
+ *                              H, b, error_raw: of the system last handed in; searched 0)
+ * An answer of the kind that was not asked for is SP_ERR_INVALID_ARGUMENT and changes nothing. */
+enum { SP_OPT_WANT_DONE = 0, SP_OPT_WANT_LINEARIZE = 1, SP_OPT_WANT_TRIAL = 2 };
+typedef struct sp_opt_request {
+    int want;
+    int level, iteration; /* annealing level and its outer iteration */
+    float robust_scale;   /* robust_scales[level] */
+    float T[16];          /* column-major */
+    float T_lin[16];      /* pose of the latest linearisation */
+    float damping;        /* lambda (LM) / trust-region radius (dog-leg) in force */
+} sp_opt_request;
+typedef struct sp_opt_stepper sp_opt_stepper;
+int sp_opt_stepper_create(const sp_opt_params* opt, const float* T_init16, const float* robust_scales, int n_levels,
+                          sp_opt_stepper** out);
+void sp_opt_stepper_destroy(sp_opt_stepper* stepper);
+int sp_opt_stepper_next(const sp_opt_stepper* stepper, sp_opt_request* out);
+int sp_opt_stepper_linearized(sp_opt_stepper* stepper, const sp_linearized* lin_host);
+int sp_opt_stepper_trial(sp_opt_stepper* stepper, float error, uint32_t inlier, float* rho_out);
+int sp_opt_stepper_result(const sp_opt_stepper* stepper, sp_align_result* out);
 /* Registration::optimize_gauss_newton (registration.hpp:791-828) as ONE device thread, so a whole fixed-length
  * iteration loop can stay on the stream with no host round trip:
  *   delta = LDLT(H + lambda*I).solve(-b);  T <- T * se3_exp(delta);  delta_out[0..5] = delta,

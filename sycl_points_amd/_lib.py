@@ -79,6 +79,12 @@ class AlignResult(C.Structure):  # sp_align_result
                 ("log", OptLogEntry * OPT_LOG_ENTRIES)]
 
 
+class OptRequest(C.Structure):  # sp_opt_request
+    _fields_ = [("want", C.c_int), ("level", C.c_int), ("iteration", C.c_int), ("robust_scale", C.c_float), ("T", C.c_float * 16),
+                ("T_lin", C.c_float * 16), ("damping", C.c_float)]
+
+
+OPT_WANT_DONE, OPT_WANT_LINEARIZE, OPT_WANT_TRIAL = 0, 1, 2
 assert C.sizeof(Linearized) == 192
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
@@ -180,6 +186,12 @@ SIGNATURES = {
                                     _sz, _vp]),
     "sp_gicp_source_set_persistent": (_i, [_vp, _i]),
     "sp_gicp_source_set_wave_per_point": (_i, [_vp, _i]),
+    "sp_opt_stepper_create": (_i, [C.POINTER(OptParams), _vp, C.POINTER(C.c_float), _i, C.POINTER(_vp)]),
+    "sp_opt_stepper_destroy": (None, [_vp]),
+    "sp_opt_stepper_next": (_i, [_vp, C.POINTER(OptRequest)]),
+    "sp_opt_stepper_linearized": (_i, [_vp, C.POINTER(Linearized)]),
+    "sp_opt_stepper_trial": (_i, [_vp, _f, C.c_uint32, C.POINTER(C.c_float)]),
+    "sp_opt_stepper_result": (_i, [_vp, C.POINTER(AlignResult)]),
     "sp_gicp_align_fused": (_i, [_vp, _vp, _vp, C.POINTER(FactorParams), _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_gicp_align_step": (_i, [_vp, _vp, _vp, C.POINTER(FactorParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_gicp_align_linearization_pose": (_i, [_vp, _i, _vp, _vp]),

@@ -1313,7 +1313,7 @@ class Registration:
         def error_at(Tcol, Tlin_col):
             return self.compute_error_frozen(source, target, Tcol.reshape(4, 4).T, scale, self._rot_scale)
 
-        return self._host_loop(result, T, linearize_at, error_at, scale)
+        return self._host_loop(T, linearize_at, error_at, scale)
 
     def opt_params(self):
         """sp_opt_params of these RegistrationParams."""
@@ -1425,101 +1425,51 @@ class Registration:
             r = self._read_lin(lin)
             return float(r.error), int(r.inlier)
 
-        return self._host_loop(result, T, linearize_at, error_at, scale)
+        return self._host_loop(T, linearize_at, error_at, scale)
 
-    def _host_loop(self, result, T, linearize_at, error_at, scale):
-        """The optimiser loop of Registration::align shared by the generic and the prepared path: `linearize_at(T)` returns
-        the reduced system at pose T (column-major 16 floats), `error_at(T_trial, T_lin)` the frozen-correspondence error."""
+    def _host_loop(self, T, linearize_at, error_at, scale):
+        """The optimiser loop of Registration::align shared by the generic and the prepared path, from pose T (column-major 16
+        floats): the library's stepper (sp_opt_stepper_*: the state machine of the device-resident launch) says what it wants
+        next; `linearize_at(T)` returns the reduced system at pose T, `error_at(T_trial, T_lin)` the frozen-correspondence
+        error."""
         L = _lib.lib()
         p = self.params
-        lm_lambda = p.lm_init_lambda
-        radius = np.float32(p.dogleg_initial_trust_region_radius)
         T_initial = T.copy()
-        delta8 = np.zeros(8, np.float32)
         dreg = DegenerateRegParams({"NONE": 0, "NL_REG": 1, "NL-REG": 1}[p.degenerate_reg_type.upper()],
                                    p.degenerate_reg_rot_eigenvalue_threshold,
                                    p.degenerate_reg_trans_eigenvalue_threshold, p.degenerate_reg_base_factor)
         prior_on = p.map_prior_enabled and bool(self._map_prior.has_prior)
-        for it in range(p.max_iterations):
-            lr = linearize_at(T)
-            result.H_raw = np.array(lr.H, np.float32).reshape(6, 6)  # registration.hpp:244-246
-            result.b_raw = np.array(lr.b, np.float32)
-            result.error_raw = float(lr.error)
-            if dreg.type:  # registration.hpp:249-250
-                check(L.sp_degenerate_regularize_host(C.byref(dreg), lr.H, lr.b, lr.inlier,
-                                                      T.ctypes.data_as(C.c_void_p), T_initial.ctypes.data_as(C.c_void_p)))
-            if prior_on:  # registration.hpp:253
-                err = C.c_float(lr.error)
-                L.sp_map_prior_apply_host(C.byref(self._map_prior), T.ctypes.data_as(C.c_void_p), lr.H, lr.b, C.byref(err))
-                lr.error = err.value
-            H = np.array(lr.H, np.float32).reshape(6, 6)
-            b = np.array(lr.b, np.float32)
-            if p.optimization_method == "GN":
-                L.sp_gn_update_host(C.byref(lr), T.ctypes.data_as(C.c_void_p), p.gn_lambda, p.criteria_rotation,
-                                    p.criteria_translation, delta8.ctypes.data_as(C.c_void_p))
-                result.converged = bool(delta8[6] > 0.5)
-                result.iterations, result.H, result.b = it, H, b
-                result.error, result.inlier = float(lr.error), int(lr.inlier)
-            elif p.optimization_method == "DOGLEG":  # optimize_powell_dogleg (registration.hpp:897-965)
-                f32 = np.float32
-                result.iterations, result.H, result.b = it, H, b
-                result.error, result.inlier = float(lr.error), int(lr.inlier)
-                clamp = lambda r: f32(min(max(r, f32(p.dogleg_min_trust_region_radius)),  # noqa: E731
-                                          f32(p.dogleg_max_trust_region_radius)))
-                radius = clamp(radius)
-                Hrow = np.ascontiguousarray(H)
-                p6, sn, pred = np.zeros(6, np.float32), C.c_float(0.0), C.c_float(0.0)
-                L.sp_dogleg_step_host(Hrow.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.c_float(radius),
-                                      p6.ctypes.data_as(C.c_void_p), C.byref(sn), C.byref(pred))
-                if pred.value <= 0.0:
-                    radius = clamp(f32(radius * f32(p.dogleg_gamma_decrease)))
+        raw = RegistrationResult()
+        op, h, req, r = self.opt_params(), C.c_void_p(), _lib.OptRequest(), _lib.AlignResult()
+        check(L.sp_opt_stepper_create(C.byref(op), T.ctypes.data_as(C.c_void_p), C.byref(C.c_float(scale)), 1, C.byref(h)))
+        try:
+            while True:
+                check(L.sp_opt_stepper_next(h, C.byref(req)))
+                if req.want == _lib.OPT_WANT_DONE:
+                    break
+                Tq = np.array(req.T, np.float32)
+                if req.want == _lib.OPT_WANT_LINEARIZE:
+                    lr = linearize_at(Tq)
+                    raw.H_raw = np.array(lr.H, np.float32).reshape(6, 6)  # registration.hpp:244-246
+                    raw.b_raw = np.array(lr.b, np.float32)
+                    raw.error_raw = float(lr.error)
+                    if dreg.type:  # registration.hpp:249-250
+                        check(L.sp_degenerate_regularize_host(C.byref(dreg), lr.H, lr.b, lr.inlier, Tq.ctypes.data_as(C.c_void_p),
+                                                              T_initial.ctypes.data_as(C.c_void_p)))
+                    if prior_on:  # registration.hpp:253
+                        err = C.c_float(lr.error)
+                        L.sp_map_prior_apply_host(C.byref(self._map_prior), Tq.ctypes.data_as(C.c_void_p), lr.H, lr.b, C.byref(err))
+                        lr.error = err.value
+                    check(L.sp_opt_stepper_linearized(h, C.byref(lr)))
                 else:
-                    E, Ttry = np.zeros(16, np.float32), np.zeros(16, np.float32)
-                    L.sp_se3_exp_host(p6.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p))
-                    L.sp_rigid_mul_host(T.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p),
-                                        Ttry.ctypes.data_as(C.c_void_p))
-                    new_error, inl = error_at(Ttry, T)
-                    new_error = f32(f32(new_error) + self._prior_error(Ttry))  # registration.hpp:933
-                    rho = f32(f32(lr.error) - f32(new_error)) / f32(pred.value)
-                    if rho < p.dogleg_eta1:
-                        radius = clamp(f32(radius * f32(p.dogleg_gamma_decrease)))
-                    else:
-                        nr = np.sqrt(f32(p6[0] * p6[0] + p6[1] * p6[1] + p6[2] * p6[2]))
-                        nt = np.sqrt(f32(p6[3] * p6[3] + p6[4] * p6[4] + p6[5] * p6[5]))
-                        result.converged = bool(nr < p.criteria_rotation and nt < p.criteria_translation)
-                        T = Ttry
-                        result.error, result.inlier = float(new_error), inl
-                        if rho > p.dogleg_eta2 and sn.value >= radius * f32(0.99):
-                            radius = clamp(f32(radius * f32(p.dogleg_gamma_increase)))
-            else:  # LM
-                current_error = np.float32(lr.error)
-                last_error = np.float32(FLT_MAX)
-                for _inner in range(p.lm_max_inner_iterations):
-                    Ttry = T.copy()
-                    L.sp_gn_update_host(C.byref(lr), Ttry.ctypes.data_as(C.c_void_p), lm_lambda, p.criteria_rotation,
-                                        p.criteria_translation, delta8.ctypes.data_as(C.c_void_p))
-                    conv = bool(delta8[6] > 0.5)
-                    result.converged = conv
-                    new_error, inl = error_at(Ttry, T)
-                    new_error = np.float32(np.float32(new_error) + self._prior_error(Ttry))  # registration.hpp:854
-                    if new_error <= current_error:
-                        result.converged, T = conv, Ttry
-                        result.error, result.inlier = float(new_error), inl
-                        lm_lambda = float(np.clip(np.float32(lm_lambda) / np.float32(p.lm_lambda_factor),
-                                                  p.lm_min_lambda, p.lm_max_lambda))
-                        break
-                    elif abs(np.float32(new_error - last_error)) <= 1e-6:
-                        result.converged, T = conv, Ttry
-                        result.error, result.inlier = float(new_error), inl
-                        break
-                    else:
-                        lm_lambda = float(np.clip(np.float32(lm_lambda) * np.float32(p.lm_lambda_factor),
-                                                  p.lm_min_lambda, p.lm_max_lambda))
-                    last_error = new_error
-                result.iterations, result.H, result.b = it, H, b
-            if result.converged:
-                break
-        result.T = T.reshape(4, 4).T.copy()
+                    new_error, inl = error_at(Tq, np.array(req.T_lin, np.float32))
+                    new_error = np.float32(np.float32(new_error) + self._prior_error(Tq))  # registration.hpp:854, :933
+                    check(L.sp_opt_stepper_trial(h, C.c_float(new_error), inl, None))
+            check(L.sp_opt_stepper_result(h, C.byref(r)))
+        finally:
+            L.sp_opt_stepper_destroy(h)
+        result = self._result_from_align_result(r)
+        result.H_raw, result.b_raw, result.error_raw = raw.H_raw, raw.b_raw, raw.error_raw
         return result
 
     # -- device-resident fixed-length loop (GN), optionally sharded over ranks
