@@ -616,52 +616,87 @@ struct AlignArgs {
 // (count = hi * 4096 + lo, as sp_linearized carries it), 30 the searched-point count (a float value), 31 unused.
 constexpr int kFanRow = 32;
 
+struct AlignWs {  // workspace: partial rows A | partial rows B | state A | state B | searched log | fan-in rows | tickets
+    float* part[2];
+    AlignState* state;       // [j & 1]: the state after iteration j
+    unsigned* searched_log;  // kSearchedLog entries
+    float* fan_row[2];       // fan-in rows (kFanRow floats each), ping-pong like the partial rows
+    unsigned* fan_counter;   // arrival tickets of the last-arriver logic
+};
+AlignWs align_ws(void* workspace) {
+    AlignWs w;
+    w.part[0] = static_cast<float*>(workspace);
+    w.part[1] = w.part[0] + (size_t)kAlignMaxBlocks * kPartial;
+    w.state = reinterpret_cast<AlignState*>(w.part[1] + (size_t)kAlignMaxBlocks * kPartial);
+    w.searched_log = reinterpret_cast<unsigned*>(w.state + 2);
+    w.fan_row[0] = reinterpret_cast<float*>(w.searched_log + kSearchedLog);
+    w.fan_row[1] = w.fan_row[0] + kFanRow;
+    w.fan_counter = reinterpret_cast<unsigned*>(w.fan_row[1] + kFanRow);
+    return w;
+}
+
+// What a launch needs of the state it starts from, 18 words on lanes 0 .. 17: the pose (16) and converged, iterations (at
+// kStateFlagWord) of `state`, or T_init and zeros when there is no previous state. Load and store are apart so that a caller can
+// issue other loads between them and have them all in one memory round trip (align_prologue).
+__device__ __forceinline__ unsigned state_load(bool has_prev, const AlignState* state, const float* T_init) {
+    unsigned sv = 0;
+    if (threadIdx.x < 18) {
+        if (has_prev)
+            sv = reinterpret_cast<const unsigned*>(state)[threadIdx.x < 16 ? threadIdx.x : kStateFlagWord + threadIdx.x - 16];
+        else
+            sv = threadIdx.x < 16 ? __float_as_uint(T_init[threadIdx.x]) : 0u;
+    }
+    return sv;
+}
+__device__ __forceinline__ void state_store(unsigned sv, float* sT, unsigned* sflag) {
+    if (threadIdx.x < 16) sT[threadIdx.x] = __uint_as_float(sv);
+    else if (threadIdx.x < 18) sflag[threadIdx.x - 16] = sv;
+}
+
 // Pose (-> sT) and flags (-> sflag: converged, iterations) of this iteration. Returns false when an earlier iteration
 // converged: workgroup 0 then carries the state forward and the launch has nothing to do.
 __device__ __forceinline__ bool align_begin(const float* T_init, const AlignState* state_in, AlignState* state_out,
-                                            int has_prev, float* sT, unsigned* sflag, float* zero_row = nullptr) {
-    if (has_prev) {
-        if (threadIdx.x < 18) {
-            const unsigned v = reinterpret_cast<const unsigned*>(state_in)[threadIdx.x < 16 ? threadIdx.x
-                                                                                             : kStateFlagWord + threadIdx.x - 16];
-            if (threadIdx.x < 16) sT[threadIdx.x] = __uint_as_float(v);
-            else sflag[threadIdx.x - 16] = v;
-        }
-    } else {
-        if (threadIdx.x < 16) sT[threadIdx.x] = T_init[threadIdx.x];
-        else if (threadIdx.x < 18) sflag[threadIdx.x - 16] = 0u;
-    }
+                                            int has_prev, float* sT, unsigned* sflag) {
+    state_store(state_load(has_prev, state_in, T_init), sT, sflag);
     __syncthreads();
     if (sflag[0]) {  // uniform over the grid
-        if (blockIdx.x == 0 && state_out) {
-            if (threadIdx.x < kStateWords)
-                reinterpret_cast<unsigned*>(state_out)[threadIdx.x] = reinterpret_cast<const unsigned*>(state_in)[threadIdx.x];
-            if (zero_row && threadIdx.x < kFanRow) zero_row[threadIdx.x] = 0.0f;  // a finished rank adds nothing to the all-reduce
-        }
+        if (blockIdx.x == 0 && state_out && threadIdx.x < kStateWords)
+            reinterpret_cast<unsigned*>(state_out)[threadIdx.x] = reinterpret_cast<const unsigned*>(state_in)[threadIdx.x];
         return false;
     }
     return true;
 }
 
-// One thread: totals of iteration k (red0: 28 sums, the uint32 count, the searched count as a float value) at pose sT ->
-// solve_linear_system + pose update + is_converged (registration.hpp:791-828, 407-410) -> state after iteration k.
-__device__ __forceinline__ void align_finish_iteration(const AlignArgs& A, const float* red0, const float* sT,
-                                                       unsigned prev_iterations, unsigned searched, sp_linearized& slin,
-                                                       float* sTn, float* sdelta, LdltScratch& ldlt_ws) {
-    unpack_totals(red0, kAcc - 1, &slin);
+// (Tried: the step — unpack_totals + gn_update_impl — or the whole prologue, as a noinline function to keep its registers apart
+// from the point loop's. The step alone changes nothing; the whole prologue brings the POINT_TO_DISTRIBUTION instantiations from
+// 1-5 spilled registers to 1-2 but gives every instantiation a 184-byte stack frame per lane. Inlined, the GICP instantiations
+// have no spill except Tukey's one register.)
+// One lane finishes an iteration: its totals (red0: 28 sums, the uint32 count, the searched count as a float value) at the pose
+// in sT -> solve_linear_system + pose update + is_converged (registration.hpp:791-828, 407-410). The step is applied to sT IN
+// PLACE (no copy, no second barrier on the path every workgroup waits on: sdelta[6] > 0.5 says converged). `publish`: this
+// workgroup also writes the state after the iteration to *so, its searched-point count to log[k] and the system to *lin_out.
+__device__ __forceinline__ void finish_iteration(const float* red0, float* sT, float lambda, float crit_rot, float crit_trans,
+                                                 unsigned prev_iterations, sp_linearized* slin, float* sdelta, LdltScratch* ws,
+                                                 bool publish, AlignState* so, unsigned* log, int k, sp_linearized* lin_out) {
+    if (publish) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) sTn[i] = sT[i];
-    gn_update_impl(&slin, sTn, A.lambda, A.crit_rot, A.crit_trans, sdelta, false, ldlt_ws);
-    AlignState* so = A.state_out;
+        for (int i = 0; i < 16; ++i) so->T_lin[i] = sT[i];
+    }
+    unpack_totals(red0, kAcc - 1, slin);
+    gn_update_impl(slin, sT, lambda, crit_rot, crit_trans, sdelta, false, *ws);
+    if (publish) {
+        const unsigned searched = (unsigned)red0[kAcc];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { so->T[i] = sTn[i]; so->T_lin[i] = sT[i]; }
+        for (int i = 0; i < 16; ++i) so->T[i] = sT[i];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) so->delta[i] = sdelta[i];
-    so->converged = sdelta[6] > 0.5f ? 1u : 0u;
-    so->iterations = prev_iterations + 1;
-    so->searched = searched;
-    so->pad = 0;
-    if (A.lin_out) *A.lin_out = slin;
+        for (int i = 0; i < 8; ++i) so->delta[i] = sdelta[i];
+        so->converged = sdelta[6] > 0.5f ? 1u : 0u;
+        so->iterations = prev_iterations + 1;
+        so->searched = searched;
+        so->pad = 0;
+        if (log && k < kSearchedLog) log[k] = searched;
+        if (lin_out) *lin_out = *slin;
+    }
 }
 
 // End of a streaming launch in the ALIGN_FANIN / ALIGN_DIRECT modes (MI355X_MICROARCH.md "fanin",
@@ -786,15 +821,6 @@ __device__ __forceinline__ void align_store_late_state(const AlignArgs& A) {
     }
 }
 
-// (Tried: this step, or the whole prologue, as a noinline function to keep its registers apart from the point loop's. The
-// step alone changes nothing; the whole prologue brings the POINT_TO_DISTRIBUTION instantiations from 1-5 spilled registers to
-// 1-2 but gives every instantiation a 184-byte stack frame per lane. Inlined, the GICP instantiations have no spill except
-// Tukey's one register.)
-__device__ __forceinline__ void prologue_step(const float* red0, sp_linearized* slin, float* sT, float lambda,
-                                                         float crit_rot, float crit_trans, float* sdelta, LdltScratch* ws) {
-    unpack_totals(red0, kAcc - 1, slin);
-    gn_update_impl(slin, sT, lambda, crit_rot, crit_trans, sdelta, false, *ws);
-}
 template <bool SHARDED>
 __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, unsigned* sflag) {
     __shared__ float red[kFinalThreads / 32][kPartial];
@@ -802,8 +828,7 @@ __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, un
     __shared__ float sdelta[8];
     __shared__ LdltScratch ldlt_ws;
     if (A.first) {
-        if (threadIdx.x < 16) sT[threadIdx.x] = A.T_init[threadIdx.x];
-        else if (threadIdx.x < 18) sflag[threadIdx.x - 16] = 0u;
+        state_store(state_load(false, nullptr, A.T_init), sT, sflag);
         // (a new alignment: the searched-point log starts empty — entry j is written when iteration j is finished; the sharded
         // modes clear it with their tickets and rows before launch 0)
         if (!SHARDED && blockIdx.x == 0 && A.searched_log && threadIdx.x >= 64 && threadIdx.x < 64 + kSearchedLog)
@@ -813,18 +838,9 @@ __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, un
     }
     // the previous state (18 words) is requested before the rows and stored after their loads have been issued: one
     // memory round trip for both
-    unsigned sv = 0;
-    if (threadIdx.x < 18) {
-        if (A.has_prev)
-            sv = reinterpret_cast<const unsigned*>(A.state_in)[threadIdx.x < 16 ? threadIdx.x : kStateFlagWord + threadIdx.x - 16];
-        else
-            sv = threadIdx.x < 16 ? __float_as_uint(A.T_init[threadIdx.x]) : 0u;
-    }
+    const unsigned sv = state_load(A.has_prev, A.state_in, A.T_init);
     const unsigned nrows = (SHARDED && A.mode == ALIGN_ROWS) ? (unsigned)kAlignMaxBlocks : gridDim.x;
-    const bool arrived = align_totals<SHARDED>(A, A.prev_rows, nrows, red, [=] {
-        if (threadIdx.x < 16) sT[threadIdx.x] = __uint_as_float(sv);
-        else if (threadIdx.x < 18) sflag[threadIdx.x - 16] = sv;
-    }, sflag);
+    const bool arrived = align_totals<SHARDED>(A, A.prev_rows, nrows, red, [=] { state_store(sv, sT, sflag); }, sflag);
     if (!arrived) {  // (uniform per workgroup; every workgroup of every rank runs into the same bound)
         if (blockIdx.x == 0) align_store_late_state(A);
         return false;
@@ -840,29 +856,10 @@ __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, un
         zero_row();
         return false;
     }
-    if (threadIdx.x == 0) {
-        // (the step is applied to sT in place: no copy, no second barrier on the path every workgroup waits on)
-        AlignState* const so = A.state_out;
-        const bool publish = blockIdx.x == 0;
-        if (publish) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) so->T_lin[i] = sT[i];
-        }
-        prologue_step(red[0], &slin, sT, A.lambda, A.crit_rot, A.crit_trans, sdelta, &ldlt_ws);
-        if (publish) {
-            const unsigned searched = (unsigned)red[0][kAcc];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) so->T[i] = sT[i];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) so->delta[i] = sdelta[i];
-            so->converged = sdelta[6] > 0.5f ? 1u : 0u;
-            so->iterations = sflag[1] + 1;
-            so->searched = searched;
-            so->pad = 0;
-            if (A.searched_log && A.k < kSearchedLog) A.searched_log[A.k] = searched;
-            if (A.lin_out) *A.lin_out = slin;
-        }
-    }
+    if (threadIdx.x == 0)
+        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], &slin, sdelta, &ldlt_ws, blockIdx.x == 0, A.state_out,
+                         A.searched_log,
+                         A.k, A.lin_out);
     __syncthreads();
     if (sdelta[6] > 0.5f) {  // converged with this step: no further linearisation (registration.hpp:266-268)
         zero_row();
@@ -880,36 +877,15 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_kernel(FusedParams P, 
     __shared__ unsigned sflag[2];
     // (converged: every rank holds the same state and stops at the same launch — nobody waits for a row)
     if (!align_prologue<SHARDED>(A, sT, sflag)) return;
-    // the pose is uniform: move it to scalar registers (it would otherwise occupy 12 VGPRs for the whole loop)
-    Rigid T = load_rigid_colmajor(sT);
-    auto uniform = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T.R[r][c] = uniform(T.R[r][c]);
-        T.t[r] = uniform(T.t[r]);
-    }
+    const Rigid T = uniform_pose(sT);
     float acc[kAcc - 1];
     unsigned cnt = 0, searched = 0;
     const unsigned stride = gridDim.x * kAlignBlock;
 #pragma unroll
     for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
-    // XCD-aware tile order: workgroup b runs on XCD b % 8, so give every XCD one contiguous eighth of the
-    // (cell-ordered) source: the target cells it reads then stay in that XCD's own L2 from one grid row / layer to the next
-    unsigned tile = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    if constexpr (FAST_NN && kWaveTail) {
-        if (P.ccache != nullptr) {  // (uniform)
-            for (unsigned b = tile * kAlignBlock; b < P.n; b += stride)
-                fused_point_wave<LOSS, P2D>(P, T, b + threadIdx.x, b + threadIdx.x < P.n, acc, cnt, searched);
-        } else {
-            for (unsigned i = tile * kAlignBlock + threadIdx.x; i < P.n; i += stride)
-                fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert>(P, T, i, acc, cnt, searched);
-        }
-    } else {
-        for (unsigned i = tile * kAlignBlock + threadIdx.x; i < P.n; i += stride)
-            fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert>(P, T, i, acc, cnt, searched);
-    }
+    const unsigned tile = xcd_tile();
+    for (unsigned i = tile * kAlignBlock + threadIdx.x; i < P.n; i += stride)
+        fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert>(P, T, i, acc, cnt, searched);
     if constexpr (!SHARDED) {
         block_reduce_store<kAcc - 1, kAlignBlock>(acc, cnt, partials + (size_t)blockIdx.x * kPartial, false, searched);
     } else if (A.mode == ALIGN_ROWS) {
@@ -925,21 +901,17 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_kernel(FusedParams P, 
 // 1024-lane workgroup per CU, at most 256 of them). The iterations are separated by the arrival counter the sharded modes' fan-in
 // already uses, not by kernel boundaries:
 //   iteration k   per-point loop exactly as gicp_align_kernel -> the workgroup's partial row, stored write-through (sc1) ->
-//                 wave 0 drains its stores, lane 0 adds 1 to the counter shard of its XCD (agent scope)
-//   then          every workgroup waits until the shards add up to grid * (k + 1) — one lane polls with sc1 loads and s_sleep,
-//                 bounded by wall_clock64 (a grid that is not fully resident ends with the error word set, never hangs) — and
-//                 runs today's prologue on the rows (sc1 loads, same fixed order: the same bits as the per-launch form)
-// (MI355X_MICROARCH.md, hand-off table, first row: one lane signals for all its workgroup's sc1 stores behind the storing
-// wave's vmcnt(0) wait; the consumer polls with sc1 loads, the polling wave loads after its poll has matched, the others behind
-// a workgroup barrier it joins.) What it removes: the kernel boundary and the launch ramp of every iteration, the launches
+//                 grid_arrive
+//   then          every workgroup waits until all grid * (k + 1) rows are there (grid_wait, registration_device.h: bounded — a
+//                 grid that is not fully resident ends with the error word set, never hangs) and runs today's prologue on
+//                 the rows (sc1 loads, same fixed order: the same bits as the per-launch form)
+// What it removes: the kernel boundary and the launch ramp of every iteration, the launches
 // that only find out that an earlier iteration converged (an alignment that converges after 3 of 20 iterations enqueued 17 of
 // them, 2.5 us each), and the finish launch (workgroup 0 finishes the last iteration itself).
 // Rows ping-pong by the parity of k: a workgroup can only write row k + 1 after every workgroup has stored row k, i.e. after
 // every workgroup has finished reading the rows of k - 1 that it overwrites.
 struct PersistArgs {
-    float* part[2];              // partial rows, ping-pong
-    AlignState* state;           // [2]
-    unsigned* searched_log;
+    AlignWs ws;                  // partial rows (ping-pong), the two states, the searched log
     unsigned* tickets;           // kTicketShards counters, kTicketStride words apart, zero when the launch starts
     const float* T_init;         // device: initial guess (read before T_out is written)
     float lambda, crit_rot, crit_trans;
@@ -962,12 +934,14 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
     __shared__ LdltScratch ldlt_ws;
     __shared__ unsigned s_flag;  // 0 go on, 1 converged / done, 2 a wait ran out
     const unsigned stride = gridDim.x * kAlignBlock;
-    unsigned tile = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const unsigned tile = xcd_tile();
     __shared__ unsigned s_prev[2];  // converged, iterations of the state this launch starts from
+    // (state_load / state_store and, below, finish_iteration written out. This kernel's instantiations spill 6-47 registers and
+    // the count moves with the text: through the helpers five of the twenty spill between 5 fewer and 4 more, so both stay as
+    // they were written for this kernel)
     if (A.k_begin >= 2) {  // the state after iteration k_begin - 2: the pose launch k_begin - 1 ran at, the flags
         if (threadIdx.x < 18) {
-            const unsigned v = reinterpret_cast<const unsigned*>(&A.state[A.k_begin & 1])[threadIdx.x < 16 ? threadIdx.x : kStateFlagWord + threadIdx.x - 16];
+            const unsigned v = reinterpret_cast<const unsigned*>(&A.ws.state[A.k_begin & 1])[threadIdx.x < 16 ? threadIdx.x : kStateFlagWord + threadIdx.x - 16];
             if (threadIdx.x < 16) sT[threadIdx.x] = __uint_as_float(v);
             else s_prev[threadIdx.x - 16] = v;
         }
@@ -975,14 +949,14 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
         if (threadIdx.x < 16) sT[threadIdx.x] = A.T_init[threadIdx.x];
         else if (threadIdx.x < 18) s_prev[threadIdx.x - 16] = 0u;
     }
-    if (A.k_begin == 0 && blockIdx.x == 0 && A.searched_log && threadIdx.x >= 64 && threadIdx.x < 64 + kSearchedLog)
-        A.searched_log[threadIdx.x - 64] = 0u;
+    if (A.k_begin == 0 && blockIdx.x == 0 && A.ws.searched_log && threadIdx.x >= 64 && threadIdx.x < 64 + kSearchedLog)
+        A.ws.searched_log[threadIdx.x - 64] = 0u;
     __syncthreads();
     if (s_prev[0]) {  // converged before this launch (uniform): workgroup 0 hands out the results of that state
         if (blockIdx.x == 0) {
-            const AlignState* const sp_ = &A.state[A.k_begin & 1];
+            const AlignState* const sp_ = &A.ws.state[A.k_begin & 1];
             if (threadIdx.x < kStateWords)
-                reinterpret_cast<unsigned*>(&A.state[(A.k_begin + 1) & 1])[threadIdx.x] = reinterpret_cast<const unsigned*>(sp_)[threadIdx.x];
+                reinterpret_cast<unsigned*>(&A.ws.state[(A.k_begin + 1) & 1])[threadIdx.x] = reinterpret_cast<const unsigned*>(sp_)[threadIdx.x];
             if (threadIdx.x < 16) A.T_out[threadIdx.x] = sp_->T[threadIdx.x];
             else if (threadIdx.x < 24 && A.delta_out8) A.delta_out8[threadIdx.x - 16] = sp_->delta[threadIdx.x - 16];
             else if (threadIdx.x == 24 && A.iterations_out) *A.iterations_out = sp_->iterations;
@@ -994,37 +968,24 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
         if (k > 0) {
             // ---- wait for the rows of iteration k - 1 (a kernel boundary did, for the first one), then finish it: the prologue
             // of gicp_align_kernel
-            if (threadIdx.x == 0) {
-                const unsigned want = gridDim.x * (unsigned)(k - A.k_begin);
-                const unsigned long long t0 = wall_clock64();
-                unsigned flag = 0;
-                for (;;) {
-                    unsigned have = 0;
-#pragma unroll
-                    for (int sh = 0; sh < kTicketShards; ++sh)
-                        have += __hip_atomic_load(A.tickets + sh * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (have >= want) break;
-                    if (wall_clock64() - t0 > A.budget) { flag = 2; break; }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                s_flag = flag;
-            }
+            if (threadIdx.x == 0) s_flag = grid_wait(A.tickets, gridDim.x * (unsigned)(k - A.k_begin), A.budget) ? 0u : 2u;
             __syncthreads();
             if (s_flag == 2) {  // (uniform per workgroup; every workgroup runs into the same bound)
                 if (blockIdx.x == 0 && threadIdx.x < 16) A.T_out[threadIdx.x] = __int_as_float(0x7fc00000);  // loud: NaN pose
                 if (blockIdx.x == 0 && threadIdx.x == 16 && A.iterations_out) *A.iterations_out = 0xffffffffu;
-                if (blockIdx.x == 0 && threadIdx.x == 17) { A.state[0].pad = 2u; A.state[1].pad = 2u; }
+                if (blockIdx.x == 0 && threadIdx.x == 17) { A.ws.state[0].pad = 2u; A.ws.state[1].pad = 2u; }
                 return;
             }
-            reduce_rows_1024<true>(A.part[(k - 1) & 1], gridDim.x, kAcc - 1, red, false, [] {});
-            if (threadIdx.x == 0) {
+            reduce_rows_1024<true>(A.ws.part[(k - 1) & 1], gridDim.x, kAcc - 1, red, false, [] {});
+            if (threadIdx.x == 0) {  // (finish_iteration, written out: see the note at the top of the kernel)
                 const bool publish = blockIdx.x == 0;
-                AlignState* const so = &A.state[(k - 1) & 1];
+                AlignState* const so = &A.ws.state[(k - 1) & 1];
                 if (publish) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) so->T_lin[i] = sT[i];
                 }
-                prologue_step(red[0], &slin, sT, A.lambda, A.crit_rot, A.crit_trans, sdelta, &ldlt_ws);
+                unpack_totals(red[0], kAcc - 1, &slin);
+                gn_update_impl(&slin, sT, A.lambda, A.crit_rot, A.crit_trans, sdelta, false, ldlt_ws);
                 const bool conv = sdelta[6] > 0.5f;
                 const bool last = conv || k == A.max_iterations;
                 if (publish) {
@@ -1037,10 +998,10 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
                     so->iterations = iterations + 1;
                     so->searched = searched;
                     so->pad = 0;
-                    if (A.searched_log && k - 1 < kSearchedLog) A.searched_log[k - 1] = searched;
+                    if (A.ws.searched_log && k - 1 < kSearchedLog) A.ws.searched_log[k - 1] = searched;
                     if (A.lin_out) *A.lin_out = slin;
                     if (last) {  // the outputs, and the same state in the other slot (whoever reads state[last & 1] finds it)
-                        A.state[k & 1] = *so;
+                        A.ws.state[k & 1] = *so;
 #pragma unroll
                         for (int i = 0; i < 16; ++i) A.T_out[i] = sT[i];
                         if (A.delta_out8)
@@ -1064,13 +1025,8 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
                                                            //  begins later was handed the right value)
         for (unsigned i = tile * kAlignBlock + threadIdx.x; i < P.n; i += stride)
             fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert>(P, T, i, acc, cnt, searched);
-        block_reduce_store<kAcc - 1, kAlignBlock, true>(acc, cnt, A.part[k & 1] + (size_t)blockIdx.x * kPartial, false, searched);
-        if (threadIdx.x < kWave) {  // the storing lanes all sit in wave 0
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (threadIdx.x == 0)
-                __hip_atomic_fetch_add(A.tickets + (blockIdx.x & (kTicketShards - 1)) * kTicketStride, 1u, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        }
+        block_reduce_store<kAcc - 1, kAlignBlock, true>(acc, cnt, A.ws.part[k & 1] + (size_t)blockIdx.x * kPartial, false, searched);
+        grid_arrive(A.tickets);
         // (after the last iteration's rows only workgroup 0 is needed: it finishes the iteration and writes the outputs)
         if (k == A.max_iterations - 1 && blockIdx.x != 0) return;
     }
@@ -1108,7 +1064,6 @@ __global__ __launch_bounds__(kFinalThreads) void align_solve_kernel(AlignArgs A,
     __shared__ float sT[16];
     __shared__ unsigned sflag[2];
     __shared__ sp_linearized slin;
-    __shared__ float sTn[16];
     __shared__ float sdelta[8];
     __shared__ LdltScratch ldlt_ws;
     if (!align_begin(A.T_init, A.state_in, A.state_out, A.has_prev, sT, sflag)) {
@@ -1120,11 +1075,9 @@ __global__ __launch_bounds__(kFinalThreads) void align_solve_kernel(AlignArgs A,
         align_publish(A.state_out, Pb);
         return;
     }
-    if (threadIdx.x == 0) {
-        const unsigned searched = (unsigned)red[0][kAcc];
-        if ((A.mode == ALIGN_ROWS || A.mode == ALIGN_PROLOGUE) && A.searched_log && A.k < kSearchedLog) A.searched_log[A.k] = searched;
-        align_finish_iteration(A, red[0], sT, sflag[1], searched, slin, sTn, sdelta, ldlt_ws);
-    }
+    if (threadIdx.x == 0)  // (ALIGN_FANIN / ALIGN_DIRECT: the streaming launch's last arriver has written the log entry, align_tail)
+        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], &slin, sdelta, &ldlt_ws, true, A.state_out,
+                         (A.mode == ALIGN_ROWS || A.mode == ALIGN_PROLOGUE) ? A.searched_log : nullptr, A.k, A.lin_out);
     align_publish(A.state_out, Pb);
 }
 
@@ -1169,19 +1122,14 @@ void launch_one(Which which, const KParams& P, float* partials, float* weights, 
     else weights_kernel<REG, LOSS><<<grid, kBlock, 0, st>>>(P, weights);
 }
 template <int REG>
-bool launch_loss(Which which, int loss, const KParams& P, float* partials, float* weights, unsigned grid,
-                 hipStream_t st) {
-    switch (loss) {  // Registration::dispatch (registration.hpp:372-405)
-        case SP_LOSS_NONE: launch_one<REG, LOSS_NONE>(which, P, partials, weights, grid, st); return true;
-        case SP_LOSS_HUBER: launch_one<REG, LOSS_HUBER>(which, P, partials, weights, grid, st); return true;
-        case SP_LOSS_TUKEY: launch_one<REG, LOSS_TUKEY>(which, P, partials, weights, grid, st); return true;
-        case SP_LOSS_CAUCHY: launch_one<REG, LOSS_CAUCHY>(which, P, partials, weights, grid, st); return true;
-        case SP_LOSS_GEMAN_MCCLURE: launch_one<REG, LOSS_GEMAN_MCCLURE>(which, P, partials, weights, grid, st); return true;
-    }
-    return false;
+int launch_loss(Which which, int loss, const KParams& P, float* partials, float* weights, unsigned grid, hipStream_t st) {
+    return with_loss(loss, [&](auto L) {
+        launch_one<REG, L>(which, P, partials, weights, grid, st);
+        return SP_OK;
+    });
 }
-bool launch_reg(Which which, int reg, int loss, const KParams& P, float* partials, float* weights, unsigned grid,
-                hipStream_t st) {
+int launch_reg(Which which, int reg, int loss, const KParams& P, float* partials, float* weights, unsigned grid,
+               hipStream_t st) {
     switch (reg) {
         case SP_REG_POINT_TO_POINT: return launch_loss<SP_REG_POINT_TO_POINT>(which, loss, P, partials, weights, grid, st);
         case SP_REG_POINT_TO_PLANE: return launch_loss<SP_REG_POINT_TO_PLANE>(which, loss, P, partials, weights, grid, st);
@@ -1189,7 +1137,7 @@ bool launch_reg(Which which, int reg, int loss, const KParams& P, float* partial
         case SP_REG_GICP: return launch_loss<SP_REG_GICP>(which, loss, P, partials, weights, grid, st);
         case SP_REG_GENZ: return launch_loss<SP_REG_GENZ>(which, loss, P, partials, weights, grid, st);
     }
-    return false;
+    return unknown_combination();
 }
 
 // validate_params (registration.hpp:129-193): which attribute arrays a reg_type needs.
@@ -1235,17 +1183,11 @@ int run_reduction(Which which, const float* src, const float* scov, size_t n, co
     if (v != SP_OK) return v;
     if (n >= (1ull << 32)) { sp_set_error("[Registration] more than 2^32 source points"); return SP_ERR_INVALID_ARGUMENT; }
     if (n == 0) return zero_async(out, sizeof(sp_linearized), st);
-    if (!ws || ws_bytes < sp_gicp_workspace_bytes(n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_workspace(ws, ws_bytes, n); rc != SP_OK) return rc;
     const KParams P = make_params(src, scov, n, tgt, tcov, tnrm, nn_idx, nn_d2, T, T_dev, fp);
     const unsigned grid = reduce_grid(n);
     float* partials = static_cast<float*>(ws);
-    if (!launch_reg(which, fp->reg_type, fp->robust_type, P, partials, nullptr, grid, st)) {
-        sp_set_error("[Registration::dispatch] Combination not found in tags!");
-        return SP_ERR_RUNTIME;
-    }
+    if (const int rc = launch_reg(which, fp->reg_type, fp->robust_type, P, partials, nullptr, grid, st); rc != SP_OK) return rc;
     final_reduce_kernel<<<1, kFinalThreads, 0, st>>>(partials, grid, which == K_LINEARIZE ? kAcc - 1 : 1, out,
                                                      GnArgs{nullptr, 0.0f, 0.0f, 0.0f, nullptr});
     return launch_status();
@@ -1281,11 +1223,10 @@ extern "C" int sp_icp_robust_weights(const float* src_points, const float* src_c
     if (n == 0) return SP_OK;
     const KParams P = make_params(src_points, src_covs, n, tgt_points, tgt_covs, tgt_normals, nn_idx, nn_d2, transT,
                                   transT_on_device, params);
-    if (!launch_reg(K_WEIGHTS, params->reg_type, params->robust_type, P, nullptr, weights_out, stream_grid(n),
-                    as_stream(stream))) {
-        sp_set_error("[Registration::dispatch] Combination not found in tags!");
-        return SP_ERR_RUNTIME;
-    }
+    if (const int rc = launch_reg(K_WEIGHTS, params->reg_type, params->robust_type, P, nullptr, weights_out, stream_grid(n),
+                                  as_stream(stream));
+        rc != SP_OK)
+        return rc;
     return launch_status();
 }
 extern "C" int sp_genz_counts(const float* tgt_covs, const int32_t* nn_idx, const float* nn_d2, size_t n, float max_corr,
@@ -1538,41 +1479,26 @@ extern "C" int sp_gicp_iteration_fused(const sp_gicp_target* target, const sp_gi
     using namespace sp;
     hipStream_t st = as_stream(stream);
     if (!target || !source || !params || !out) return SP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_prepared_reg("iteration_fused", target, params); rc != SP_OK) return rc;
+    if (const int rc = check_prepared_reg(target, params); rc != SP_OK) return rc;
     if (gn && !transT_on_device) {
         sp_set_error("[sp_gicp_iteration_fused] the fused Gauss-Newton update needs the pose on the device");
         return SP_ERR_INVALID_ARGUMENT;
     }
     const size_t n = source->n;
     if (n == 0) return zero_async(out, sizeof(sp_linearized), st);
-    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_workspace(workspace, workspace_bytes, n); rc != SP_OK) return rc;
     target->note(st);
     const FusedParams P = make_fused_params(target, source, params, transT, transT_on_device, nn_idx_out, nn_d2_out);
     const bool fills_cache = P.ccache != nullptr && (source->opt_stage_mask & 1);
     const unsigned grid = reduce_grid(n);
     float* partials = static_cast<float*>(workspace);
-    // Unsorted lanes touch unrelated cells: the ring walk (fewest cache lines per query) wins. Cell-sorted lanes share
-    // their lines: the branch-light 2x2x2 walk wins (profiles/README.md, r01_c).
-    const bool fast = source->opt_fast_nn < 0 ? source->sorted : (source->opt_fast_nn != 0);
-    const bool p2d = params->reg_type == SP_REG_POINT_TO_DISTRIBUTION;
-#define SP_LAUNCH_FUSED(L)                                                              \
-    if (!(source->opt_stage_mask & 1)) {}                                                   \
-    else if (fast && p2d) gicp_fused_kernel<L, true, true><<<grid, kBlock, 0, st>>>(P, partials);   \
-    else if (fast) gicp_fused_kernel<L, true><<<grid, kBlock, 0, st>>>(P, partials);   \
-    else if (p2d) gicp_fused_kernel<L, false, true><<<grid, kBlock, 0, st>>>(P, partials);   \
-    else gicp_fused_kernel<L, false><<<grid, kBlock, 0, st>>>(P, partials)
-    switch (params->robust_type) {
-        case SP_LOSS_NONE: SP_LAUNCH_FUSED(LOSS_NONE); break;
-        case SP_LOSS_HUBER: SP_LAUNCH_FUSED(LOSS_HUBER); break;
-        case SP_LOSS_TUKEY: SP_LAUNCH_FUSED(LOSS_TUKEY); break;
-        case SP_LOSS_CAUCHY: SP_LAUNCH_FUSED(LOSS_CAUCHY); break;
-        case SP_LOSS_GEMAN_MCCLURE: SP_LAUNCH_FUSED(LOSS_GEMAN_MCCLURE); break;
-        default: sp_set_error("[Registration::dispatch] Combination not found in tags!"); return SP_ERR_RUNTIME;
-    }
-#undef SP_LAUNCH_FUSED
+    const int rc = with_variant(params->robust_type, source_fast_nn(source), params->reg_type == SP_REG_POINT_TO_DISTRIBUTION,
+                                [&](auto L, auto FAST_NN, auto P2D) {
+        if (source->opt_stage_mask & 1)
+            gicp_fused_kernel<L, FAST_NN, P2D><<<grid, kBlock, 0, st>>>(P, partials);
+        return SP_OK;
+    });
+    if (rc != SP_OK) return rc;
     if (fills_cache) { source->cache_valid = true; source->qcert_valid = false; }  // (these kernels refresh rows, not margin certificates)
     GnArgs ga{nullptr, 0.0f, 0.0f, 0.0f, nullptr};
     if (gn) ga = GnArgs{transT, gn->lambda, gn->crit_rotation, gn->crit_translation, delta_out8};
@@ -1582,35 +1508,12 @@ extern "C" int sp_gicp_iteration_fused(const sp_gicp_target* target, const sp_gi
 
 namespace sp {
 namespace {
-struct AlignWs {  // workspace: partial rows A | partial rows B | state A | state B | searched log | fan-in rows | tickets
-    float* part[2];
-    AlignState* state;       // [j & 1]: the state after iteration j
-    unsigned* searched_log;  // kSearchedLog entries
-    float* fan_row[2];       // fan-in rows (kFanRow floats each), ping-pong like the partial rows
-    unsigned* fan_counter;   // arrival tickets of the last-arriver logic
-};
-AlignWs align_ws(void* workspace) {
-    AlignWs w;
-    w.part[0] = static_cast<float*>(workspace);
-    w.part[1] = w.part[0] + (size_t)kAlignMaxBlocks * kPartial;
-    w.state = reinterpret_cast<AlignState*>(w.part[1] + (size_t)kAlignMaxBlocks * kPartial);
-    w.searched_log = reinterpret_cast<unsigned*>(w.state + 2);
-    w.fan_row[0] = reinterpret_cast<float*>(w.searched_log + kSearchedLog);
-    w.fan_row[1] = w.fan_row[0] + kFanRow;
-    w.fan_counter = reinterpret_cast<unsigned*>(w.fan_row[1] + kFanRow);
-    return w;
-}
 constexpr size_t kAlignResetBytes = (kSearchedLog + 2 * kFanRow + 4) * sizeof(float);  // log | rows | tickets: zero at k = 0
-int align_check(const char* who, const sp_gicp_target* target, const sp_gicp_source* source, const sp_factor_params* params,
+int align_check(const sp_gicp_target* target, const sp_gicp_source* source, const sp_factor_params* params,
                 const sp_gn_params* gn, const float* T, void* workspace, size_t workspace_bytes) {
     if (!target || !source || !params || !gn || !T) return SP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_prepared_reg(who, target, params); rc != SP_OK) return rc;
-    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(source->n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
-    (void)who;
-    return SP_OK;
+    if (const int rc = check_prepared_reg(target, params); rc != SP_OK) return rc;
+    return check_workspace(workspace, workspace_bytes, source->n);
 }
 AlignArgs align_args(const AlignWs& w, float* transT_device, const sp_gn_params* gn, int j, int mode, sp_linearized* lin_out) {
     AlignArgs A;
@@ -1635,9 +1538,8 @@ AlignArgs align_args(const AlignWs& w, float* transT_device, const sp_gn_params*
     return A;
 }
 // Sharded modes: finish iteration j from the all-reduced row(s) (enqueued behind the caller's collective).
-XchgArgs xchg_args(const sp_xchg* x, int j) {
+XchgArgs xchg_args(const sp_xchg* x) {
     if (!x) return XchgArgs{nullptr, nullptr, 0, 1, nullptr, 0ull};
-    (void)j;
     return XchgArgs{x->peers_dev, x->local, x->rank, x->world, x->epoch_dev,
                     (unsigned long long)x->timeout_ms * 100000ull};  // wall_clock64: 100 MHz
 }
@@ -1646,7 +1548,7 @@ void launch_solve(const AlignWs& w, float* transT_device, const sp_gn_params* gn
                   hipStream_t st, const sp_xchg* x = nullptr, unsigned rows = kAlignMaxBlocks,
                   AlignPublish Pb = AlignPublish{nullptr, nullptr, nullptr, nullptr}) {
     AlignArgs A = align_args(w, transT_device, gn, j, mode, lin_out);
-    A.x = xchg_args(x, j);
+    A.x = xchg_args(x);
     align_solve_kernel<<<1, kFinalThreads, 0, st>>>(A, w.part[j & 1], rows, Pb);
 }
 }  // namespace
@@ -1658,13 +1560,10 @@ extern "C" int sp_gicp_error_prepared(const sp_gicp_target* target, const sp_gic
     using namespace sp;
     hipStream_t st = as_stream(stream);
     if (!target || !source || !params || !out || !transT_lin_host) return SP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_prepared_reg("error_prepared", target, params); rc != SP_OK) return rc;
+    if (const int rc = check_prepared_reg(target, params); rc != SP_OK) return rc;
     const size_t n = source->n;
     if (n == 0) return zero_async(out, sizeof(sp_linearized), st);
-    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_workspace(workspace, workspace_bytes, n); rc != SP_OK) return rc;
     if (!source->cache_valid || source->cache_target != target || source->cache_version != target->version) {
         sp_set_error("[sp_gicp_error_prepared] no frozen correspondences: linearise first (sp_gicp_iteration_fused / "
                      "sp_gicp_align_*) with this target");  // compute_error_frozen needs the neighbours of a linearisation
@@ -1676,19 +1575,13 @@ extern "C" int sp_gicp_error_prepared(const sp_gicp_target* target, const sp_gic
     for (int i = 0; i < 16; ++i) TL.m[i] = transT_lin_host[i];
     const unsigned grid = reduce_grid(n);
     float* partials = static_cast<float*>(workspace);
-    const bool p2d = params->reg_type == SP_REG_POINT_TO_DISTRIBUTION;
-#define SP_LAUNCH_ERR(L)                                                                       \
-    if (p2d) error_prepared_kernel<L, true><<<grid, kBlock, 0, st>>>(P, TL, nullptr, partials);        \
-    else error_prepared_kernel<L, false><<<grid, kBlock, 0, st>>>(P, TL, nullptr, partials)
-    switch (params->robust_type) {
-        case SP_LOSS_NONE: SP_LAUNCH_ERR(LOSS_NONE); break;
-        case SP_LOSS_HUBER: SP_LAUNCH_ERR(LOSS_HUBER); break;
-        case SP_LOSS_TUKEY: SP_LAUNCH_ERR(LOSS_TUKEY); break;
-        case SP_LOSS_CAUCHY: SP_LAUNCH_ERR(LOSS_CAUCHY); break;
-        case SP_LOSS_GEMAN_MCCLURE: SP_LAUNCH_ERR(LOSS_GEMAN_MCCLURE); break;
-        default: sp_set_error("[Registration::dispatch] Combination not found in tags!"); return SP_ERR_RUNTIME;
-    }
-#undef SP_LAUNCH_ERR
+    const int rc = with_loss(params->robust_type, [&](auto L) {
+        return with_bool<false>(params->reg_type == SP_REG_POINT_TO_DISTRIBUTION, [&](auto P2D) {
+            error_prepared_kernel<decltype(L)::value, P2D><<<grid, kBlock, 0, st>>>(P, TL, nullptr, partials);
+            return SP_OK;
+        });
+    });
+    if (rc != SP_OK) return rc;
     final_reduce_kernel<<<1, kFinalThreads, 0, st>>>(partials, grid, 1, out, GnArgs{nullptr, 0.0f, 0.0f, 0.0f, nullptr});
     return launch_status();
 }
@@ -1700,8 +1593,7 @@ int align_step_impl(const sp_gicp_target* target, const sp_gicp_source* source, 
                     float* nn_d2_out, sp_linearized* lin_out, void* workspace, size_t workspace_bytes, void* stream,
                     const sp_xchg* xchg) {
     hipStream_t st = as_stream(stream);
-    const int rc = align_check("step", target, source, params, gn, transT_device, workspace, workspace_bytes);
-    if (rc != SP_OK) return rc;
+    if (const int rc = align_check(target, source, params, gn, transT_device, workspace, workspace_bytes); rc != SP_OK) return rc;
     if (k < 0 || rows_all_reduced < 0 || rows_all_reduced > 3 || ((rows_all_reduced == ALIGN_DIRECT) != (xchg != nullptr)))
         return SP_ERR_INVALID_ARGUMENT;
     const size_t n = source->n;
@@ -1719,7 +1611,6 @@ int align_step_impl(const sp_gicp_target* target, const sp_gicp_source* source, 
     const FusedParams P = make_fused_params(target, source, params, transT_device, 1, nn_idx_out, nn_d2_out);
     const bool fills_cache = P.ccache != nullptr && (source->opt_stage_mask & 1);
     const unsigned grid = align_grid(n);
-    const bool fast = source->opt_fast_nn < 0 ? source->sorted : (source->opt_fast_nn != 0);
     // the launch first finishes iteration k - 1: from the previous launch's rows (one GPU), from the all-reduced row(s), or
     // from the rows the peers are storing into this rank's slots
     AlignArgs A = align_args(w, transT_device, gn, k > 0 ? k - 1 : 0, mode, lin_out);
@@ -1727,36 +1618,17 @@ int align_step_impl(const sp_gicp_target* target, const sp_gicp_source* source, 
     A.prev_rows = w.part[(k + 1) & 1];
     A.k_launch = k;
     A.fan_row_out = w.fan_row[k & 1];
-    A.x = xchg_args(xchg, k);
+    A.x = xchg_args(xchg);
     float* out = w.part[k & 1];
-    const bool p2d = params->reg_type == SP_REG_POINT_TO_DISTRIBUTION;
-#define SP_LAUNCH_ALIGN2(L, S)                                                                          \
-    if (fast && p2d) gicp_align_kernel<L, true, true, S><<<grid, kAlignBlock, 0, st>>>(P, A, out);         \
-    else if (fast) gicp_align_kernel<L, true, false, S><<<grid, kAlignBlock, 0, st>>>(P, A, out);          \
-    else if (p2d) gicp_align_kernel<L, false, true, S><<<grid, kAlignBlock, 0, st>>>(P, A, out);           \
-    else gicp_align_kernel<L, false, false, S><<<grid, kAlignBlock, 0, st>>>(P, A, out)
-#define SP_LAUNCH_ALIGN(L)                                                                             \
-    if (!(source->opt_stage_mask & 1)) {}                                                                  \
-    else if (mode == ALIGN_PROLOGUE) { SP_LAUNCH_ALIGN2(L, false); }                                      \
-    else { SP_LAUNCH_ALIGN2(L, true); }
-#ifdef SP_DEV_MIN  // development builds only (scratch/devbuild.sh): one instantiation of the kernel, a fraction of the compile time
-    if (params->robust_type != SP_LOSS_NONE || !fast || p2d || mode != ALIGN_PROLOGUE) {
-        sp_set_error("SP_DEV_MIN build: only GICP / NONE / sorted source / one GPU");
-        return SP_ERR_RUNTIME;
-    }
-    if (source->opt_stage_mask & 1) gicp_align_kernel<LOSS_NONE, true, false, false><<<grid, kAlignBlock, 0, st>>>(P, A, out);
-#else
-    switch (params->robust_type) {
-        case SP_LOSS_NONE: SP_LAUNCH_ALIGN(LOSS_NONE); break;
-        case SP_LOSS_HUBER: SP_LAUNCH_ALIGN(LOSS_HUBER); break;
-        case SP_LOSS_TUKEY: SP_LAUNCH_ALIGN(LOSS_TUKEY); break;
-        case SP_LOSS_CAUCHY: SP_LAUNCH_ALIGN(LOSS_CAUCHY); break;
-        case SP_LOSS_GEMAN_MCCLURE: SP_LAUNCH_ALIGN(LOSS_GEMAN_MCCLURE); break;
-        default: sp_set_error("[Registration::dispatch] Combination not found in tags!"); return SP_ERR_RUNTIME;
-    }
-#endif
-#undef SP_LAUNCH_ALIGN
-#undef SP_LAUNCH_ALIGN2
+    const int rc = with_bool<false>(mode != ALIGN_PROLOGUE, [&](auto SHARDED) {
+        return with_variant(params->robust_type, source_fast_nn(source), params->reg_type == SP_REG_POINT_TO_DISTRIBUTION,
+                            [&](auto L, auto FAST_NN, auto P2D) {
+            if (source->opt_stage_mask & 1)
+                gicp_align_kernel<L, FAST_NN, P2D, decltype(SHARDED)::value><<<grid, kAlignBlock, 0, st>>>(P, A, out);
+            return SP_OK;
+        });
+    });
+    if (rc != SP_OK) return rc;
     if (fills_cache) { source->cache_valid = true; source->qcert_valid = false; }  // (these kernels refresh rows, not margin certificates)
     return launch_status();
 }
@@ -1791,10 +1663,7 @@ int align_finish_impl(const sp_gicp_source* source, float* transT_device, const 
     hipStream_t st = as_stream(stream);
     if (!source || !transT_device || !gn || last_k < 0 || rows_all_reduced < 0 || rows_all_reduced > 3)
         return SP_ERR_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(source->n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_workspace(workspace, workspace_bytes, source->n); rc != SP_OK) return rc;
     const AlignWs w = align_ws(workspace);
     if (source->opt_stage_mask & 2) {
         launch_solve(w, transT_device, gn, last_k, rows_all_reduced, lin_out, st, xchg,
@@ -1886,7 +1755,7 @@ static_assert(kTicketOffsetBytes + kTicketShards * kTicketStride * 4 <= (size_t)
 PersistGuard* persistent_ok(const sp_gicp_target* target, const sp_gicp_source* source, const sp_factor_params* params,
                             const sp_gn_params* gn, const float* T, void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (source->opt_persistent == 0 || source->opt_stage_mask != 3) return nullptr;
-    if (align_check("fused", target, source, params, gn, T, workspace, workspace_bytes) != SP_OK) return nullptr;  // (reported by the step)
+    if (align_check(target, source, params, gn, T, workspace, workspace_bytes) != SP_OK) return nullptr;  // (reported by the step)
     return persist_acquire(st, align_grid(source->n));
 }
 int launch_persistent(const sp_gicp_target* target, const sp_gicp_source* source, float* transT_device,
@@ -1897,15 +1766,12 @@ int launch_persistent(const sp_gicp_target* target, const sp_gicp_source* source
         PersistGuard* g; hipStream_t st;
         ~Release() { persist_release(g, st); }
     } release{guard, st};
-    const AlignWs w = align_ws(workspace);
     unsigned* const tickets = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + kTicketOffsetBytes);
     if (zero_async(tickets, kTicketShards * kTicketStride * sizeof(unsigned), st) != SP_OK) return SP_ERR_HIP;
     target->note(st);
     const FusedParams P = make_fused_params(target, source, params, transT_device, 1, nn_idx_out, nn_d2_out);
     PersistArgs A;
-    A.part[0] = w.part[0]; A.part[1] = w.part[1];
-    A.state = w.state;
-    A.searched_log = w.searched_log;
+    A.ws = align_ws(workspace);
     A.tickets = tickets;
     A.T_init = transT_device;
     A.lambda = gn->lambda; A.crit_rot = gn->crit_rotation; A.crit_trans = gn->crit_translation;
@@ -1918,27 +1784,12 @@ int launch_persistent(const sp_gicp_target* target, const sp_gicp_source* source
     A.cache_valid_later = (source->opt_reuse && P.ccache != nullptr) ? 1 : 0;
     A.budget = 50ull * 100000ull;  // 50 ms of wall_clock64 (100 MHz)
     const unsigned grid = align_grid(source->n);
-    const bool fast = source->opt_fast_nn < 0 ? source->sorted : (source->opt_fast_nn != 0);
-    const bool p2d = params->reg_type == SP_REG_POINT_TO_DISTRIBUTION;
-#define SP_LAUNCH_PERSIST(L)                                                                              \
-    if (fast && p2d) gicp_align_persistent_kernel<L, true, true><<<grid, kAlignBlock, 0, st>>>(P, A);      \
-    else if (fast) gicp_align_persistent_kernel<L, true, false><<<grid, kAlignBlock, 0, st>>>(P, A);       \
-    else if (p2d) gicp_align_persistent_kernel<L, false, true><<<grid, kAlignBlock, 0, st>>>(P, A);        \
-    else gicp_align_persistent_kernel<L, false, false><<<grid, kAlignBlock, 0, st>>>(P, A)
-#ifdef SP_DEV_MIN
-    if (params->robust_type != SP_LOSS_NONE || !fast || p2d) { sp_set_error("SP_DEV_MIN build"); return SP_ERR_RUNTIME; }
-    gicp_align_persistent_kernel<LOSS_NONE, true, false><<<grid, kAlignBlock, 0, st>>>(P, A);
-#else
-    switch (params->robust_type) {
-        case SP_LOSS_NONE: SP_LAUNCH_PERSIST(LOSS_NONE); break;
-        case SP_LOSS_HUBER: SP_LAUNCH_PERSIST(LOSS_HUBER); break;
-        case SP_LOSS_TUKEY: SP_LAUNCH_PERSIST(LOSS_TUKEY); break;
-        case SP_LOSS_CAUCHY: SP_LAUNCH_PERSIST(LOSS_CAUCHY); break;
-        case SP_LOSS_GEMAN_MCCLURE: SP_LAUNCH_PERSIST(LOSS_GEMAN_MCCLURE); break;
-        default: sp_set_error("[Registration::dispatch] Combination not found in tags!"); return SP_ERR_RUNTIME;
-    }
-#endif
-#undef SP_LAUNCH_PERSIST
+    const int rc = with_variant(params->robust_type, source_fast_nn(source), params->reg_type == SP_REG_POINT_TO_DISTRIBUTION,
+                                [&](auto L, auto FAST_NN, auto P2D) {
+        gicp_align_persistent_kernel<L, FAST_NN, P2D><<<grid, kAlignBlock, 0, st>>>(P, A);
+        return SP_OK;
+    });
+    if (rc != SP_OK) return rc;
     if (P.ccache != nullptr) { source->cache_valid = true; source->qcert_valid = false; }
     return launch_status();
 }

@@ -9,6 +9,8 @@
 #include "radix_sort.h"
 #include "sp_xchg.h"
 
+#include <type_traits>
+
 void sp_set_error(const char* msg);
 
 #include "sp_internal.h"
@@ -729,12 +731,6 @@ constexpr bool kSeedSearches = SP_SEED_SEARCHES != 0;
 #define SP_NEG_CERT 0
 #endif
 constexpr bool kNegCert = SP_NEG_CERT != 0;  // negative certificates in the per-iteration kernels of registration.hip (fused_point's NEG)
-// Whether the per-iteration kernels finish their open queries (nothing proven inside the 4x4x4 block) with the whole wave
-// (fused_point_wave) instead of each lane for itself. A / B on the same box: profiles/r05_c_*.
-#ifndef SP_WAVE_TAIL
-#define SP_WAVE_TAIL 0
-#endif
-constexpr bool kWaveTail = SP_WAVE_TAIL != 0;
 
 // The pose of a launch into scalar registers (it is uniform; it would otherwise occupy 12 VGPRs for the whole loop).
 __device__ __forceinline__ Rigid uniform_pose(const float* sT) {
@@ -748,8 +744,50 @@ __device__ __forceinline__ Rigid uniform_pose(const float* sT) {
     }
     return T;
 }
+// XCD-aware tile order: workgroup b runs on XCD b % 8, so give every XCD one contiguous eighth of the
+// (cell-ordered) source: the target cells it reads then stay in that XCD's own L2 from one grid row / layer to the next
+__device__ __forceinline__ unsigned xcd_tile() {
+    unsigned tile = blockIdx.x;
+    if ((gridDim.x & 7u) == 0u) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    return tile;
+}
+
+// The grid-wide hand-off between two steps of a persistent launch (gicp_align_persistent_kernel, and gicp_optimize_kernel where a
+// lane has a point to itself): every workgroup stores a partial row, then every workgroup reads all of them. An arrival counter
+// sharded over kTicketShards lines, zero when the launch starts and never reset in it, separates the two
+// (MI355X_MICROARCH.md, hand-off table, first row; cdna_hip_programming.md Guideline 16, the counter form with sc1 loads in place
+// of an acquire). Its conditions:
+//   * every word of the row was stored write-through at agent scope (store_row_word<true>: global_store ... sc1) by lanes of
+//     wave 0 of the workgroup,
+//   * grid_arrive (every lane of the workgroup calls it): wave 0 drains those stores (s_waitcnt vmcnt(0)) and only then lane 0
+//     adds 1 to the shard of its XCD — one lane signals for all its workgroup's stores; relaxed, agent scope,
+//   * grid_wait (ONE lane calls it): polls the shards with relaxed agent-scope loads and s_sleep until they add up to `want`
+//     (= grid * steps so far), bounded by `budget` wall_clock64 ticks — false when the bound ran out: a grid that is not fully
+//     resident ends with its error word set by the caller, never hangs,
+//   * after the poll has matched, the rows are read with sc1 loads only (load_row_word<true>, never a plain load of another
+//     workgroup's bytes): the polling wave after its poll, the others behind a workgroup barrier it joins.
 constexpr int kTicketShards = 8;
 constexpr int kTicketStride = 32;  // uint32 words between two shards (128 bytes: a line each)
+__device__ __forceinline__ void grid_arrive(unsigned* tickets) {
+    if (threadIdx.x < kWave) {  // the storing lanes all sit in wave 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0)
+            __hip_atomic_fetch_add(tickets + (blockIdx.x & (kTicketShards - 1)) * kTicketStride, 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__device__ __forceinline__ bool grid_wait(unsigned* tickets, unsigned want, unsigned long long budget) {
+    const unsigned long long t0 = wall_clock64();
+    for (;;) {
+        unsigned have = 0;
+#pragma unroll
+        for (int sh = 0; sh < kTicketShards; ++sh)
+            have += __hip_atomic_load(tickets + sh * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (have >= want) return true;
+        if (wall_clock64() - t0 > budget) return false;
+        __builtin_amdgcn_s_sleep(2);
+    }
+}
 
 }  // namespace
 }  // namespace sp
@@ -833,7 +871,7 @@ FusedParams make_fused_params(const sp_gicp_target* target, const sp_gicp_source
 }
 
 // The prepared forms exist for RegType::GICP and POINT_TO_DISTRIBUTION; the target's rows must be of the factor asked for.
-int check_prepared_reg(const char* who, const sp_gicp_target* target, const sp_factor_params* params) {
+int check_prepared_reg(const sp_gicp_target* target, const sp_factor_params* params) {
     if (params->reg_type != SP_REG_GICP && params->reg_type != SP_REG_POINT_TO_DISTRIBUTION) {
         sp_set_error("[sp_gicp_*] only RegType::GICP and RegType::POINT_TO_DISTRIBUTION have a prepared/fused form");
         return SP_ERR_INVALID_ARGUMENT;
@@ -846,13 +884,73 @@ int check_prepared_reg(const char* who, const sp_gicp_target* target, const sp_f
         sp_set_error("[sp_gicp_*] the rotation constraint needs the raw covariances: use sp_gicp_linearize");
         return SP_ERR_INVALID_ARGUMENT;
     }
-    (void)who;
+    return SP_OK;
+}
+
+int check_workspace(const void* workspace, size_t workspace_bytes, size_t n) {
+    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(n)) {
+        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
     return SP_OK;
 }
 
 unsigned align_grid(size_t n) {
     unsigned grid = div_up(n, kAlignBlock);
     return grid > (unsigned)kAlignMaxBlocks ? (unsigned)kAlignMaxBlocks : (grid ? grid : 1u);
+}
+
+// Which search a lane runs. Unsorted lanes touch unrelated cells: the ring walk (fewest cache lines per query) wins. Cell-sorted
+// lanes share their lines: the branch-light 2x2x2 walk wins (profiles/README.md, r01_c).
+bool source_fast_nn(const sp_gicp_source* source) {
+    return source->opt_fast_nn < 0 ? source->sorted : (source->opt_fast_nn != 0);
+}
+
+// Run-time choices -> template arguments (Registration::dispatch, registration.hpp:372-405): f gets the choice as a
+// std::integral_constant / std::bool_constant, instantiates its kernel with it, launches, and returns a status.
+// SP_DEV_MIN (development builds only, scratch/devbuild.sh: one instantiation of every kernel, a fraction of the compile time)
+// builds the first robust loss and, of a with_bool<DEV>, the DEV side only; everything else is an error at run time.
+#ifdef SP_DEV_MIN
+constexpr bool kDevMin = true;
+#else
+constexpr bool kDevMin = false;
+#endif
+inline int not_in_dev_build() {
+    sp_set_error("SP_DEV_MIN build: only GICP / NONE / sorted source / one GPU");
+    return SP_ERR_RUNTIME;
+}
+inline int unknown_combination() {  // (a RegType or robust loss outside the enums)
+    sp_set_error("[Registration::dispatch] Combination not found in tags!");
+    return SP_ERR_RUNTIME;
+}
+template <typename F>
+int with_loss(int robust_type, F&& f) {
+    if constexpr (kDevMin) {
+        return robust_type == SP_LOSS_NONE ? f(std::integral_constant<int, LOSS_NONE>{}) : not_in_dev_build();
+    } else {
+        switch (robust_type) {
+            case SP_LOSS_NONE: return f(std::integral_constant<int, LOSS_NONE>{});
+            case SP_LOSS_HUBER: return f(std::integral_constant<int, LOSS_HUBER>{});
+            case SP_LOSS_TUKEY: return f(std::integral_constant<int, LOSS_TUKEY>{});
+            case SP_LOSS_CAUCHY: return f(std::integral_constant<int, LOSS_CAUCHY>{});
+            case SP_LOSS_GEMAN_MCCLURE: return f(std::integral_constant<int, LOSS_GEMAN_MCCLURE>{});
+        }
+        return unknown_combination();
+    }
+}
+template <bool DEV, typename F>
+int with_bool(bool b, F&& f) {
+    if constexpr (kDevMin) return b == DEV ? f(std::bool_constant<DEV>{}) : not_in_dev_build();
+    else return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// The three choices every prepared-path kernel has: f(loss, FAST_NN, P2D).
+template <typename F>
+int with_variant(int robust_type, bool fast, bool p2d, F&& f) {
+    return with_loss(robust_type, [&](auto loss) {
+        return with_bool<true>(fast, [&](auto fast_c) {
+            return with_bool<false>(p2d, [&](auto p2d_c) { return f(loss, fast_c, p2d_c); });
+        });
+    });
 }
 
 }  // namespace

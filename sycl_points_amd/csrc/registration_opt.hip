@@ -12,10 +12,9 @@
 //   linearise  fused_point of the per-iteration Gauss-Newton kernel (certificate -> cached correspondence, else exact NN on
 //              the grid; 28 sums + inlier count)                                                -> one partial row per workgroup
 //   trial      error_prepared_point: K12 at the trial pose over the cache rows (frozen correspondences) -> one partial row
-// Between steps every workgroup waits for all rows (arrival counter sharded over 8 lines, one lane polls with sc1 loads and
-// s_sleep, bounded by wall_clock64 — the hand-off of gicp_align_persistent_kernel), sums them in reduce_rows_1024's fixed
-// order and lets ONE lane run the optimiser's state machine (opt_after_*) on LDS: every workgroup takes the same decisions from
-// the same bits, so nothing is broadcast. A launch of ONE workgroup (up to 1024 points: the reference pipeline's default
+// Between steps every workgroup waits for all rows (grid_arrive / grid_wait, registration_device.h: the hand-off
+// gicp_align_persistent_kernel uses), sums them in reduce_rows_1024's fixed order and lets ONE lane run the optimiser's state
+// machine (opt_after_*) on LDS: every workgroup takes the same decisions from the same bits, so nothing is broadcast. A launch of ONE workgroup (up to 1024 points: the reference pipeline's default
 // random sample) keeps its totals in LDS and touches no counter.
 // Rows ping-pong by step parity: a workgroup can only write the row of step s + 1 after every workgroup has stored the row
 // of step s, i.e. after every workgroup has finished reading the rows of step s - 1 that it overwrites.
@@ -211,8 +210,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_optimize_kernel(FusedParams P, Opt
     __shared__ float red[BLOCK / 32][kPartial];
     __shared__ unsigned s_wait;
     const unsigned stride = gridDim.x * BLOCK;
-    unsigned tile = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const unsigned tile = xcd_tile();
     const bool single = gridDim.x == 1;
     const bool publish = blockIdx.x == 0;
     if (threadIdx.x < 16) {
@@ -356,27 +354,8 @@ __global__ __launch_bounds__(BLOCK) void gicp_optimize_kernel(FusedParams P, Opt
                 return;
             }
         } else if (!single) {
-            // the hand-off of gicp_align_persistent_kernel: wave 0 (the storing lanes) drains its sc1 stores, lane 0 signals
-            if (threadIdx.x < kWave) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (threadIdx.x == 0) {
-                    __hip_atomic_fetch_add(A.tickets + (blockIdx.x & (kTicketShards - 1)) * kTicketStride, 1u, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned want = gridDim.x * (step + 1u);
-                    const unsigned long long t0 = wall_clock64();
-                    unsigned flag = 0;
-                    for (;;) {
-                        unsigned have = 0;
-#pragma unroll
-                        for (int sh = 0; sh < kTicketShards; ++sh)
-                            have += __hip_atomic_load(A.tickets + sh * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (have >= want) break;
-                        if (wall_clock64() - t0 > A.budget) { flag = 2; break; }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                    s_wait = flag;
-                }
-            }
+            grid_arrive(A.tickets);
+            if (threadIdx.x == 0) s_wait = grid_wait(A.tickets, gridDim.x * (step + 1u), A.budget) ? 0u : 2u;
             __syncthreads();
             if (s_wait == 2) {
                 wait_ran_out();
@@ -457,16 +436,13 @@ extern "C" int sp_gicp_align_optimize(const sp_gicp_target* target, const sp_gic
         sp_set_error("[sp_gicp_align_optimize] max_iterations must be in 1..65535 (0 iterations: the result is the initial guess)");
         return SP_ERR_INVALID_ARGUMENT;
     }
-    if (const int rc = check_prepared_reg("align_optimize", target, params); rc != SP_OK) return rc;
+    if (const int rc = check_prepared_reg(target, params); rc != SP_OK) return rc;
     const size_t n = source->n;
     if (n == 0) {
         sp_set_error("[sp_gicp_align_optimize] empty source (Registration::align returns the initial guess)");
         return SP_ERR_INVALID_ARGUMENT;
     }
-    if (!workspace || workspace_bytes < sp_gicp_workspace_bytes(n)) {
-        sp_set_error("[Registration] workspace too small (sp_gicp_workspace_bytes)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_workspace(workspace, workspace_bytes, n); rc != SP_OK) return rc;
     if (source->opt_persistent == 0) {
         sp_set_error("[sp_gicp_align_optimize] not available: persistent launches are switched off for this source "
                      "(sp_gicp_source_set_persistent)");
@@ -475,7 +451,7 @@ extern "C" int sp_gicp_align_optimize(const sp_gicp_target* target, const sp_gic
     // workgroups of 256 lanes while they all fit the device one per compute unit (64 K points), of 1024 beyond
     const bool small = n <= (size_t)256 * 256;
     const unsigned block = small ? 256u : (unsigned)kAlignBlock;
-    const bool fast = source->opt_fast_nn < 0 ? source->sorted : (source->opt_fast_nn != 0);
+    const bool fast = source_fast_nn(source);
     const bool waveq = fast && ((source->opt_wave_query == 1 && n <= kWaveQueryMax) || (source->opt_wave_query == 2 && n <= kWaveQueryForcedMax));
     // (wave per point: four waves a workgroup, each alone on its SIMD with 256 registers, up to two points a wave; beyond, sixteen
     // waves a workgroup: a wave then walks through its points one after the other and the other waves of its SIMD hide its round
@@ -534,29 +510,23 @@ extern "C" int sp_gicp_align_optimize(const sp_gicp_target* target, const sp_gic
         sp_set_error("[sp_gicp_align_optimize] the prepared target has no reuse certificates");
         return SP_ERR_INVALID_ARGUMENT;
     }
-    const bool p2d = params->reg_type == SP_REG_POINT_TO_DISTRIBUTION;
-#define SP_LAUNCH_OPT2(L, B)                                                                        \
-    if (fast && p2d) gicp_optimize_kernel<L, true, true, B><<<grid, B, 0, st>>>(P, A);              \
-    else if (fast) gicp_optimize_kernel<L, true, false, B><<<grid, B, 0, st>>>(P, A);               \
-    else if (p2d) gicp_optimize_kernel<L, false, true, B><<<grid, B, 0, st>>>(P, A);                \
-    else gicp_optimize_kernel<L, false, false, B><<<grid, B, 0, st>>>(P, A)
-#define SP_LAUNCH_OPT(L)                                                                           \
-    if (waveq && wq_block == 256u && p2d) gicp_optimize_kernel<L, true, true, 256, true><<<grid, 256, 0, st>>>(P, A);  \
-    else if (waveq && wq_block == 256u) gicp_optimize_kernel<L, true, false, 256, true><<<grid, 256, 0, st>>>(P, A);   \
-    else if (waveq && p2d) gicp_optimize_kernel<L, true, true, kAlignBlock, true><<<grid, kAlignBlock, 0, st>>>(P, A);  \
-    else if (waveq) gicp_optimize_kernel<L, true, false, kAlignBlock, true><<<grid, kAlignBlock, 0, st>>>(P, A);       \
-    else if (small) { SP_LAUNCH_OPT2(L, 256); }                                                    \
-    else { SP_LAUNCH_OPT2(L, kAlignBlock); }
-    switch (params->robust_type) {
-        case SP_LOSS_NONE: SP_LAUNCH_OPT(LOSS_NONE); break;
-        case SP_LOSS_HUBER: SP_LAUNCH_OPT(LOSS_HUBER); break;
-        case SP_LOSS_TUKEY: SP_LAUNCH_OPT(LOSS_TUKEY); break;
-        case SP_LOSS_CAUCHY: SP_LAUNCH_OPT(LOSS_CAUCHY); break;
-        case SP_LOSS_GEMAN_MCCLURE: SP_LAUNCH_OPT(LOSS_GEMAN_MCCLURE); break;
-        default: sp_set_error("[Registration::dispatch] Combination not found in tags!"); return SP_ERR_RUNTIME;
-    }
-#undef SP_LAUNCH_OPT2
-#undef SP_LAUNCH_OPT
+    const int rc = with_variant(params->robust_type, fast, params->reg_type == SP_REG_POINT_TO_DISTRIBUTION,
+                                [&](auto L, auto FAST_NN, auto P2D) {
+        constexpr int loss = L;
+        constexpr bool fast_nn = FAST_NN, p2d = P2D;
+        return with_bool<false>((waveq ? wq_block : block) == 256u, [&](auto SMALL) {
+            constexpr int B = decltype(SMALL)::value ? 256 : kAlignBlock;
+            if constexpr (fast_nn) {  // (a wave per point exists with the fast search only: waveq implies fast)
+                if (waveq) {
+                    gicp_optimize_kernel<loss, true, p2d, B, true><<<grid, B, 0, st>>>(P, A);
+                    return SP_OK;
+                }
+            }
+            gicp_optimize_kernel<loss, fast_nn, p2d, B><<<grid, B, 0, st>>>(P, A);
+            return SP_OK;
+        });
+    });
+    if (rc != SP_OK) return rc;
     source->cache_valid = true;
     source->qcert_valid = margin_certs;
     return launch_status();
