@@ -5,7 +5,8 @@
 //   algorithms/registration/{linearized_result,result}.hpp
 //   algorithms/registration/registration.hpp             : Registration (align, compute_linearized_result,
 //                                                          compute_error_frozen, compute_icp_robust_weights)
-//   algorithms/registration/pipeline/{aligner,robust}.hpp, registration_pipeline(_params).hpp
+//   algorithms/deskew/relative_pose_deskew.hpp           : deskew::deskew_point_cloud_constant_velocity
+//   algorithms/registration/pipeline/{aligner,velocity_update,robust}.hpp, registration_pipeline(_params).hpp
 // Host control flow follows the reference; every per-point kernel is a C-ABI call. When the KNNBase handed to align()
 // is a GridKNN and the factor is GICP, the iteration uses the prepared / fused kernel (sp_gicp_iteration_fused).
 #pragma once
@@ -24,6 +25,61 @@ namespace sycl_points {
 namespace algorithms {
 
 // robust::RobustLossType lives in features.hpp (covariance::estimate_robust_async needs it too)
+
+// ------------------------------------------------------------------------------------------------ deskew
+namespace deskew {
+
+/// deskew/relative_pose_deskew.hpp:36-178 — constant body velocity between two poses: every point is moved from the sensor
+/// frame at its own time stamp into the frame of `current_relative_pose`; normals and covariances are rotated with it. One
+/// kernel (sp_deskew_constant_velocity), data stays on the device. In place (`&input_cloud == &output_cloud`) is allowed and —
+/// unlike the reference, which zeroes its outputs before it reads its inputs — returns the rotated normals and covariances.
+/// false: an empty cloud, a cloud without time stamps, a duration <= 0.
+inline bool deskew_point_cloud_constant_velocity(const PointCloudShared& input_cloud, PointCloudShared& output_cloud,
+                                                 const Eigen::Isometry3f& previous_relative_pose,
+                                                 const Eigen::Isometry3f& current_relative_pose,
+                                                 float inter_scan_duration_seconds = -1.0f) {
+    if (!input_cloud.queue.ptr || !output_cloud.queue.ptr)
+        throw std::runtime_error("[deskew_point_cloud_constant_velocity] SYCL queue is not initialized");
+    const size_t N = input_cloud.size();
+    if (N == 0 || !input_cloud.has_timestamps()) return false;
+    const float duration = inter_scan_duration_seconds > 0.0f
+                               ? inter_scan_duration_seconds
+                               : static_cast<float>((input_cloud.end_time_ms - input_cloud.start_time_ms) * 1e-3);
+    if (duration <= 0.0f) return false;
+    const bool in_place = &input_cloud == &output_cloud;
+    const bool cov = input_cloud.has_cov(), nrm = input_cloud.has_normal();
+    if (!in_place) {  // :62-95: the output mirrors the input's timing and the attributes the deskew does not touch
+        output_cloud.start_time_ms = input_cloud.start_time_ms;
+        output_cloud.end_time_ms = input_cloud.end_time_ms;
+        *output_cloud.timestamp_offsets = *input_cloud.timestamp_offsets;
+        if (!nrm) output_cloud.normals->clear();
+        if (!cov) output_cloud.covs->clear();
+        if (input_cloud.has_rgb()) *output_cloud.rgb = *input_cloud.rgb; else output_cloud.rgb->clear();
+        if (input_cloud.has_intensity()) *output_cloud.intensities = *input_cloud.intensities; else output_cloud.intensities->clear();
+    }
+    float twist[6];
+    sp_relative_twist_host(previous_relative_pose.matrix().data(), current_relative_pose.matrix().data(), twist);
+    const float* ts = input_cloud.timestamp_offsets->device_data();
+    const float *pin, *cin = nullptr, *nin = nullptr;
+    float *pout, *cout = nullptr, *nout = nullptr;
+    if (in_place) {
+        pin = pout = reinterpret_cast<float*>(output_cloud.points->device_data_rw());
+        if (cov) cin = cout = reinterpret_cast<float*>(output_cloud.covs->device_data_rw());
+        if (nrm) nin = nout = reinterpret_cast<float*>(output_cloud.normals->device_data_rw());
+    } else {
+        pin = input_cloud.points_device();
+        cin = input_cloud.covs_device();
+        nin = input_cloud.normals_device();
+        pout = reinterpret_cast<float*>(output_cloud.points->device_data_for_write(N));  // (resize: every row is written)
+        if (cov) cout = reinterpret_cast<float*>(output_cloud.covs->device_data_for_write(N));
+        if (nrm) nout = reinterpret_cast<float*>(output_cloud.normals->device_data_for_write(N));
+    }
+    throw_on_error(sp_deskew_constant_velocity(pin, cin, nin, ts, N, twist, duration, pout, cout, nout, input_cloud.queue.stream()));
+    sycl_utils::events(input_cloud.queue.stream()).wait_and_throw();  // :175
+    return true;
+}
+
+}  // namespace deskew
 
 namespace registration {
 
@@ -787,15 +843,70 @@ struct RegistrationRobustScheduleParams {
     float init_scale = 10.0f, min_scale = 0.5f, rotation_init_scale = 10.0f, rotation_min_scale = 0.5f;
     size_t auto_scaling_iter = 4;
 };
+struct RegistrationVelocityUpdateParams { bool enable = false; size_t iter = 1; };
 struct RegistrationPipelineParams {
     using RandomSampling = RegistrationRandomSamplingParams;
     using Robust = RegistrationRobustScheduleParams;
+    using VelocityUpdate = RegistrationVelocityUpdateParams;
     RegistrationParams registration;
     RandomSampling random_sampling;
     Robust robust;
+    VelocityUpdate velocity_update;
 };
 
 namespace pipeline {
+/// pipeline/velocity_update.hpp:16-104 — repeats deskew and registration assuming constant sensor velocity: each round
+/// deskews the source with the motion from options.prev_pose to the pose the previous round ended on (over options.dt), into
+/// a cloud of its own, and aligns that.
+class VelocityUpdateAligner {
+public:
+    using Ptr = std::shared_ptr<VelocityUpdateAligner>;
+    VelocityUpdateAligner(RegistrationAligner aligner, size_t velocity_update_iter, bool verbose = false)
+        : aligner_(std::move(aligner)), velocity_update_iter_(velocity_update_iter), verbose_(verbose) {}
+    VelocityUpdateAligner(const Registration::Ptr& registration, size_t velocity_update_iter, bool verbose = false)
+        : VelocityUpdateAligner(make_registration_aligner(registration), velocity_update_iter, verbose) {}
+    RegistrationResult align(const PointCloudShared& source, const PointCloudShared& target, const knn::KNNBase& target_knn,
+                             const TransformMatrix& initial_guess = TransformMatrix::Identity(),
+                             const Registration::ExecutionOptions& options = Registration::ExecutionOptions()) const {
+        RegistrationResult result;
+        result.T.matrix() = initial_guess;
+        if (source.size() == 0) return result;
+        deskewed_pc_ = std::make_shared<PointCloudShared>(source.queue);  // the deskew writes into a cloud that aliases nothing
+        if (!source.has_timestamps()) {
+            if (verbose_) std::cout << "deskew skipped: source has no timestamps" << std::endl;
+            *deskewed_pc_ = source;  // shallow
+            return aligner_(*deskewed_pc_, target, target_knn, result.T.matrix(), options);
+        }
+        const Eigen::Isometry3f prev(options.prev_pose);
+        const size_t rounds = std::max<size_t>(1, velocity_update_iter_);
+        for (size_t round = 0; round < rounds; ++round) {
+            if (verbose_) {
+                float twist[6];
+                sp_relative_twist_host(prev.matrix().data(), result.T.matrix().data(), twist);
+                const float angle = std::sqrt(twist[0] * twist[0] + twist[1] * twist[1] + twist[2] * twist[2]);
+                const float dist = std::sqrt(twist[3] * twist[3] + twist[4] * twist[4] + twist[5] * twist[5]);
+                std::cout << "deskewed: " << round << std::endl;
+                std::cout << "deskewed[" << round << "]: angle=" << angle << ", dist=" << dist << std::endl;
+            }
+            deskew::deskew_point_cloud_constant_velocity(source, *deskewed_pc_, prev, result.T, options.dt);
+            result = aligner_(*deskewed_pc_, target, target_knn, result.T.matrix(), options);
+        }
+        return result;
+    }
+    /// the deskewed source of the most recent align(); null before the first
+    const PointCloudShared::Ptr get_deskewed_point_cloud() const { return deskewed_pc_; }
+    RegistrationAligner make_aligner() const {
+        return [this](const PointCloudShared& s, const PointCloudShared& t, const knn::KNNBase& k, const TransformMatrix& T,
+                      const Registration::ExecutionOptions& o) { return this->align(s, t, k, T, o); };
+    }
+
+private:
+    RegistrationAligner aligner_;
+    size_t velocity_update_iter_ = 1;
+    bool verbose_ = false;
+    mutable PointCloudShared::Ptr deskewed_pc_ = nullptr;
+};
+
 /// pipeline/robust.hpp:17-128 — geometric annealing of the robust scale around the wrapped aligner.
 class RobustAligner {
 public:
@@ -862,7 +973,8 @@ private:
 };
 }  // namespace pipeline
 
-/// registration_pipeline.hpp:16-149 — optional random sampling of the source, then (annealed) alignment.
+/// registration_pipeline.hpp:16-149 — optional random sampling of the source, then (annealed) alignment, each level through the
+/// optional deskew-and-realign rounds of the velocity update.
 class RegistrationPipeline {
 public:
     using Ptr = std::shared_ptr<RegistrationPipeline>;
@@ -896,9 +1008,11 @@ public:
         registration_->compute_icp_robust_weights(*source, target, target_knn, pose, robust_scale, out);
     }
     const PointCloudShared* get_registration_input_point_cloud() const { return input_.get(); }
-    /// registration_pipeline.hpp:82-89. The velocity-update (deskew) stage is outside this library's scope,
-    /// so this is always the registration input — what the reference returns with velocity_update disabled.
-    const PointCloudShared::Ptr get_deskewed_point_cloud() const { return input_; }
+    /// registration_pipeline.hpp:82-89: the deskewed source of the latest align(); the registration input with velocity_update off
+    const PointCloudShared::Ptr get_deskewed_point_cloud() const {
+        if (velocity_update_ != nullptr) return velocity_update_->get_deskewed_point_cloud();
+        return input_;
+    }
     /// registration_pipeline.hpp:91-97
     float get_inlier_ratio(const RegistrationResult& result) const {
         const auto* in = get_registration_input_point_cloud();
@@ -907,11 +1021,20 @@ public:
     }
 
 private:
-    void wrap_aligner() {  // registration_pipeline.hpp:100-119 (robust wrapper outermost)
+    /// registration_pipeline.hpp:100-119: RobustAligner -> VelocityUpdateAligner -> base aligner (for each robust scale, for each
+    /// deskew update: align)
+    void wrap_aligner() {
+        if (params_.velocity_update.enable) {
+            velocity_update_ = std::make_shared<pipeline::VelocityUpdateAligner>(aligner_, params_.velocity_update.iter,
+                                                                                 params_.registration.verbose);
+            aligner_ = velocity_update_->make_aligner();
+        }
         if (params_.robust.auto_scale) {
-            // (no velocity-update wrapper sits between the two in this library, so the robust wrapper may talk to the backend)
-            robust_ = registration_ != nullptr ? std::make_shared<pipeline::RobustAligner>(registration_, params_)
-                                               : std::make_shared<pipeline::RobustAligner>(aligner_, params_);
+            // (with nothing between the two the robust wrapper talks to the backend: all levels in one launch; with the velocity
+            // update in between it is the host loop over the levels, each inner Registration::align one device-resident launch)
+            robust_ = registration_ != nullptr && velocity_update_ == nullptr
+                          ? std::make_shared<pipeline::RobustAligner>(registration_, params_)
+                          : std::make_shared<pipeline::RobustAligner>(aligner_, params_);
             aligner_ = robust_->make_aligner();
         }
     }
@@ -927,6 +1050,7 @@ private:
     RegistrationPipelineParams params_;
     Registration::Ptr registration_;
     pipeline::RobustAligner::Ptr robust_;
+    pipeline::VelocityUpdateAligner::Ptr velocity_update_;
     pipeline::RegistrationAligner aligner_;
     mutable filter::PreprocessFilter::Ptr filter_;
     mutable PointCloudShared::Ptr input_;

@@ -347,6 +347,24 @@ int sp_polar_downsample_report(const float* points, size_t n, int coord, float d
 int sp_transform(const float* points, const float* covs, const float* normals, size_t n, const float* transT_host,
                  float* points_out, float* covs_out, float* normals_out, void* stream);
 
+/* deskew::deskew_point_cloud_constant_velocity's kernel (algorithms/deskew/relative_pose_deskew.hpp:120-172): every point is
+ * moved from the sensor frame at its own sampling time into the frame at the end of the motion delta_twist6_host (se3_log of
+ * the motion over scan_duration_seconds, rotation first, HOST memory). Per point: ts = t_ms * 1e-3f; a non-finite ts copies
+ * the row (point, normal, all 16 floats of the covariance); otherwise tau = clamp(ts / scan_duration_seconds, 0, 1),
+ * M = se3_exp(twist * tau), p' = M p, n' = (R n, 0), C' = R (C3 R^T) in the top-left 3x3 of a zeroed 4x4, R the rotation of M.
+ * covs / normals may be NULL (together with their outputs). In place allowed (*_out == *_in): every row is read before it
+ * is written, so an in-place call returns the rotated normals and covariances — the reference, which zeroes its outputs
+ * before it reads its inputs, returns zeros there. A null points / timestamp_offsets_ms / points_out / twist, covs or normals
+ * given without their output or the other way round, a duration that is not positive and finite, n >= 2^32 ->
+ * SP_ERR_INVALID_ARGUMENT before any HIP call. n == 0: SP_OK, nothing enqueued. Enqueue only. */
+int sp_deskew_constant_velocity(const float* points, const float* covs, const float* normals,
+                                const float* timestamp_offsets_ms, size_t n, const float* delta_twist6_host,
+                                float scan_duration_seconds, float* points_out, float* covs_out, float* normals_out,
+                                void* stream);
+/* se3_log(prev^-1 * cur), inverse and product as Eigen's Isometry3f forms them (relative_pose_deskew.hpp:103-104,
+ * pipeline/velocity_update.hpp:71-72): the twist sp_deskew_constant_velocity takes. Poses column-major 4x4. Host only. */
+void sp_relative_twist_host(const float* prev_pose16, const float* cur_pose16, float* twist6_out);
+
 /* BoxFilterOperator kernel (filter/preprocess_operator/box_filter_operator.hpp:36-44, common.hpp:15-25, K10):
  * flags_out[i] = 1 keep / 0 remove. */
 int sp_box_filter_flags(const float* points, size_t n, float min_distance, float max_distance, uint8_t* flags_out,

@@ -771,6 +771,44 @@ def transform_copy(cloud, T):
     return transform(out, T)
 
 
+def relative_twist(previous_pose, current_pose):
+    """se3_log(previous_pose^-1 * current_pose) as the deskew takes it (sp_relative_twist_host): 6 floats, rotation first."""
+    tw = np.zeros(6, np.float32)
+    a, b = _T16(previous_pose), _T16(current_pose)
+    _lib.lib().sp_relative_twist_host(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), tw.ctypes.data_as(C.c_void_p))
+    return tw
+
+
+def deskew_point_cloud_constant_velocity(cloud, previous_pose, current_pose, inter_scan_duration_seconds=-1.0):
+    """deskew::deskew_point_cloud_constant_velocity (deskew/relative_pose_deskew.hpp:36-178): a new cloud with every point moved
+    from the sensor frame at its time stamp (timestamp_offsets, ms) into the frame of `current_pose`, assuming constant body
+    velocity from `previous_pose`; normals and covariances are rotated with it, the other attributes are shared. None where the
+    reference returns false: an empty cloud, no time stamps, or no positive duration (the fallback is the cloud's own
+    (end_time_ms - start_time_ms) * 1e-3 when it carries those attributes)."""
+    n = cloud.size()
+    if n == 0 or not cloud.has_timestamps():
+        return None
+    duration = np.float32(inter_scan_duration_seconds)
+    if not duration > 0.0:
+        duration = np.float32((float(getattr(cloud, "end_time_ms", 0.0)) - float(getattr(cloud, "start_time_ms", 0.0))) * 1e-3)
+    if not duration > 0.0:
+        return None
+    p = _dev_f32(cloud.points, 4)
+    ts = _dev_f32(cloud.timestamp_offsets)
+    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
+    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
+    out = PointCloudShared(torch.empty_like(p), None if covs is None else torch.empty_like(covs),
+                           None if nrm is None else torch.empty_like(nrm), cloud.rgb, cloud.intensities, cloud.timestamp_offsets,
+                           device=p.device)
+    tw = relative_twist(previous_pose, current_pose)
+    check(_lib.lib().sp_deskew_constant_velocity(_ptr(p), _ptr(covs), _ptr(nrm), _ptr(ts), n, tw.ctypes.data_as(C.c_void_p),
+                                                 float(duration), _ptr(out.points), _ptr(out.covs), _ptr(out.normals), _stream()))
+    for k in ("start_time_ms", "end_time_ms"):
+        if hasattr(cloud, k):
+            setattr(out, k, getattr(cloud, k))
+    return out
+
+
 def box_filter_flags(points, min_distance, max_distance):
     p = _dev_f32(_points_of(points), 4)
     flags = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
