@@ -3,7 +3,11 @@
 //   algorithms/filter/voxel_downsampling.hpp     : filter::VoxelGrid
 //   algorithms/filter/polar_downsampling.hpp     : filter::PolarGrid
 //   algorithms/common/coordinate_system.hpp      : CoordinateSystem, coordinate_system_from_string
-//   algorithms/filter/preprocess_filter.hpp      : filter::PreprocessFilter (box_filter, random_sampling)
+//   algorithms/filter/preprocess_filter.hpp      : filter::PreprocessFilter (box_filter, random_sampling, farthest_point_sampling,
+//                                                  angle_incidence_filter)
+//   algorithms/filter/intensity_correction.hpp   : intensity_correction::correct_intensity
+//   algorithms/filter/intensity_gaussian.hpp     : intensity_gaussian::smooth_intensity
+//   algorithms/filter/intensity_local_mean_norm.hpp : intensity_local_mean_norm::normalize
 //   algorithms/common/filter_by_flags.hpp        : filter::FilterByFlags
 //   algorithms/common/transform.hpp              : transform::transform, transform_copy
 #pragma once
@@ -647,6 +651,20 @@ public:
         }
     }
     void farthest_point_sampling(PointCloudShared& data, size_t sampling_num) { farthest_point_sampling(data, data, sampling_num); }
+    /// preprocess_filter.hpp:147-160, 276-279 + preprocess_operator/angle_incidence_filter_operator.hpp:23-110: the flags on the
+    /// device (sp_angle_incidence_flags: the cloud's normals, else extract_normal of its covariances), then every attribute through
+    /// the flags path on the same stream: nothing waits in between, one count is read back. An empty source returns before any
+    /// check and leaves the output as it is; the checks and their texts are the reference's (the library reports them).
+    void angle_incidence_filter(const PointCloudShared& source, PointCloudShared& output, float min_angle, float max_angle) {
+        const size_t N = source.size();
+        if (N == 0) return;
+        throw_on_error(sp_angle_incidence_flags(source.points_device(), source.normals_device(), source.covs_device(), N, min_angle,
+                                                max_angle, flags_->device_data_for_write(N), queue_.stream()));
+        apply_flags(source, output);
+    }
+    void angle_incidence_filter(PointCloudShared& data, float min_angle, float max_angle) {
+        angle_incidence_filter(data, data, min_angle, max_angle);
+    }
 
 private:
     /// output = the rows `picked` of every attribute of source (sp_gather_rows_multi)
@@ -763,6 +781,69 @@ private:
 };
 
 }  // namespace filter
+
+// ================================================================================================ intensity filters
+namespace intensity_correction {
+
+/// filter/intensity_correction.hpp:50-135, in place (sp_intensity_correct: the reference's checks in its order and their texts)
+inline void correct_intensity(PointCloudShared& cloud, float exponent = 2.0f, float scale = 1.0f, float min_intensity = 0.0f,
+                              float max_intensity = 1000.0f, float ref_distance = 1.0f, float angle_exponent = 0.0f) {
+    const size_t N = cloud.size();
+    if (N == 0) return;
+    float* const inten = cloud.has_intensity() ? cloud.intensities->device_data_rw() : nullptr;
+    if (inten) cloud.intensities->set_device_size(N);
+    throw_on_error(sp_intensity_correct(cloud.points_device(), cloud.normals_device(), cloud.covs_device(), inten, N, exponent, scale,
+                                        min_intensity, max_intensity, ref_distance, angle_exponent, cloud.queue.stream()));
+    cloud.queue.wait();
+}
+
+}  // namespace intensity_correction
+
+namespace detail {
+/// smooth_intensity / normalize: a fresh intensity vector written by sp_intensity_gaussian and swapped into the cloud
+/// (intensity_gaussian.hpp:116-150, intensity_local_mean_norm.hpp:76-112); mean_min <= 0 selects the smoothing
+inline void intensity_gaussian_swap(PointCloudShared& cloud, const knn::KNNResult& neighbors, float sigma_azimuth,
+                                    float sigma_elevation, float sigma_range, float mean_min, size_t k_limit) {
+    const size_t N = cloud.size();
+    const size_t k_stride = neighbors.k;
+    const size_t k_use = (k_limit > 0 && k_limit < k_stride) ? k_limit : k_stride;
+    const bool usable = cloud.has_intensity() && k_stride >= 1;  // (otherwise the library reports what is missing)
+    auto tmp = std::make_shared<IntensityContainerShared>(cloud.queue);
+    throw_on_error(sp_intensity_gaussian(cloud.points_device(), cloud.has_intensity() ? cloud.intensities->device_data() : nullptr,
+                                         usable && neighbors.indices ? neighbors.indices->device_data() : nullptr, N, k_stride, k_use,
+                                         sigma_azimuth, sigma_elevation, sigma_range, mean_min,
+                                         usable ? tmp->device_data_for_write(N) : nullptr, cloud.queue.stream()));
+    cloud.queue.wait();
+    std::swap(cloud.intensities, tmp);
+}
+}  // namespace detail
+
+namespace intensity_gaussian {
+
+/// filter/intensity_gaussian.hpp:88-151
+inline void smooth_intensity(PointCloudShared& cloud, const knn::KNNResult& neighbors, float sigma_azimuth, float sigma_elevation,
+                             float sigma_range = 0.05f, size_t k_limit = 0) {
+    if (cloud.size() == 0) return;
+    detail::intensity_gaussian_swap(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, 0.0f, k_limit);
+}
+
+}  // namespace intensity_gaussian
+
+namespace intensity_local_mean_norm {
+
+/// filter/intensity_local_mean_norm.hpp:36-113
+inline void normalize(PointCloudShared& cloud, const knn::KNNResult& neighbors, float sigma_azimuth, float sigma_elevation,
+                      float sigma_range = 0.05f, float mean_min = 1e-3f, size_t k_limit = 0) {
+    if (cloud.size() == 0) return;
+    if (mean_min <= 0.0f) {  // the last of the reference's checks (:72-74); the ones before it are the library's, in its order
+        if (cloud.has_intensity() && neighbors.k >= 1 && !(sigma_azimuth <= 0.0f || sigma_elevation <= 0.0f || sigma_range <= 0.0f))
+            throw std::runtime_error("[intensity_local_mean_norm::normalize] mean_min must be positive");
+        mean_min = 1.0f;  // (selects the normalisation's texts)
+    }
+    detail::intensity_gaussian_swap(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, mean_min, k_limit);
+}
+
+}  // namespace intensity_local_mean_norm
 
 // ================================================================================================ transform
 namespace transform {

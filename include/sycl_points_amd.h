@@ -365,6 +365,39 @@ int sp_deskew_constant_velocity(const float* points, const float* covs, const fl
  * pipeline/velocity_update.hpp:71-72): the twist sp_deskew_constant_velocity takes. Poses column-major 4x4. Host only. */
 void sp_relative_twist_host(const float* prev_pose16, const float* cur_pose16, float* twist6_out);
 
+/* ------------------------------------------------------------------- scan filters after kNN and covariances */
+
+/* AngleIncidenceFilterOperator::apply's kernel and checks (filter/preprocess_operator/angle_incidence_filter_operator.hpp:23-110):
+ * flags_out[i] = 1 keep / 0 remove. A point with a non-finite component is removed; the normal is normals[i] when normals is
+ * given (it wins, :73), else extract_normal(p, covs[i]) — the function sp_normals_from_cov stores, so both paths agree bit for
+ * bit; dot = dot<3>(p, n), denom = |p| * |n| (frobenius_norm<3>); denom <= 1e-6f is removed; so is |dot / denom| outside
+ * [cos(max_angle), cos(min_angle)] (both cosines: std::cos on the host, :55-56). n == 0: SP_OK before any check, nothing enqueued.
+ * Neither normals nor covs -> SP_ERR_RUNTIME; min_angle < 0, max_angle > pi/2 or min_angle >= max_angle ->
+ * SP_ERR_INVALID_ARGUMENT, both with the reference's text (:27-34). The caller compacts with sp_compact_by_flags_multi on the same
+ * stream. Enqueue only. */
+int sp_angle_incidence_flags(const float* points, const float* normals, const float* covs, size_t n, float min_angle,
+                             float max_angle, uint8_t* flags_out, void* stream);
+/* intensity_correction::correct_intensity (filter/intensity_correction.hpp:20-135), in place:
+ * I' = clamp(I * pow(|p| / ref_distance, exponent) * angle_factor * scale, min_intensity, max_intensity), the products in that
+ * order (:34-37); angle_factor = pow(max(|cos|, 1e-3f), -angle_exponent) with the cosine of sp_angle_incidence_flags, and 1 when
+ * angle_exponent == 0, when neither normals nor covs is given, or when denom <= 1e-6f. Normals win over covs (:100-128).
+ * n == 0: SP_OK before any check. exponent < 0, ref_distance <= 0, a null intensities -> SP_ERR_RUNTIME with the reference's
+ * text (:60-68). Enqueue only. */
+int sp_intensity_correct(const float* points, const float* normals, const float* covs, float* intensities, size_t n,
+                         float exponent, float scale, float min_intensity, float max_intensity, float ref_distance,
+                         float angle_exponent, void* stream);
+/* intensity_gaussian::kernel::compute (filter/intensity_gaussian.hpp:37-86) when mean_min <= 0: out[i] = sum w I / sum w over the
+ * first k_use entries of row i of knn_indices (rows of k_stride entries), w = exp(-(dr^2 inv2_r + daz^2 inv2_az + del^2 inv2_el))
+ * in the sensor-local basis of point i, inv2 = 0.5f / sigma^2 formed on the host; |p| < 1e-6f and sum w == 0 give I[i].
+ * intensity_local_mean_norm::kernel::compute (filter/intensity_local_mean_norm.hpp:26-32) when mean_min > 0:
+ * out[i] = I[i] / fmax(that mean, mean_min). A neighbour index outside [0, n) is skipped (the reference reads out of bounds;
+ * KNNResult pads with -1). intensities_out must not be intensities_in (SP_ERR_INVALID_ARGUMENT): the kernel reads neighbours.
+ * k_stride < 1, a sigma <= 0, a null intensities_in -> SP_ERR_RUNTIME with the text of the function mean_min selects (:103-111 /
+ * :60-71); k_use outside [1, k_stride], n >= 2^31 -> SP_ERR_INVALID_ARGUMENT. n == 0: SP_OK before any check. Enqueue only. */
+int sp_intensity_gaussian(const float* points, const float* intensities_in, const int32_t* knn_indices, size_t n, size_t k_stride,
+                          size_t k_use, float sigma_azimuth, float sigma_elevation, float sigma_range, float mean_min,
+                          float* intensities_out, void* stream);
+
 /* BoxFilterOperator kernel (filter/preprocess_operator/box_filter_operator.hpp:36-44, common.hpp:15-25, K10):
  * flags_out[i] = 1 keep / 0 remove. */
 int sp_box_filter_flags(const float* points, size_t n, float min_distance, float max_distance, uint8_t* flags_out,

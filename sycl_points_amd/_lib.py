@@ -157,6 +157,9 @@ SIGNATURES = {
                                         _sz, _vp]),
     "sp_transform": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sp_deskew_constant_velocity": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, _vp, _vp, _vp, _vp]),
+    "sp_angle_incidence_flags": (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp, _vp]),
+    "sp_intensity_correct": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp]),
+    "sp_intensity_gaussian": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _f, _f, _f, _f, _vp, _vp]),
     "sp_relative_twist_host": (None, [_vp, _vp, _vp]),
     "sp_box_filter_flags": (_i, [_vp, _sz, _f, _f, _vp, _vp]),
     "sp_compact_workspace_bytes": (_sz, [_sz]),

@@ -832,6 +832,96 @@ def compact_by_flags(rows, flags, want_indices=False):
     return (out[:v], idx) if want_indices else out[:v]
 
 
+def _normals_or_covs(cloud):
+    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
+    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
+    return nrm, covs
+
+
+def angle_incidence_filter(cloud, min_angle, max_angle, return_flags=False):
+    """PreprocessFilter::angle_incidence_filter (filter/preprocess_filter.hpp:147-160, preprocess_operator/
+    angle_incidence_filter_operator.hpp:23-110): a new cloud with the points whose angle of incidence (between the ray from the
+    origin and the normal, sign ignored) lies in [min_angle, max_angle]; the normal is the cloud's, or extract_normal of its
+    covariance. Every attribute is compacted by the same flags (sp_angle_incidence_flags, then sp_compact_by_flags_multi on the
+    same stream, one count read back). An empty cloud comes back as it is, before any check."""
+    n = cloud.size()
+    if n == 0:
+        return (cloud, None) if return_flags else cloud
+    L = _lib.lib()
+    p = _dev_f32(cloud.points, 4)
+    nrm, covs = _normals_or_covs(cloud)
+    flags = torch.empty(n, dtype=torch.uint8, device=p.device)
+    check(L.sp_angle_incidence_flags(_ptr(p), _ptr(nrm), _ptr(covs), n, min_angle, max_angle, _ptr(flags), _stream()))
+    names = [k for k, has in (("points", True), ("covs", cloud.has_cov()), ("normals", cloud.has_normal()), ("rgb", cloud.has_rgb()),
+                              ("intensities", cloud.has_intensity()), ("timestamp_offsets", cloud.has_timestamps())) if has]
+    src = [getattr(cloud, k) for k in names]
+    for t in src:
+        if not (t.is_cuda and t.is_contiguous()):
+            raise SpError(1, "expected contiguous CUDA tensors")
+    dst = [torch.empty_like(t) for t in src]
+    na = len(src)
+    rows = (C.c_void_p * na)(*[t.data_ptr() for t in src])
+    rows_out = (C.c_void_p * na)(*[t.data_ptr() for t in dst])
+    row_bytes = (C.c_size_t * na)(*[t.element_size() * (t.numel() // n) for t in src])
+    n_out = torch.zeros(1, dtype=torch.int32, device=p.device)
+    nbytes = L.sp_compact_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    check(L.sp_compact_by_flags_multi(rows, row_bytes, rows_out, na, n, _ptr(flags), None, _ptr(n_out), _ptr(ws), nbytes, _stream()))
+    m = int(n_out.item())
+    out = PointCloudShared(device=p.device)
+    for k, t in zip(names, dst):
+        setattr(out, k, t[:m])
+    for k in ("start_time_ms", "end_time_ms"):
+        if hasattr(cloud, k):
+            setattr(out, k, getattr(cloud, k))
+    return (out, flags) if return_flags else out
+
+
+def correct_intensity(cloud, exponent=2.0, scale=1.0, min_intensity=0.0, max_intensity=1000.0, ref_distance=1.0, angle_exponent=0.0):
+    """intensity_correction::correct_intensity (filter/intensity_correction.hpp:50-135): cloud.intensities in place,
+    I' = clamp(I * (|p| / ref_distance)^exponent * angle_factor * scale, min, max); the angle factor needs normals or covariances
+    and a non-zero angle_exponent. The reference's checks in its order; an empty cloud returns before them."""
+    n = cloud.size()
+    if n == 0:
+        return
+    nrm, covs = _normals_or_covs(cloud)
+    inten = _dev_f32(cloud.intensities) if cloud.has_intensity() else None
+    check(_lib.lib().sp_intensity_correct(_ptr(_dev_f32(cloud.points, 4)), _ptr(nrm), _ptr(covs), _ptr(inten), n, exponent, scale,
+                                          min_intensity, max_intensity, ref_distance, angle_exponent, _stream()))
+
+
+def _intensity_gaussian(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, mean_min, k_limit):
+    n = cloud.size()
+    if n == 0:
+        return
+    idx = neighbors.indices if isinstance(neighbors, KNNResult) else neighbors
+    k = int(idx.shape[1]) if idx.dim() == 2 else 0
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or (k and idx.shape[0] != n):
+        raise SpError(1, "expected a contiguous int32 (N, k) tensor of neighbour indices")
+    k_use = k_limit if 0 < k_limit < k else k
+    inten = _dev_f32(cloud.intensities) if cloud.has_intensity() else None
+    out = None if inten is None else torch.empty_like(inten)
+    check(_lib.lib().sp_intensity_gaussian(_ptr(_dev_f32(cloud.points, 4)), _ptr(inten), _ptr(idx), n, k, k_use, sigma_azimuth,
+                                           sigma_elevation, sigma_range, mean_min, _ptr(out), _stream()))
+    cloud.intensities = out  # (the reference swaps a fresh vector in)
+
+
+def smooth_intensity(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range=0.05, k_limit=0):
+    """intensity_gaussian::smooth_intensity (filter/intensity_gaussian.hpp:88-151): cloud.intensities replaced by their
+    directional Gaussian mean over the first k_limit (0: all) neighbours of `neighbors` (a KNNResult of the cloud on itself)."""
+    _intensity_gaussian(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, 0.0, k_limit)
+
+
+def normalize_intensity_local_mean(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range=0.05, mean_min=1e-3, k_limit=0):
+    """intensity_local_mean_norm::normalize (filter/intensity_local_mean_norm.hpp:36-113): I / max(local mean, mean_min)."""
+    if cloud.size() and mean_min <= 0.0:  # (:72-74: the last of the reference's checks; the library reports the ones before it)
+        k = neighbors.k if isinstance(neighbors, KNNResult) else (neighbors.shape[1] if neighbors.dim() == 2 else 0)
+        if cloud.has_intensity() and k >= 1 and min(sigma_azimuth, sigma_elevation, sigma_range) > 0.0:
+            raise SpError(2, "[intensity_local_mean_norm::normalize] mean_min must be positive")
+        mean_min = 1.0  # (selects the normalisation's texts)
+    _intensity_gaussian(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, mean_min, k_limit)
+
+
 @dataclass
 class FpsResult:
     order: torch.Tensor   # int32 [S]: the i-th selected index, repeats included
