@@ -35,10 +35,3 @@ print("self kNN k=3 on the ppc 0.5 grid  %.3f ms"%wall(lambda: g.self_knn(3,want
 print("self kNN k=3 on the ppc 6 grid    %.3f ms"%wall(lambda: g6.self_knn(3,want_knn=True,want_covs=False)))
 g2=sp.GridKNN.build(tp,points_per_cell=2.0)
 print("self kNN k=3 on a ppc 2 grid      %.3f ms"%wall(lambda: g2.self_knn(3,want_knn=True,want_covs=False)))
-from sycl_points_amd import _lib
-[x._set_option('self_knn_mode',1) for x in (g,g2,g6)]
-print("mode 1 (lane per query): k=3 ppc 0.5 %.3f ms | ppc 2 %.3f ms | ppc 6 %.3f ms"%(wall(lambda: g.self_knn(3,want_knn=True,want_covs=False)),wall(lambda: g2.self_knn(3,want_knn=True,want_covs=False)),wall(lambda: g6.self_knn(3,want_knn=True,want_covs=False))))
-a=g.self_knn(3,want_knn=True,want_covs=False)[0]
-[x._set_option('self_knn_mode',0) for x in (g,g2,g6)]
-b=g.self_knn(3,want_knn=True,want_covs=False)[0]
-print("same neighbours:", bool((a.indices==b.indices).all()), bool((a.distances==b.distances).all()))

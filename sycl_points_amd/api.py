@@ -394,7 +394,7 @@ class GridKNN(KNNBase):
             pass
 
     def self_knn(self, k, want_knn=True, want_covs=False, want_normals=False):
-        """kNN of the grid's own cloud (tile kernel, csrc/grid.hip) with covariance / normal estimation optionally
+        """kNN of the grid's own cloud (the self-kNN kernels of csrc/grid.hip, chosen by k) with covariance / normal estimation optionally
         fused in — covariance::estimate_async(knn, points, k) (covariance.hpp:305-311) when the KNNBase is a GridKNN
         built on `points`. Returns (KNNResult | None, covs | None, normals | None), rows in original point order."""
         if k > 20:

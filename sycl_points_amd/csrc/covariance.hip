@@ -15,10 +15,9 @@ void sp_set_error(const char* msg);
 namespace sp {
 namespace {
 
-// covariance::kernel::estimate (covariance.hpp:16-47). Returns false when fewer than 4 neighbours: identity.
-__device__ __forceinline__ bool estimate_cov(const float4* __restrict__ pts, const int32_t* __restrict__ nbr, int k,
+// covariance::kernel::estimate (covariance.hpp:16-47): the sums in neighbour order; identity when fewer than 4 neighbours.
+__device__ __forceinline__ void estimate_cov(const float4* __restrict__ pts, const int32_t* __restrict__ nbr, int k,
                                              Mat3& C) {
-    // outer(p,p) is bitwise symmetric (p_i*p_j == p_j*p_i), so 6 running sums carry all 9 entries.
     float sx = 0.0f, sy = 0.0f, sz = 0.0f;
     float oxx = 0.0f, oxy = 0.0f, oxz = 0.0f, oyy = 0.0f, oyz = 0.0f, ozz = 0.0f;
     unsigned cnt = 0;
@@ -31,31 +30,9 @@ __device__ __forceinline__ bool estimate_cov(const float4* __restrict__ pts, con
         oyy += p.y * p.y; oyz += p.y * p.z; ozz += p.z * p.z;
         ++cnt;
     }
-    if (cnt < 4) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) C.m[i][j] = (i == j) ? 1.0f : 0.0f;
-        return false;
-    }
-    const float inv = 1.0f / (float)cnt;  // 1.0f / correspondences (size_t -> float), covariance.hpp:44
-    const float mx = sx * inv, my = sy * inv, mz = sz * inv;
-    // (sum_outer * inv) - outer(mean, mean), then ensure_symmetric (eigen_utils.hpp:208-219): (a + a) * 0.5
-    const float cxx = oxx * inv - mx * mx, cxy = oxy * inv - mx * my, cxz = oxz * inv - mx * mz;
-    const float cyy = oyy * inv - my * my, cyz = oyz * inv - my * mz, czz = ozz * inv - mz * mz;
-    const float sxy = (cxy + cxy) * 0.5f, sxz = (cxz + cxz) * 0.5f, syz = (cyz + cyz) * 0.5f;
-    C.m[0][0] = cxx; C.m[0][1] = sxy; C.m[0][2] = sxz;
-    C.m[1][0] = sxy; C.m[1][1] = cyy; C.m[1][2] = syz;
-    C.m[2][0] = sxz; C.m[2][1] = syz; C.m[2][2] = czz;
-    return true;
+    C = cov_from_sums(sx, sy, sz, oxx, oxy, oxz, oyy, oyz, ozz, cnt);
 }
 
-__device__ __forceinline__ void store_cov(float4* __restrict__ out, const Mat3& C) {
-    out[0] = make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f);  // column 0
-    out[1] = make_float4(C.m[0][1], C.m[1][1], C.m[2][1], 0.0f);
-    out[2] = make_float4(C.m[0][2], C.m[1][2], C.m[2][2], 0.0f);
-    out[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
 __global__ __launch_bounds__(kBlock) void cov_direct_kernel(const float4* __restrict__ pts, unsigned n,
                                                             const int32_t* __restrict__ knn, int k,
                                                             float4* __restrict__ covs) {
@@ -148,20 +125,10 @@ __device__ __forceinline__ bool estimate_cov_weighted(const float4* __restrict__
         tw += wj;
     }
     if (cnt < 4 || tw < FLT_EPSILON) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) C.m[i][j] = (i == j) ? 1.0f : 0.0f;
+        C = identity3();
         return false;
     }
-    const float inv = 1.0f / tw;
-    mx = sx * inv; my = sy * inv; mz = sz * inv;
-    const float cxx = oxx * inv - mx * mx, cxy = oxy * inv - mx * my, cxz = oxz * inv - mx * mz;
-    const float cyy = oyy * inv - my * my, cyz = oyz * inv - my * mz, czz = ozz * inv - mz * mz;
-    const float sxy = (cxy + cxy) * 0.5f, sxz = (cxz + cxz) * 0.5f, syz = (cyz + cyz) * 0.5f;
-    C.m[0][0] = cxx; C.m[0][1] = sxy; C.m[0][2] = sxz;
-    C.m[1][0] = sxy; C.m[1][1] = cyy; C.m[1][2] = syz;
-    C.m[2][0] = sxz; C.m[2][1] = syz; C.m[2][2] = czz;
+    C = cov_from_scaled_sums(sx, sy, sz, oxx, oxy, oxz, oyy, oyz, ozz, 1.0f / tw, mx, my, mz);
     return true;
 }
 

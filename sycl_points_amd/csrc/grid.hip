@@ -24,6 +24,7 @@
 
 #include "grid_device.h"
 #include "radix_sort.h"
+#include "sp_cov_normal.h"
 
 void sp_set_error(const char* msg);
 
@@ -358,70 +359,20 @@ __global__ __launch_bounds__(kBlock) void grid_search_kernel(const float4* __res
     float kth = bound2;
     int kth_idx = -1;
 
-    const bool finite_q = isfinite(qx) && isfinite(qy) && isfinite(qz);
-    if (finite_q && g.n > 0) {
-        const int cx = cell_coord(qx, g.ox, g.inv_h, g.nx), cy = cell_coord(qy, g.oy, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-        const int rmax = max(max(g.nx, g.ny), g.nz);
-        for (int r = 0; r <= rmax; ++r) {
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-            for (int z = z0; z <= z1; ++z) {
-                const float dz2 = gap2(qz, g.oz + z * g.h, g.oz + (z + 1) * g.h, g.eps);
-                if (dz2 > kth) continue;
-                for (int y = y0; y <= y1; ++y) {
-                    const float dyz2 = dz2 + gap2(qy, g.oy + y * g.h, g.oy + (y + 1) * g.h, g.eps);
-                    if (dyz2 > kth) continue;
-                    const bool shell_row = (r == 0) || (z == cz - r) || (z == cz + r) || (y == cy - r) || (y == cy + r);
-                    const unsigned row = ((unsigned)z * g.ny + y) * g.nx;
-                    // a shell row is scanned over its whole x-range; an interior row only at its two end cells
-                    const int nseg = shell_row ? 1 : 2;
-                    for (int sgi = 0; sgi < nseg; ++sgi) {
-                        int xa, xb;
-                        if (shell_row) { xa = x0; xb = x1; }
-                        else if (sgi == 0) { xa = cx - r; xb = cx - r; if (xa < 0) continue; }
-                        else { xa = cx + r; xb = cx + r; if (xb > g.nx - 1) continue; }
-                        const float d2box = dyz2 + gap2(qx, g.ox + xa * g.h, g.ox + (xb + 1) * g.h, g.eps);
-                        if (d2box > kth) continue;
-                        const unsigned s = start[row + xa], e = start[row + xb + 1];
-                        for (unsigned i = s; i < e; i += 4) {
-                            // up to four independent 16-byte loads in flight
-                            const float4 p0 = pts[i];
-                            const float4 p1 = pts[min(i + 1, e - 1)];
-                            const float4 p2 = pts[min(i + 2, e - 1)];
-                            const float4 p3 = pts[min(i + 3, e - 1)];
-                            const float d0 = dist2(qx, qy, qz, p0.x, p0.y, p0.z);
-                            const float d1 = dist2(qx, qy, qz, p1.x, p1.y, p1.z);
-                            const float d2 = dist2(qx, qy, qz, p2.x, p2.y, p2.z);
-                            const float d3 = dist2(qx, qy, qz, p3.x, p3.y, p3.z);
-                            const int i0 = __float_as_int(p0.w), i1 = __float_as_int(p1.w), i2 = __float_as_int(p2.w),
-                                      i3 = __float_as_int(p3.w);
-                            if (d0 < kth || (d0 == kth && i0 < kth_idx)) lex_insert<KCAP>(bd, bi, k, d0, i0, kth, kth_idx);
-                            if (i + 1 < e && (d1 < kth || (d1 == kth && i1 < kth_idx)))
-                                lex_insert<KCAP>(bd, bi, k, d1, i1, kth, kth_idx);
-                            if (i + 2 < e && (d2 < kth || (d2 == kth && i2 < kth_idx)))
-                                lex_insert<KCAP>(bd, bi, k, d2, i2, kth, kth_idx);
-                            if (i + 3 < e && (d3 < kth || (d3 == kth && i3 < kth_idx)))
-                                lex_insert<KCAP>(bd, bi, k, d3, i3, kth, kth_idx);
-                            if (bound2 < kth) { kth = bound2; kth_idx = -1; }  // (a list that is not full yet says FLT_MAX)
-                        }
-                    }
+    if (isfinite(qx) && isfinite(qy) && isfinite(qz) && g.n > 0)
+        grid_ring_walk(start, g, qx, qy, qz, 0, false, [&] { return kth; }, [&](unsigned s, unsigned e) {
+            for (unsigned i = s; i < e; i += 4) {
+                float4 p[4];
+                float d[4];
+                load4_dist2(pts, i, e, qx, qy, qz, p, d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int pi = __float_as_int(p[j].w);
+                    if (i + j < e && (d[j] < kth || (d[j] == kth && pi < kth_idx))) lex_insert<KCAP>(bd, bi, k, d[j], pi, kth, kth_idx);
                 }
+                if (bound2 < kth) { kth = bound2; kth_idx = -1; }  // (a list that is not full yet says FLT_MAX)
             }
-            // distance from the query to the faces of the scanned block; faces on the grid boundary do not count
-            float cov = FLT_MAX;
-            if (cx - r > 0) cov = fminf(cov, qx - (g.ox + (cx - r) * g.h));
-            if (cx + r < g.nx - 1) cov = fminf(cov, (g.ox + (cx + r + 1) * g.h) - qx);
-            if (cy - r > 0) cov = fminf(cov, qy - (g.oy + (cy - r) * g.h));
-            if (cy + r < g.ny - 1) cov = fminf(cov, (g.oy + (cy + r + 1) * g.h) - qy);
-            if (cz - r > 0) cov = fminf(cov, qz - (g.oz + (cz - r) * g.h));
-            if (cz + r < g.nz - 1) cov = fminf(cov, (g.oz + (cz + r + 1) * g.h) - qz);
-            if (cov == FLT_MAX) break;  // the block is the whole grid
-            cov = fmaxf(cov - g.eps, 0.0f);
-            if (kth < cov * cov) break;  // strict: an unseen point at exactly the k-th distance could win a tie
-        }
-    }
+        });
     const size_t o = (size_t)qi * (size_t)k;
 #pragma unroll
     for (int i = 0; i < KCAP; ++i)
@@ -431,12 +382,10 @@ __global__ __launch_bounds__(kBlock) void grid_search_kernel(const float4* __res
 // ---------------------------------------------------------------------------------------------------------------
 // Self-kNN on the grid (every point of the cloud queries its own cloud: the covariance / normal preprocessing of
 // the pipeline, pipeline/pointcloud_processing.hpp:144-156 and examples/example_registration.cpp:92-109).
-// Work unit = up to 64 consecutive points of one x-row of cells, one wave per unit. The unit's candidate set is the
-// 3 x 3 block of rows around it over the unit's x-span +- 1 cell: nine contiguous segments of the cell-ordered point
-// array. Candidates are streamed 64 at a time: one coalesced 16-byte load per lane, parked in LDS, then every lane
-// tests all of them with wave-uniform (broadcast) LDS reads — a brute force over a small local tile, with no
-// per-lane pointer chasing and no divergence except in the sorted insertion. A query whose k-th distance reaches
-// outside the scanned block (sparse regions) is appended to a to-do list and finished by the ring walk.
+// Work unit = up to 64 consecutive points of one x-row of cells, one wave per unit (the selection and the wave-cooperative
+// kernel below; the lane kernel for short lists takes the points as they lie). A kernel that looks at the 27 cells around a
+// query only appends the queries whose k-th distance reaches outside them (sparse regions) to a to-do list, which a wave per
+// query finishes.
 // The work units of every x-row (ceil(points in the row / 64); entry `rows` = 0, so the scan that follows needs no memset).
 // (A hand-written single-workgroup scan of these ~16 k values took 16-45 us in three forms against 7.6 us for the library's.)
 // The fullest cell (a statistic of the build: callers choose between the grid and the hierarchy by it, sp_grid_max_cell_points).
@@ -472,20 +421,30 @@ __global__ void row_units_kernel(const unsigned* __restrict__ start, unsigned nx
     const unsigned r = blockIdx.x * kBlock + threadIdx.x;
     if (r <= rows) units[r] = r < rows ? (start[(size_t)(r + 1) * nx] - start[(size_t)r * nx] + 63u) / 64u : 0u;
 }
+// x-row of a work unit: the last r with unit_off[r] <= unit (wave-uniform binary search).
+__device__ __forceinline__ unsigned unit_row(const unsigned* __restrict__ unit_off, unsigned rows, unsigned unit) {
+    unsigned lo = 0, hi = rows;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (unit_off[mid] <= unit) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 struct TileOut {
     int32_t* knn_idx;  // [n][k] original order (may be null)
     float* knn_d2;
     float4* covs;      // [n][4] (may be null)
     float4* normals;   // [n] (may be null)
-    unsigned* todo;    // queries (positions in grid order) the ring walk must finish
+    unsigned* todo;    // queries (positions in grid order; query numbers for an external search) that the selection kernel
+                       // could not prove inside its 27 cells: the wave-list kernel that follows finishes them, a wave each
     unsigned* todo_count;
     unsigned pos_lo, pos_hi;  // only the queries at grid positions [pos_lo, pos_hi) are searched (sp_grid_self_knn_range)
 };
 
 // covariance::kernel::estimate (feature/covariance.hpp:16-47) over the neighbour list in ascending order, reading
 // the neighbours from the cell-ordered copy (same values as points[idx], nearby in memory).
-__device__ __forceinline__ void cov_from_list(const float4* __restrict__ pts, const int* bp, int k, float c[6],
-                                              bool& identity) {
+__device__ __forceinline__ Mat3 cov_from_list(const float4* __restrict__ pts, const int* bp, int k) {
     float sx = 0.0f, sy = 0.0f, sz = 0.0f, oxx = 0.0f, oxy = 0.0f, oxz = 0.0f, oyy = 0.0f, oyz = 0.0f, ozz = 0.0f;
     unsigned cnt = 0;
     for (int j = 0; j < k; ++j) {
@@ -497,13 +456,7 @@ __device__ __forceinline__ void cov_from_list(const float4* __restrict__ pts, co
         oyy += p.y * p.y; oyz += p.y * p.z; ozz += p.z * p.z;
         ++cnt;
     }
-    identity = cnt < 4;
-    if (identity) return;
-    const float inv = 1.0f / (float)cnt;
-    const float mx = sx * inv, my = sy * inv, mz = sz * inv;
-    const float cxy = oxy * inv - mx * my, cxz = oxz * inv - mx * mz, cyz = oyz * inv - my * mz;
-    c[0] = oxx * inv - mx * mx; c[1] = (cxy + cxy) * 0.5f; c[2] = (cxz + cxz) * 0.5f;
-    c[3] = oyy * inv - my * my; c[4] = (cyz + cyz) * 0.5f; c[5] = ozz * inv - mz * mz;
+    return cov_from_sums(sx, sy, sz, oxx, oxy, oxz, oyy, oyz, ozz, cnt);
 }
 
 // What a lane that holds the sorted neighbour list of point q (distances, original indices, grid positions) writes:
@@ -519,137 +472,14 @@ __device__ __forceinline__ void self_knn_outputs(const float4* __restrict__ pts,
             if (i < k) { out.knn_idx[o + i] = bi[i]; out.knn_d2[o + i] = bd[i]; }
     }
     if (out.covs || out.normals) {
-        float c[6];
-        bool identity;
-        cov_from_list(pts, bp, k, c, identity);
-        Mat3 C;
-        if (identity) {
-            C.m[0][0] = C.m[1][1] = C.m[2][2] = 1.0f;
-            C.m[0][1] = C.m[0][2] = C.m[1][0] = C.m[1][2] = C.m[2][0] = C.m[2][1] = 0.0f;
-        } else {
-            C.m[0][0] = c[0]; C.m[0][1] = c[1]; C.m[0][2] = c[2];
-            C.m[1][0] = c[1]; C.m[1][1] = c[3]; C.m[1][2] = c[4];
-            C.m[2][0] = c[2]; C.m[2][1] = c[4]; C.m[2][2] = c[5];
-        }
-        if (out.covs) {
-            float4* o4 = out.covs + 4 * (size_t)orig;
-            o4[0] = make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f);
-            o4[1] = make_float4(C.m[0][1], C.m[1][1], C.m[2][1], 0.0f);
-            o4[2] = make_float4(C.m[0][2], C.m[1][2], C.m[2][2], 0.0f);
-            o4[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        if (out.normals) {  // covariance::kernel::extract_normal (covariance.hpp:49-65)
-            float ev[3];
-            Mat3 V;
-            symmetric_eigen3(C, ev, V);
-            const float nx_ = V.m[0][0], ny_ = V.m[1][0], nz_ = V.m[2][0];
-            const float dd = chain3(nx_, q.x, ny_, q.y, nz_, q.z);
-            out.normals[orig] = (dd <= 1.0f) ? make_float4(nx_, ny_, nz_, 0.0f) : make_float4(-nx_, -ny_, -nz_, 0.0f);
-        }
+        const Mat3 C = cov_from_list(pts, bp, k);
+        if (out.covs) store_cov(out.covs + 4 * (size_t)orig, C);
+        if (out.normals) out.normals[orig] = normal_of(C, q);
     }
-}
-
-template <int KCAP>
-__global__ __launch_bounds__(kWave) void grid_self_knn_tile_kernel(const float4* __restrict__ pts,
-                                                                   const unsigned* __restrict__ start,
-                                                                   const unsigned* __restrict__ unit_off, GridDesc g,
-                                                                   int k, TileOut out) {
-    __shared__ float4 tile[kWave];
-    const unsigned unit = blockIdx.x;
-    const unsigned rows = (unsigned)g.ny * g.nz;
-    // row of this unit: last r with unit_off[r] <= unit (wave-uniform binary search)
-    unsigned lo = 0, hi = rows;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (unit_off[mid] <= unit) lo = mid;
-        else hi = mid;
-    }
-    const unsigned row = lo;
-    const int ry = (int)(row % g.ny), rz = (int)(row / g.ny);
-    const unsigned row_s = start[(size_t)row * g.nx], row_e = start[(size_t)(row + 1) * g.nx];
-    const unsigned qs = row_s + (unit - unit_off[row]) * 64u;
-    const unsigned qe = min(qs + 64u, row_e);
-    if (qe <= out.pos_lo || qs >= out.pos_hi) return;  // wave-uniform: the unit lies outside the requested range
-    const unsigned lane = threadIdx.x;
-    const bool active = qs + lane < qe && qs + lane >= out.pos_lo && qs + lane < out.pos_hi;
-    const float4 q = pts[min(qs + lane, qe - 1)];
-    // x-span of the unit's queries (cells are ascending along the row)
-    const float4 qf = pts[qs], ql = pts[qe - 1];
-    const int cxa = cell_coord(qf.x, g.ox, g.inv_h, g.nx), cxb = cell_coord(ql.x, g.ox, g.inv_h, g.nx);
-    const int xa = max(cxa - 1, 0), xb = min(cxb + 1, g.nx - 1);
-    const int ya = max(ry - 1, 0), yb = min(ry + 1, g.ny - 1), za = max(rz - 1, 0), zb = min(rz + 1, g.nz - 1);
-
-    float bd[KCAP];
-    int bi[KCAP], bp[KCAP];
-#pragma unroll
-    for (int i = 0; i < KCAP; ++i) { bd[i] = FLT_MAX; bi[i] = -1; bp[i] = -1; }
-    float kth = FLT_MAX;
-    int kth_idx = -1;
-
-    // the queries' own row first, then the four rows sharing a face with it, then the corner rows: the k-th best is tight
-    // before the far rows arrive and they rarely take the insertion branch (which costs the whole wave when any lane takes it)
-    for (int ring = 0; ring < 3; ++ring)
-      for (int z = za; z <= zb; ++z)
-        for (int y = ya; y <= yb; ++y) {
-            if (abs(z - rz) + abs(y - ry) != ring) continue;
-            const unsigned rr = ((unsigned)z * g.ny + y) * g.nx;
-            const unsigned s = start[rr + xa], e = start[rr + xb + 1];
-            for (unsigned base = s; base < e; base += kWave) {
-                const unsigned cnt = min((unsigned)kWave, e - base);
-                __syncthreads();
-                if (lane < cnt) tile[lane] = pts[base + lane];
-                __syncthreads();
-                for (unsigned c = 0; c < cnt; ++c) {
-                    const float4 p = tile[c];
-                    const float d = dist2(q.x, q.y, q.z, p.x, p.y, p.z);
-                    const int pi = __float_as_int(p.w);
-                    if (d < kth || (d == kth && pi < kth_idx)) {
-                        // sorted insertion by (distance, original index); positions ride along
-                        float cd = d;
-                        int ci = pi, cp = (int)(base + c);
-                        bool shifting = false;
-#pragma unroll
-                        for (int i = 0; i < KCAP; ++i) {
-                            if (i < k) {
-                                const bool sw = shifting || cd < bd[i] || (cd == bd[i] && ci < bi[i]);
-                                const float td = bd[i];
-                                const int ti = bi[i], tp = bp[i];
-                                const float nd = sw ? cd : td;
-                                const int ni = sw ? ci : ti;
-                                bd[i] = nd; bi[i] = ni; bp[i] = sw ? cp : tp;
-                                cd = sw ? td : cd; ci = sw ? ti : ci; cp = sw ? tp : cp;
-                                shifting = sw;
-                                kth = nd; kth_idx = ni;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    if (!active) return;
-    // is the k-th neighbour provably inside the scanned block?
-    float cov = FLT_MAX;
-    if (xa > 0) cov = fminf(cov, q.x - (g.ox + xa * g.h));
-    if (xb < g.nx - 1) cov = fminf(cov, (g.ox + (xb + 1) * g.h) - q.x);
-    if (ya > 0) cov = fminf(cov, q.y - (g.oy + ya * g.h));
-    if (yb < g.ny - 1) cov = fminf(cov, (g.oy + (yb + 1) * g.h) - q.y);
-    if (za > 0) cov = fminf(cov, q.z - (g.oz + za * g.h));
-    if (zb < g.nz - 1) cov = fminf(cov, (g.oz + (zb + 1) * g.h) - q.z);
-    bool exact = true;
-    if (cov != FLT_MAX) {
-        cov = fmaxf(cov - g.eps, 0.0f);
-        exact = kth < cov * cov;
-    }
-    if (!exact) {
-        const unsigned slot = atomicAdd(out.todo_count, 1u);
-        out.todo[slot] = qs + lane;
-        return;
-    }
-    self_knn_outputs<KCAP>(pts, q, bd, bi, bp, k, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Lane per query for LONG lists (7 <= k <= 24): bound, collect, sort — no insertion anywhere.
+// Lane per query for LONG lists (7 <= k <= 20): bound, collect, sort — no insertion anywhere.
 // The wave-cooperative kernel below spends ~630 vector instructions on ONE query (a 64-lane sorting network and ballot-ranked
 // insertions); a lane-per-query kernel does 64 queries per instruction but could not keep a sorted 20-entry list cheaply
 // (every insertion is a 20-step select chain that the whole wave walks). Here nothing is kept sorted while scanning:
@@ -662,8 +492,8 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_tile_kernel(const float4*
 //   3. the <= 32 candidates within t go to a per-lane list in LDS, come back as exact 64-bit (distance, index) keys and each
 //      is RANKED among the lane's keys (a branch-free count): lexicographic order = brute force's tie rule; ranks < k are
 //      the list, written straight to their places;
-//   4. exactness as in the tile kernel: the k-th distance must be inside the block's coverage, otherwise (or when a segment
-//      is longer than its slots, or no threshold is found) the query goes to the to-do list of the ring-walk kernel.
+//   4. exactness: the k-th distance must be inside the coverage of the 27 cells, otherwise (or when the cells hold more
+//      candidates than there are slots, or no threshold is found) the query goes to the to-do list of the wave-list kernel.
 // Same lists, distances and covariances as the other kernels, bit for bit.
 constexpr int kSelCand = 192;  // candidates of one query (27 cells: 162 at the default density, sigma 13)
 constexpr int kSelList = 32;   // entries that may pass the threshold
@@ -830,8 +660,8 @@ __device__ __forceinline__ bool self_knn_select_core(const float4* __restrict__ 
         if ((unsigned)i < c) {
             l_spos[rank][lane] = pos[i];
             if (rank == (unsigned)k - 1u) kth = key_d2(key[i]);
-            // (written before exactness is known: a query that turns out unproven is rewritten by the to-do kernel, which
-            // runs after this one)
+            // (written before exactness is known: a query that turns out unproven is rewritten by the wave-list kernel,
+            // which runs after this one)
             if (write_lists && rank < (unsigned)k) {
                 list_idx[rank] = key_idx(key[i]);
                 list_d2[rank] = key_d2(key[i]);
@@ -865,13 +695,7 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_select_kernel(const float
     __shared__ int l_pos[kSelList][kWave];                      //  8 KB  (20 KB per wave: eight waves per CU)
     const unsigned unit = blockIdx.x;
     const unsigned rows = (unsigned)g.ny * g.nz;
-    unsigned lo = 0, hi = rows;
-    while (hi - lo > 1) {  // row of this unit: last r with unit_off[r] <= unit (wave-uniform)
-        const unsigned mid = (lo + hi) >> 1;
-        if (unit_off[mid] <= unit) lo = mid;
-        else hi = mid;
-    }
-    const unsigned row = lo;
+    const unsigned row = unit_row(unit_off, rows, unit);
     const int ry = (int)(row % g.ny), rz = (int)(row / g.ny);
     const unsigned row_s = start[(size_t)row * g.nx], row_e = start[(size_t)(row + 1) * g.nx];
     const unsigned qs = row_s + (unit - unit_off[row]) * 64u;
@@ -906,35 +730,16 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_select_kernel(const float
             oxx += p.x * p.x; oxy += p.x * p.y; oxz += p.x * p.z;
             oyy += p.y * p.y; oyz += p.y * p.z; ozz += p.z * p.z;
         }
-        const float inv = 1.0f / (float)k;
-        const float mx = sx * inv, my = sy * inv, mz = sz * inv;
-        const float cxy = oxy * inv - mx * my, cxz = oxz * inv - mx * mz, cyz = oyz * inv - my * mz;
-        Mat3 C;
-        C.m[0][0] = oxx * inv - mx * mx; C.m[0][1] = (cxy + cxy) * 0.5f; C.m[0][2] = (cxz + cxz) * 0.5f;
-        C.m[1][1] = oyy * inv - my * my; C.m[1][2] = (cyz + cyz) * 0.5f; C.m[2][2] = ozz * inv - mz * mz;
-        C.m[1][0] = C.m[0][1]; C.m[2][0] = C.m[0][2]; C.m[2][1] = C.m[1][2];
-        if (out.covs) {
-            float4* o4 = out.covs + 4 * (size_t)orig;
-            o4[0] = make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f);
-            o4[1] = make_float4(C.m[0][1], C.m[1][1], C.m[2][1], 0.0f);
-            o4[2] = make_float4(C.m[0][2], C.m[1][2], C.m[2][2], 0.0f);
-            o4[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        if (out.normals) {  // covariance::kernel::extract_normal (covariance.hpp:49-65)
-            float ev[3];
-            Mat3 V;
-            symmetric_eigen3(C, ev, V);
-            const float nx_ = V.m[0][0], ny_ = V.m[1][0], nz_ = V.m[2][0];
-            const float dd = chain3(nx_, q.x, ny_, q.y, nz_, q.z);
-            out.normals[orig] = (dd <= 1.0f) ? make_float4(nx_, ny_, nz_, 0.0f) : make_float4(-nx_, -ny_, -nz_, 0.0f);
-        }
+        const Mat3 C = cov_from_sums(sx, sy, sz, oxx, oxy, oxz, oyy, oyz, ozz, (unsigned)k);
+        if (out.covs) store_cov(out.covs + 4 * (size_t)orig, C);
+        if (out.normals) out.normals[orig] = normal_of(C, q);
     }
 }
 
-// The same selection for EXTERNAL queries (KNNBase::knn_search_async on a GridKNN, 8 <= k <= 24): a lane per query in the
-// caller's order, its cell from its (transformed) coordinates; what cannot be proven inside the 27 cells (and non-finite
-// queries) goes to the ring-walk kernel through a list. 1 M queries against 1 M points, k = 20: 7.4 ms with the ring walk
-// alone (a 20-step insertion per candidate in every lane).
+// The same selection for EXTERNAL queries (KNNBase::knn_search_async on a GridKNN, 10 < k <= 20): a lane per query in the
+// caller's order (or in cell order, `order`), its cell from its (transformed) coordinates; what cannot be proven inside the 27
+// cells goes to the wave-list kernel through a list; a non-finite query gets the empty list here. 1 M queries against 1 M points,
+// k = 20: 7.4 ms with the ring walk alone (a 20-step insertion per candidate in every lane).
 __global__ __launch_bounds__(kWave) void grid_search_select_kernel(const float4* __restrict__ pts,
                                                                    const unsigned* __restrict__ start, GridDesc g,
                                                                    const float4* __restrict__ queries, unsigned nq, int k,
@@ -969,7 +774,7 @@ __global__ __launch_bounds__(kWave) void grid_search_select_kernel(const float4*
 // Lane per point, for short lists (k <= 10): the ring walk of grid_search_kernel over the grid's own cell-ordered points
 // (neighbouring lanes walk neighbouring cells), positions carried along for the fused covariance / normal. Exact by
 // construction (the walk ends when the k-th neighbour is proven), so there is no to-do list. On 1M points: k = 10 in
-// 0.6 ms against 1.1 ms for the wave-cooperative kernel, k = 6 in 0.35 ms against 0.9 ms for the tile kernel.
+// 0.6 ms against 1.1 ms for the wave-cooperative kernel. (An LDS-tile kernel served k <= 6 before it: DESIGN.md, appendix A.)
 template <int KCAP>
 __global__ __launch_bounds__(kBlock) void grid_self_knn_lane_kernel(const float4* __restrict__ pts,
                                                                     const unsigned* __restrict__ start, GridDesc g, int k,
@@ -984,73 +789,20 @@ __global__ __launch_bounds__(kBlock) void grid_self_knn_lane_kernel(const float4
     for (int i = 0; i < KCAP; ++i) { bd[i] = FLT_MAX; bi[i] = -1; bp[i] = -1; }
     float kth = FLT_MAX;
     int kth_idx = -1;
-    auto consider = [&](float d, int pi, int pos) {
-        if (!(d < kth || (d == kth && pi < kth_idx))) return;
-        float cd = d;
-        int ci = pi, cp = pos;
-        bool shifting = false;
+    if (isfinite(qx) && isfinite(qy) && isfinite(qz))
+        grid_ring_walk(start, g, qx, qy, qz, 0, false, [&] { return kth; }, [&](unsigned s, unsigned e) {
+            for (unsigned i = s; i < e; i += 4) {
+                float4 p[4];
+                float d[4];
+                load4_dist2(pts, i, e, qx, qy, qz, p, d);
 #pragma unroll
-        for (int i = 0; i < KCAP; ++i) {
-            if (i < k) {
-                const bool sw = shifting || cd < bd[i] || (cd == bd[i] && ci < bi[i]);
-                const float td = bd[i];
-                const int ti = bi[i], tp = bp[i];
-                bd[i] = sw ? cd : td; bi[i] = sw ? ci : ti; bp[i] = sw ? cp : tp;
-                cd = sw ? td : cd; ci = sw ? ti : ci; cp = sw ? tp : cp;
-                shifting = sw;
-                kth = bd[i]; kth_idx = bi[i];
-            }
-        }
-    };
-    if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-        const int cx = cell_coord(qx, g.ox, g.inv_h, g.nx), cy = cell_coord(qy, g.oy, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-        const int rmax = max(max(g.nx, g.ny), g.nz);
-        for (int r = 0; r <= rmax; ++r) {
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-            for (int z = z0; z <= z1; ++z) {
-                const float dz2 = gap2(qz, g.oz + z * g.h, g.oz + (z + 1) * g.h, g.eps);
-                if (dz2 > kth) continue;
-                for (int y = y0; y <= y1; ++y) {
-                    const float dyz2 = dz2 + gap2(qy, g.oy + y * g.h, g.oy + (y + 1) * g.h, g.eps);
-                    if (dyz2 > kth) continue;
-                    const bool shell_row = (r == 0) || (z == cz - r) || (z == cz + r) || (y == cy - r) || (y == cy + r);
-                    const unsigned row = ((unsigned)z * g.ny + y) * g.nx;
-                    const int nseg = shell_row ? 1 : 2;  // a shell row over its whole x-range, an interior row at its two end cells
-                    for (int sgi = 0; sgi < nseg; ++sgi) {
-                        int xa, xb;
-                        if (shell_row) { xa = x0; xb = x1; }
-                        else if (sgi == 0) { xa = cx - r; xb = cx - r; if (xa < 0) continue; }
-                        else { xa = cx + r; xb = cx + r; if (xb > g.nx - 1) continue; }
-                        if (dyz2 + gap2(qx, g.ox + xa * g.h, g.ox + (xb + 1) * g.h, g.eps) > kth) continue;
-                        const unsigned s = start[row + xa], e = start[row + xb + 1];
-                        for (unsigned i = s; i < e; i += 4) {  // up to four independent 16-byte loads in flight
-                            const float4 p0 = pts[i], p1 = pts[min(i + 1, e - 1)], p2 = pts[min(i + 2, e - 1)],
-                                         p3 = pts[min(i + 3, e - 1)];
-                            const float d0 = dist2(qx, qy, qz, p0.x, p0.y, p0.z), d1 = dist2(qx, qy, qz, p1.x, p1.y, p1.z),
-                                        d2 = dist2(qx, qy, qz, p2.x, p2.y, p2.z), d3 = dist2(qx, qy, qz, p3.x, p3.y, p3.z);
-                            consider(d0, __float_as_int(p0.w), (int)i);
-                            if (i + 1 < e) consider(d1, __float_as_int(p1.w), (int)i + 1);
-                            if (i + 2 < e) consider(d2, __float_as_int(p2.w), (int)i + 2);
-                            if (i + 3 < e) consider(d3, __float_as_int(p3.w), (int)i + 3);
-                        }
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    const int pi = __float_as_int(p[j].w);
+                    if (i + j < e && (d[j] < kth || (d[j] == kth && pi < kth_idx)))
+                        lex_insert<KCAP>(bd, bi, k, d[j], pi, kth, kth_idx, bp, (int)(i + j));
                 }
             }
-            float cov = FLT_MAX;  // distance to the faces of the scanned block; faces on the grid boundary do not count
-            if (cx - r > 0) cov = fminf(cov, qx - (g.ox + (cx - r) * g.h));
-            if (cx + r < g.nx - 1) cov = fminf(cov, (g.ox + (cx + r + 1) * g.h) - qx);
-            if (cy - r > 0) cov = fminf(cov, qy - (g.oy + (cy - r) * g.h));
-            if (cy + r < g.ny - 1) cov = fminf(cov, (g.oy + (cy + r + 1) * g.h) - qy);
-            if (cz - r > 0) cov = fminf(cov, qz - (g.oz + (cz - r) * g.h));
-            if (cz + r < g.nz - 1) cov = fminf(cov, (g.oz + (cz + r + 1) * g.h) - qz);
-            if (cov == FLT_MAX) break;
-            cov = fmaxf(cov - g.eps, 0.0f);
-            if (kth < cov * cov) break;  // strict: an unseen point at exactly the k-th distance could win a tie
-        }
-    }
+        });
     self_knn_outputs<KCAP>(pts, q, bd, bi, bp, k, out);
 }
 
@@ -1186,52 +938,19 @@ __device__ __forceinline__ void self_knn_wave_queries(const float4* __restrict__
                 insert_candidates(c, best, kth, k, kmask, lane);
             }
         }
-        // Exactness: is the k-th neighbour inside the scanned block? If not (sparse neighbourhoods), keep adding rings
-        // of cells — still wave-cooperatively, one shell segment at a time — until it is.
-        const int cy = ry, cz = rz;
-        const int rmax = max(max(g.nx, g.ny), g.nz);
-        for (int R = 1; R <= rmax; ++R) {
-            float cov = FLT_MAX;
-            if (cx - R > 0) cov = fminf(cov, qx - (g.ox + (cx - R) * g.h));
-            if (cx + R < g.nx - 1) cov = fminf(cov, (g.ox + (cx + R + 1) * g.h) - qx);
-            if (cy - R > 0) cov = fminf(cov, qy - (g.oy + (cy - R) * g.h));
-            if (cy + R < g.ny - 1) cov = fminf(cov, (g.oy + (cy + R + 1) * g.h) - qy);
-            if (cz - R > 0) cov = fminf(cov, qz - (g.oz + (cz - R) * g.h));
-            if (cz + R < g.nz - 1) cov = fminf(cov, (g.oz + (cz + R + 1) * g.h) - qz);
-            if (cov == FLT_MAX) break;  // the block is the whole grid
-            cov = fmaxf(cov - g.eps, 0.0f);
-            if (key_d2(kth) < cov * cov) break;  // proven exact (strict: an unseen point at exactly kth could win a tie)
-            const int Rn = R + 1;        // add the shell at Chebyshev distance Rn
-            const int z0 = max(cz - Rn, 0), z1 = min(cz + Rn, g.nz - 1), y0 = max(cy - Rn, 0), y1 = min(cy + Rn, g.ny - 1);
-            const int x0 = max(cx - Rn, 0), x1 = min(cx + Rn, g.nx - 1);
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y) {
-                    // only the part of the shell the ball of the current k-th distance reaches (the k-th best moves as
-                    // candidates are inserted; the test uses its current value)
-                    const float dyz2 = gap2(qz, g.oz + z * g.h, g.oz + (z + 1) * g.h, g.eps) +
-                                       gap2(qy, g.oy + y * g.h, g.oy + (y + 1) * g.h, g.eps);
-                    if (dyz2 > key_d2(kth)) continue;
-                    const bool shell_row = (z == cz - Rn) || (z == cz + Rn) || (y == cy - Rn) || (y == cy + Rn);
-                    const unsigned rr = ((unsigned)z * g.ny + y) * g.nx;
-                    for (int sgi = 0; sgi < (shell_row ? 1 : 2); ++sgi) {
-                        int sxa, sxb;
-                        if (shell_row) { sxa = x0; sxb = x1; }
-                        else if (sgi == 0) { sxa = sxb = cx - Rn; if (sxa < 0) continue; }
-                        else { sxa = sxb = cx + Rn; if (sxb > g.nx - 1) continue; }
-                        if (dyz2 + gap2(qx, g.ox + sxa * g.h, g.ox + (sxb + 1) * g.h, g.eps) > key_d2(kth)) continue;
-                        const unsigned s0 = start[rr + sxa], e0 = start[rr + sxb + 1];
-                        for (unsigned base = s0; base < e0; base += 64) {
-                            const unsigned pos = base + lane;
-                            const bool valid = pos < e0;
-                            const float4 p = pts[valid ? pos : e0 - 1];
-                            Cand c;
-                            c.key = valid ? cand_key(dist2(qx, qy, qz, p.x, p.y, p.z), __float_as_int(p.w)) : kNoCand;
-                            c.pos = (int)pos;
-                            insert_candidates(c, best, kth, k, kmask, lane);
-                        }
-                    }
-                }
-        }
+        // Exactness: is the k-th neighbour inside the scanned block (the shells 0 and 1 of the ring walk)? If not (sparse
+        // neighbourhoods), the walk goes on from shell 2 — still wave-cooperatively, one shell segment at a time.
+        grid_ring_walk(start, g, qx, qy, qz, 2, true, [&] { return key_d2(kth); }, [&](unsigned s0, unsigned e0) {
+            for (unsigned base = s0; base < e0; base += 64) {
+                const unsigned pos = base + lane;
+                const bool valid = pos < e0;
+                const float4 p = pts[valid ? pos : e0 - 1];
+                Cand c;
+                c.key = valid ? cand_key(dist2(qx, qy, qz, p.x, p.y, p.z), __float_as_int(p.w)) : kNoCand;
+                c.pos = (int)pos;
+                insert_candidates(c, best, kth, k, kmask, lane);
+            }
+        });
         const bool have = (int)lane < k && key_d2(best.key) != FLT_MAX;
         if (out.knn_idx && (int)lane < k) {
             const size_t o = (size_t)qorig * (size_t)k + lane;
@@ -1261,19 +980,7 @@ __device__ __forceinline__ void self_knn_wave_queries(const float4* __restrict__
             const float sx = bcast_f(acc9, 0), sy = bcast_f(acc9, 1), sz = bcast_f(acc9, 2), oxx = bcast_f(acc9, 3),
                         oxy = bcast_f(acc9, 4), oxz = bcast_f(acc9, 5), oyy = bcast_f(acc9, 6), oyz = bcast_f(acc9, 7),
                         ozz = bcast_f(acc9, 8);
-            Mat3 C;
-            if (cnt < 4) {
-                C.m[0][0] = C.m[1][1] = C.m[2][2] = 1.0f;
-                C.m[0][1] = C.m[0][2] = C.m[1][0] = C.m[1][2] = C.m[2][0] = C.m[2][1] = 0.0f;
-            } else {
-                const float inv = 1.0f / (float)cnt;
-                const float mx = sx * inv, my = sy * inv, mz = sz * inv;
-                const float cxy = oxy * inv - mx * my, cxz = oxz * inv - mx * mz, cyz = oyz * inv - my * mz;
-                C.m[0][0] = oxx * inv - mx * mx; C.m[1][1] = oyy * inv - my * my; C.m[2][2] = ozz * inv - mz * mz;
-                C.m[0][1] = C.m[1][0] = (cxy + cxy) * 0.5f;
-                C.m[0][2] = C.m[2][0] = (cxz + cxz) * 0.5f;
-                C.m[1][2] = C.m[2][1] = (cyz + cyz) * 0.5f;
-            }
+            const Mat3 C = cov_from_sums(sx, sy, sz, oxx, oxy, oxz, oyy, oyz, ozz, cnt);
             if (out.covs && lane < 4) {
                 const float4 col = lane == 0 ? make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f)
                                  : lane == 1 ? make_float4(C.m[0][1], C.m[1][1], C.m[2][1], 0.0f)
@@ -1282,13 +989,8 @@ __device__ __forceinline__ void self_knn_wave_queries(const float4* __restrict__
                 out.covs[4 * (size_t)qorig + lane] = col;
             }
             if (out.normals) {
-                float ev[3];
-                Mat3 V;
-                symmetric_eigen3(C, ev, V);
-                const float nx_ = V.m[0][0], ny_ = V.m[1][0], nz_ = V.m[2][0];
-                const float dd = chain3(nx_, qx, ny_, qy, nz_, qz);
-                if (lane == 0)
-                    out.normals[qorig] = (dd <= 1.0f) ? make_float4(nx_, ny_, nz_, 0.0f) : make_float4(-nx_, -ny_, -nz_, 0.0f);
+                const float4 nrm = normal_of(C, make_float4(qx, qy, qz, 0.0f));
+                if (lane == 0) out.normals[qorig] = nrm;
             }
         }
     }
@@ -1301,13 +1003,7 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_wave_kernel(const float4*
     __shared__ float sm_terms[9][33];  // covariance terms of the k <= 20 neighbours (row stride 33: conflict-free columns)
     const unsigned unit = blockIdx.x;
     const unsigned rows = (unsigned)g.ny * g.nz;
-    unsigned lo = 0, hi = rows;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (unit_off[mid] <= unit) lo = mid;
-        else hi = mid;
-    }
-    const unsigned row = lo;
+    const unsigned row = unit_row(unit_off, rows, unit);
     const int ry = (int)(row % g.ny), rz = (int)(row / g.ny);
     const unsigned row_s = start[(size_t)row * g.nx], row_e = start[(size_t)(row + 1) * g.nx];
     const unsigned qs = row_s + (unit - unit_off[row]) * 64u;
@@ -1315,8 +1011,8 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_wave_kernel(const float4*
     if (qs + nq <= out.pos_lo || qs >= out.pos_hi) return;  // the unit lies outside the requested range
     self_knn_wave_queries(pts, start, g, k, out, sm_terms, qs, nq, ry, rz, pts[min(qs + threadIdx.x, row_e - 1u)]);
 }
-// The same search for a LIST of queries (the to-do list of the lane-per-query kernels): a fixed grid of waves takes them one
-// at a time. The ring walk that used to finish them kept 27 k of 1 M queries busy for 1.5 ms (a lane each, a 20-step
+// The same search for a LIST of queries (the to-do list of the selection kernel): a fixed grid of waves takes them one
+// at a time. A lane-per-query ring walk that used to finish them kept 27 k of 1 M queries busy for 1.5 ms (a lane each, a 20-step
 // insertion per candidate); a wave each, they take a few tens of microseconds.
 __global__ __launch_bounds__(kWave) void grid_self_knn_wave_list_kernel(const float4* __restrict__ pts,
                                                                         const unsigned* __restrict__ start, GridDesc g, int k,
@@ -1349,125 +1045,6 @@ __global__ __launch_bounds__(kWave) void grid_search_wave_list_kernel(const floa
     }
 }
 
-// Ring walk for the queries the tile kernel could not prove exact (their positions are listed in `todo`).
-template <int KCAP>
-__global__ __launch_bounds__(kBlock) void grid_self_knn_todo_kernel(const float4* __restrict__ pts,
-                                                                    const unsigned* __restrict__ start, GridDesc g,
-                                                                    int k, TileOut out) {
-    const unsigned t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= *out.todo_count) return;
-    const float4 q = pts[out.todo[t]];
-    float bd[KCAP];
-    int bi[KCAP], bp[KCAP];
-#pragma unroll
-    for (int i = 0; i < KCAP; ++i) { bd[i] = FLT_MAX; bi[i] = -1; bp[i] = -1; }
-    float kth = FLT_MAX;
-    int kth_idx = -1;
-    const int cx = cell_coord(q.x, g.ox, g.inv_h, g.nx), cy = cell_coord(q.y, g.oy, g.inv_h, g.ny),
-              cz = cell_coord(q.z, g.oz, g.inv_h, g.nz);
-    const int rmax = max(max(g.nx, g.ny), g.nz);
-    for (int r = 0; r <= rmax; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-        for (int z = z0; z <= z1; ++z) {
-            const float dz2 = gap2(q.z, g.oz + z * g.h, g.oz + (z + 1) * g.h, g.eps);
-            if (dz2 > kth) continue;
-            for (int y = y0; y <= y1; ++y) {
-                const float dyz2 = dz2 + gap2(q.y, g.oy + y * g.h, g.oy + (y + 1) * g.h, g.eps);
-                if (dyz2 > kth) continue;
-                const bool shell_row = (r == 0) || (z == cz - r) || (z == cz + r) || (y == cy - r) || (y == cy + r);
-                const unsigned row = ((unsigned)z * g.ny + y) * g.nx;
-                const int nseg = shell_row ? 1 : 2;
-                for (int sgi = 0; sgi < nseg; ++sgi) {
-                    int xa, xb;
-                    if (shell_row) { xa = x0; xb = x1; }
-                    else if (sgi == 0) { xa = cx - r; xb = cx - r; if (xa < 0) continue; }
-                    else { xa = cx + r; xb = cx + r; if (xb > g.nx - 1) continue; }
-                    if (dyz2 + gap2(q.x, g.ox + xa * g.h, g.ox + (xb + 1) * g.h, g.eps) > kth) continue;
-                    const unsigned s = start[row + xa], e = start[row + xb + 1];
-                    for (unsigned i = s; i < e; ++i) {
-                        const float4 p = pts[i];
-                        const float d = dist2(q.x, q.y, q.z, p.x, p.y, p.z);
-                        const int pi = __float_as_int(p.w);
-                        if (d < kth || (d == kth && pi < kth_idx)) {
-                            float cd = d;
-                            int ci = pi, cp = (int)i;
-                            bool shifting = false;
-#pragma unroll
-                            for (int j = 0; j < KCAP; ++j) {
-                                if (j < k) {
-                                    const bool sw = shifting || cd < bd[j] || (cd == bd[j] && ci < bi[j]);
-                                    const float td = bd[j];
-                                    const int ti = bi[j], tp = bp[j];
-                                    const float nd = sw ? cd : td;
-                                    const int ni = sw ? ci : ti;
-                                    bd[j] = nd; bi[j] = ni; bp[j] = sw ? cp : tp;
-                                    cd = sw ? td : cd; ci = sw ? ti : ci; cp = sw ? tp : cp;
-                                    shifting = sw;
-                                    kth = nd; kth_idx = ni;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        float cov = FLT_MAX;
-        if (cx - r > 0) cov = fminf(cov, q.x - (g.ox + (cx - r) * g.h));
-        if (cx + r < g.nx - 1) cov = fminf(cov, (g.ox + (cx + r + 1) * g.h) - q.x);
-        if (cy - r > 0) cov = fminf(cov, q.y - (g.oy + (cy - r) * g.h));
-        if (cy + r < g.ny - 1) cov = fminf(cov, (g.oy + (cy + r + 1) * g.h) - q.y);
-        if (cz - r > 0) cov = fminf(cov, q.z - (g.oz + (cz - r) * g.h));
-        if (cz + r < g.nz - 1) cov = fminf(cov, (g.oz + (cz + r + 1) * g.h) - q.z);
-        if (cov == FLT_MAX) break;
-        cov = fmaxf(cov - g.eps, 0.0f);
-        if (kth < cov * cov) break;
-    }
-    const unsigned orig = __float_as_uint(q.w);
-    if (out.knn_idx) {
-        const size_t o = (size_t)orig * (size_t)k;
-#pragma unroll
-        for (int i = 0; i < KCAP; ++i)
-            if (i < k) { out.knn_idx[o + i] = bi[i]; out.knn_d2[o + i] = bd[i]; }
-    }
-    if (out.covs || out.normals) {
-        float c[6];
-        bool identity;
-        cov_from_list(pts, bp, k, c, identity);
-        Mat3 C;
-        if (identity) {
-            C.m[0][0] = C.m[1][1] = C.m[2][2] = 1.0f;
-            C.m[0][1] = C.m[0][2] = C.m[1][0] = C.m[1][2] = C.m[2][0] = C.m[2][1] = 0.0f;
-        } else {
-            C.m[0][0] = c[0]; C.m[0][1] = c[1]; C.m[0][2] = c[2];
-            C.m[1][0] = c[1]; C.m[1][1] = c[3]; C.m[1][2] = c[4];
-            C.m[2][0] = c[2]; C.m[2][1] = c[4]; C.m[2][2] = c[5];
-        }
-        if (out.covs) {
-            float4* o4 = out.covs + 4 * (size_t)orig;
-            o4[0] = make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f);
-            o4[1] = make_float4(C.m[0][1], C.m[1][1], C.m[2][1], 0.0f);
-            o4[2] = make_float4(C.m[0][2], C.m[1][2], C.m[2][2], 0.0f);
-            o4[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        if (out.normals) {
-            float ev[3];
-            Mat3 V;
-            symmetric_eigen3(C, ev, V);
-            const float nx_ = V.m[0][0], ny_ = V.m[1][0], nz_ = V.m[2][0];
-            const float dd = chain3(nx_, q.x, ny_, q.y, nz_, q.z);
-            out.normals[orig] = (dd <= 1.0f) ? make_float4(nx_, ny_, nz_, 0.0f) : make_float4(-nx_, -ny_, -nz_, 0.0f);
-        }
-    }
-}
-
-__global__ void fill_todo_kernel(unsigned* todo, unsigned* count, unsigned n) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) todo[i] = i;
-    if (i == 0) *count = n;
-}
-
 // The work units of the self-kNN tiling (ceil(points in row / 64) per x-row, prefix-summed), made on first use: allocates, and
 // reads their number back (one synchronisation per grid that is ever asked for a self-kNN).
 int ensure_units(const sp_grid* gr, hipStream_t st) {
@@ -1490,30 +1067,30 @@ int ensure_units(const sp_grid* gr, hipStream_t st) {
     return SP_OK;
 }
 
+// Which kernel searches the cloud's own points (k <= 20: sp_grid_self_knn_range turns larger lists away). self_knn_mode 0: the
+// lane kernel up to k = 7, above it the selection inside the 27 cells and a wave for each query it could not prove; 3: the
+// selection from k = 7; 2, and 3 below k = 7: the wave-cooperative kernel.
 template <int KCAP>
 int launch_self(const sp_grid* gr, int k, const TileOut& out, hipStream_t st) {
     if (const int rc = ensure_units(gr, st); rc != SP_OK) return rc;
     const GridDesc g = grid_desc(gr);
     if (zero_async(out.todo_count, 4, st) != SP_OK) return SP_ERR_HIP;
-    if (KCAP <= 10 && gr->self_knn_mode == 0 && k <= 7) {  // short lists: lane per point, exact without a to-do pass
-        grid_self_knn_lane_kernel<KCAP><<<div_up(out.pos_hi - out.pos_lo, kBlock), kBlock, 0, st>>>(gr->d_pts, gr->d_start, g, k, out);
-        return launch_status();
-    }
-    if (gr->n_units) {
-        // lane-per-query tile kernel for short lists (k = 3 on 1M points: 0.70 ms against 1.94 ms; it loses from k = 7 up: scratch/selfknn_modes.py)
-        if (KCAP <= 10 && (gr->self_knn_mode == 1 || (gr->self_knn_mode == 0 && k <= 6)))
-            grid_self_knn_tile_kernel<KCAP><<<gr->n_units, kWave, 0, st>>>(gr->d_pts, gr->d_start, gr->d_unit_off, g, k, out);
-        else if (k >= 7 && k <= 24 && (gr->self_knn_mode == 0 || gr->self_knn_mode == 3)) {
-            // (1 M points: k = 8 / 10 / 12 / 16 / 20 in 0.48 / 0.49 / 0.49 / 0.52 / 0.60 ms against 0.54 / 0.68 for the lane kernel
-            // and 0.84 ... 0.95 for the wave-cooperative one; with covariances 0.47 ... 0.57 against 1.0 ... 1.15)
-            grid_self_knn_select_kernel<<<gr->n_units, kWave, 0, st>>>(gr->d_pts, gr->d_start, gr->d_unit_off, g, k, out);
-            // its unproven queries (a few per cent: the k-th neighbour not provably inside the 27 cells), a wave each
-            grid_self_knn_wave_list_kernel<<<kNumCU * 32, kWave, 0, st>>>(gr->d_pts, gr->d_start, g, k, out);
+    if constexpr (KCAP <= 10) {
+        if (gr->self_knn_mode == 0 && k <= 7) {  // short lists: lane per point, exact without a to-do pass
+            grid_self_knn_lane_kernel<KCAP><<<div_up(out.pos_hi - out.pos_lo, kBlock), kBlock, 0, st>>>(gr->d_pts, gr->d_start, g, k, out);
             return launch_status();
-        } else
-            grid_self_knn_wave_kernel<<<gr->n_units, kWave, 0, st>>>(gr->d_pts, gr->d_start, gr->d_unit_off, g, k, out);
+        }
     }
-    grid_self_knn_todo_kernel<KCAP><<<div_up(gr->n, kBlock), kBlock, 0, st>>>(gr->d_pts, gr->d_start, g, k, out);
+    if (gr->n_units == 0) return launch_status();
+    if (gr->self_knn_mode == 0 || (gr->self_knn_mode == 3 && k >= 7)) {
+        // (1 M points: k = 8 / 10 / 12 / 16 / 20 in 0.48 / 0.49 / 0.49 / 0.52 / 0.60 ms against 0.54 / 0.68 for the lane kernel
+        // and 0.84 ... 0.95 for the wave-cooperative one; with covariances 0.47 ... 0.57 against 1.0 ... 1.15)
+        grid_self_knn_select_kernel<<<gr->n_units, kWave, 0, st>>>(gr->d_pts, gr->d_start, gr->d_unit_off, g, k, out);
+        // its unproven queries (a few per cent: the k-th neighbour not provably inside the 27 cells), a wave each
+        grid_self_knn_wave_list_kernel<<<kNumCU * 32, kWave, 0, st>>>(gr->d_pts, gr->d_start, g, k, out);
+    } else {
+        grid_self_knn_wave_kernel<<<gr->n_units, kWave, 0, st>>>(gr->d_pts, gr->d_start, gr->d_unit_off, g, k, out);
+    }
     return launch_status();
 }
 
@@ -1601,7 +1178,7 @@ int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* 
                                                                       tv, T_dev ? T : nullptr, idx, d2, order);
         return launch_status();
     }
-    if (k > 10 && k <= 24 && gr->n != 0 && (gr->self_knn_mode == 0 || gr->self_knn_mode == 3)) {
+    if (k > 10 && gr->n != 0 && (gr->self_knn_mode == 0 || gr->self_knn_mode == 3)) {  // (k <= 20: sp_grid_search)
         // lane-per-query selection inside the 27 cells; the queries it cannot prove (a few per cent at the densities the grid
         // is built for) are listed and finished a wave each. (k <= 10 stays on the ring walk: its row pruning scans fewer
         // candidates than all 27 cells, which decides for queries in random order — 0.8 against 2.2 ms at k = 10.) The list lives in the library's buffer pool for the
@@ -2058,7 +1635,7 @@ extern "C" int sp_grid_self_knn_range(const sp_grid* grid, size_t k, size_t pos_
         sp_set_error("[GridKNN::self_knn] null grid or k == 0");
         return SP_ERR_INVALID_ARGUMENT;
     }
-    if (k > 20) {
+    if (k > 20) {  // the kernels are made for lists of up to 20: launch_self and the wave kernel's covariance rely on it
         sp_set_error("[GridKNN::knn_search_async] `k` is too large (max 20).");
         return SP_ERR_RUNTIME;
     }
@@ -2106,7 +1683,10 @@ extern "C" int sp_grid_radius_search(const sp_grid* grid, const float* queries, 
 // Per-handle tuning switch (sp_internal.h): exported for tests/ and scratch/ only.
 extern "C" int sp_internal_grid_option(sp_grid* grid, int option, int value) {
     if (!grid) return SP_ERR_INVALID_ARGUMENT;
-    if (option == SP_INTERNAL_SELF_KNN_MODE) grid->self_knn_mode = value;
+    if (option == SP_INTERNAL_SELF_KNN_MODE) {
+        if (value != 0 && value != 2 && value != 3) return SP_ERR_INVALID_ARGUMENT;  // (1 was the LDS-tile kernel: DESIGN.md, appendix A)
+        grid->self_knn_mode = value;
+    }
     else if (option == SP_INTERNAL_GRID_SORT_QUERIES) grid->sort_queries = value;
     else return SP_ERR_INVALID_ARGUMENT;
     return SP_OK;

@@ -1,4 +1,5 @@
-// Device-side pieces of the uniform-grid search shared by grid.hip (GridKNN) and gicp_fused.hip.
+// Device-side pieces of the uniform-grid search shared by grid.hip (GridKNN), bvh.hip and, through registration_device.h, the
+// alignment kernels of registration.hip, registration_opt.hip and opt_stepper.hip.
 #pragma once
 #include "sp_common.h"
 #include "sp_math.h"
@@ -23,8 +24,9 @@ struct sp_grid {
     hipEvent_t built_ev = nullptr;
     mutable uint32_t max_cell = 0;    // points in the fullest cell, measured on first request (sp_grid_max_cell_points)
     mutable bool max_cell_known = false;
-    // tuning switch (sp_internal.h): self-kNN kernel — 0 chosen by k (lane per point for k <= 10, wave-cooperative above),
-    // 1 LDS-tile kernel (k <= 10), 2 wave-cooperative kernel. Results are identical.
+    // tuning switch (sp_internal.h): self-kNN kernel — 0 chosen by k (lane per point for k <= 7, lane-per-query selection
+    // plus a wave per unproven query above), 2 wave-cooperative kernel, 3 the selection from k = 7. External searches use the
+    // selection for k > 10 under 0 and 3, the ring walk under 2. Results are identical.
     int self_knn_mode = 0;
     int sort_queries = 1;  // external queries (400 k or more) are searched in cell order (sp_internal.h; 0: as given)
     mutable sp::StreamSet streams;  // every stream the arrays have been handed to (sp_grid_destroy tags the pool entries)
@@ -60,20 +62,22 @@ __device__ __forceinline__ int cell_coord(float v, float o, float inv_h, int dim
     return (int)fminf(fmaxf(t, 0.0f), (float)(dim - 1));
 }
 
-// (distance, index) lexicographic sorted insertion into the first k slots.
+// (distance, index) lexicographic sorted insertion into the first k slots. With `bp` the grid positions of the entries ride
+// along (the fused covariance reads the neighbours by position).
 template <int KCAP>
 __device__ __forceinline__ void lex_insert(float (&bd)[KCAP], int (&bi)[KCAP], int k, float d, int idx, float& kth,
-                                           int& kth_idx) {
+                                           int& kth_idx, int* bp = nullptr, int pos = 0) {
     if (KCAP == 1) {
         const bool better = d < bd[0] || (d == bd[0] && idx < bi[0]);
         bi[0] = better ? idx : bi[0];
         bd[0] = better ? d : bd[0];
+        if (bp) bp[0] = better ? pos : bp[0];
         kth = bd[0];
         kth_idx = bi[0];
         return;
     }
     float cd = d;
-    int ci = idx;
+    int ci = idx, cp = pos;
     bool shifting = false;
 #pragma unroll
     for (int i = 0; i < KCAP; ++i) {
@@ -87,6 +91,11 @@ __device__ __forceinline__ void lex_insert(float (&bd)[KCAP], int (&bi)[KCAP], i
             bi[i] = ni;
             cd = sw ? td : cd;
             ci = sw ? ti : ci;
+            if (bp) {  // (known when the call is inlined: no test remains)
+                const int tp = bp[i];
+                bp[i] = sw ? cp : tp;
+                cp = sw ? tp : cp;
+            }
             shifting = sw;
             kth = nd;
             kth_idx = ni;
@@ -100,8 +109,76 @@ __device__ __forceinline__ float gap2(float v, float lo, float hi, float eps) {
     return g * g;
 }
 
-// Exact nearest neighbour (k = 1) of (qx,qy,qz) on the grid, ties to the lowest original index — the same walk as
-// grid_search_kernel<1>, additionally reporting the winner's position in the cell-ordered point array and its
+// Candidates [i, i + 4) of the segment that ends at e (i < e): four independent 16-byte loads in flight, and their squared
+// distances to the query. Slots past the end repeat the segment's last point: the caller tests i + j < e.
+__device__ __forceinline__ void load4_dist2(const float4* __restrict__ pts, unsigned i, unsigned e, float qx, float qy, float qz,
+                                            float4 (&p)[4], float (&d)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = pts[j ? min(i + j, e - 1) : i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] = dist2(qx, qy, qz, p[j].x, p[j].y, p[j].z);
+}
+
+// The ring walk: every search that is not confined to a fixed block of cells goes through it. Shells of cells at Chebyshev
+// distance r = r_start, r_start + 1, ... around the cell of the (finite) query; of shell r the rows of its two z- and two y-faces
+// (for r = 0: the one row) are scanned over their whole x-range, every other row only at its two end cells. For each x-segment that survives the pruning
+// `scan(s, e)` gets its range [s, e) of the cell-ordered point array. `bound2()` is the caller's current bound — the k-th best
+// squared distance, or a tighter limit of the caller's — and is asked again at every test, because it shrinks while candidates
+// arrive. `proven_before`: the caller has scanned the whole block of the shells r < r_start itself, so the walk first asks whether
+// that block already proves the answer.
+// Why it is exact: a z-layer, a row or a segment is skipped only when its box lies farther than the bound — with the box widened
+// by eps (gap2), which bounds the rounding of the cell assignment, so that a point the build put in a neighbouring cell is never
+// pruned with it; a skipped box cannot hold a winner now or later, since the bound only shrinks. The walk ends when the block
+// scanned so far holds the ball of the bound: the distance from the query to the block's nearest face, less eps. Faces on the
+// grid's boundary do not count (nothing lies beyond them); when no face counts the block is the whole grid. The comparison is
+// strict: an unseen point at exactly the bound could still win a tie by its index.
+template <class Bound, class Scan>
+__device__ __forceinline__ void grid_ring_walk(const unsigned* __restrict__ start, const GridDesc& g, float qx, float qy,
+                                               float qz, int r_start, bool proven_before, Bound&& bound2, Scan&& scan) {
+    const int cx = cell_coord(qx, g.ox, g.inv_h, g.nx), cy = cell_coord(qy, g.oy, g.inv_h, g.ny),
+              cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
+    const int rmax = max(max(g.nx, g.ny), g.nz);
+    auto covered = [&](int r) {  // do the shells up to r hold the ball of the bound?
+        float cov = FLT_MAX;
+        if (cx - r > 0) cov = fminf(cov, qx - (g.ox + (cx - r) * g.h));
+        if (cx + r < g.nx - 1) cov = fminf(cov, (g.ox + (cx + r + 1) * g.h) - qx);
+        if (cy - r > 0) cov = fminf(cov, qy - (g.oy + (cy - r) * g.h));
+        if (cy + r < g.ny - 1) cov = fminf(cov, (g.oy + (cy + r + 1) * g.h) - qy);
+        if (cz - r > 0) cov = fminf(cov, qz - (g.oz + (cz - r) * g.h));
+        if (cz + r < g.nz - 1) cov = fminf(cov, (g.oz + (cz + r + 1) * g.h) - qz);
+        if (cov == FLT_MAX) return true;
+        cov = fmaxf(cov - g.eps, 0.0f);
+        return bound2() < cov * cov;
+    };
+    if (proven_before && covered(r_start - 1)) return;
+    for (int r = r_start; r <= rmax; ++r) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
+        for (int z = z0; z <= z1; ++z) {
+            const float dz2 = gap2(qz, g.oz + z * g.h, g.oz + (z + 1) * g.h, g.eps);
+            if (dz2 > bound2()) continue;
+            for (int y = y0; y <= y1; ++y) {
+                const float dyz2 = dz2 + gap2(qy, g.oy + y * g.h, g.oy + (y + 1) * g.h, g.eps);
+                if (dyz2 > bound2()) continue;
+                const bool shell_row = (z == cz - r) || (z == cz + r) || (y == cy - r) || (y == cy + r);
+                const unsigned row = ((unsigned)z * g.ny + y) * g.nx;
+                const int nseg = shell_row ? 1 : 2;
+                for (int sgi = 0; sgi < nseg; ++sgi) {
+                    int xa, xb;
+                    if (shell_row) { xa = x0; xb = x1; }
+                    else if (sgi == 0) { xa = cx - r; xb = cx - r; if (xa < 0) continue; }
+                    else { xa = cx + r; xb = cx + r; if (xb > g.nx - 1) continue; }
+                    if (dyz2 + gap2(qx, g.ox + xa * g.h, g.ox + (xb + 1) * g.h, g.eps) > bound2()) continue;
+                    scan(start[row + xa], start[row + xb + 1]);
+                }
+            }
+        }
+        if (covered(r)) break;
+    }
+}
+
+// Exact nearest neighbour (k = 1) of (qx,qy,qz) on the grid, ties to the lowest original index — additionally reporting the winner's position in the cell-ordered point array and its
 // coordinates (so a caller can read per-point data stored in grid order without another gather of the point).
 struct Nearest {
     float d2;
@@ -110,6 +187,8 @@ struct Nearest {
     float x, y, z;  // its coordinates
 };
 
+// This is the k = 1 form of grid_ring_walk above, written out: the per-iteration GICP kernels that inline it sit exactly at their
+// 128-VGPR budget (csrc/Makefile), and through the shared template one of them allocates its registers differently.
 // `seed` (optional) is an upper bound found earlier — every cell of the rings r < r_start must already have been
 // searched (or be provably unable to beat the seed).
 __device__ __forceinline__ Nearest grid_nn1(const float4* __restrict__ pts, const unsigned* __restrict__ start,

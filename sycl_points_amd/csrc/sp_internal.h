@@ -25,7 +25,8 @@ enum {
     /* sp_gicp_source: NN walk inside the fused kernel: -1 (default) 2x2x2 fast path iff the source is cell-sorted,
      * 0 ring walk, 1 fast path. */
     SP_INTERNAL_FUSED_FAST_NN = 2,
-    /* sp_grid: self-kNN kernel: 0 (default) chosen by k, 1 LDS-tile kernel (k <= 10), 2 wave-cooperative kernel. */
+    /* sp_grid: self-kNN kernel: 0 (default) chosen by k (lane per point up to k = 7, lane-per-query selection above), 2 wave-cooperative
+     * kernel, 3 the selection from k = 7 (wave-cooperative below). Any other value: SP_ERR_INVALID_ARGUMENT. */
     SP_INTERNAL_SELF_KNN_MODE = 3,
     /* sp_gicp_source: sp_gicp_align_fused, when the convergence criteria can be met, runs the TAIL of the alignment as one
      * launch that loops on the device (1, default; taken when every workgroup of the grid is resident) or every iteration

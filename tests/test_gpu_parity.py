@@ -1583,7 +1583,7 @@ def test_grid_order_and_presorted_source(sp, orc, gicp20k):
         assert (nn == oi.ravel()).mean() > 0.999  # the pose differs from the oracle's by rounding only
 
 
-# ------------------------------------------------------------------ tile self-kNN (+ fused covariance / normals)
+# ------------------------------------------------------------------ grid self-kNN (+ fused covariance / normals)
 @pytest.mark.parametrize("k", [4, 10, 20])
 @pytest.mark.parametrize("shape", ["uniform", "clustered"])
 def test_grid_self_knn_and_fused_covariance(sp, orc, k, shape):
@@ -1620,3 +1620,63 @@ def test_grid_self_knn_1m_matches_kdtree_covariances(sp, orc):
     assert diff.float().mean().item() < 1e-3 and bool(((d[:, 1:] == d[:, :-1]).any(1)).all())
     same = ~diff
     assert torch.equal(covs[same], sp.covariance.estimate(ref, P)[same])
+
+
+@pytest.mark.parametrize("k, mode", [(4, 0), (8, 0), (20, 0), (10, 2)])
+@pytest.mark.parametrize("shape", ["uniform", "clustered"])
+def test_grid_fused_normals_are_the_librarys_normals(sp, orc, k, mode, shape):
+    # csrc/sp_cov_normal.h: a normal made inside a self-kNN kernel carries the bits sp_normals_from_cov stores for the
+    # covariance the same kernel returned — the lane kernel (k = 4), the selection and its wave-per-query list (8, 20) and the
+    # wave-cooperative kernel (self_knn_mode = 2)
+    n = 12000
+    pts = cloud(orc, 11, n, 4.0)
+    if shape == "clustered":  # as in test_grid_self_knn_and_fused_covariance: dense blobs + empty space + far outliers
+        rs = np.random.RandomState(1)
+        pts[: n // 2, :3] = (rs.normal(0, 0.05, (n // 2, 3)) + rs.randint(-3, 4, (n // 2, 1)) * 1.0).astype(np.float32)
+        pts[-20:, :3] *= 50.0
+    P = dev(pts)
+    finite = np.isfinite(pts[:, :3]).all(1)
+    for ppc in (1.0, 8.0):
+        grid = sp.GridKNN.build(P, points_per_cell=ppc)
+        grid._set_option("self_knn_mode", mode)
+        _, covs, nrm = grid.self_knn(k, want_knn=False, want_covs=True, want_normals=True)
+        ref = sp.covariance.extract_normals(P, covs)
+        assert np.array_equal(nrm.cpu().numpy()[finite], ref.cpu().numpy()[finite])
+
+
+@pytest.fixture(scope="module")
+def sparse_cloud(orc):
+    # 3000 points in a radius of 40 at 6 points per cell (most queries walk several rings of cells), 500 of them twice (ties)
+    pts = orc.rng(31).uniform_points(3000, 40.0)
+    pts = np.concatenate([pts, pts[:500]])
+    refs = {}
+
+    def reference(k):
+        if k not in refs:
+            oi, od = orc.knn_bruteforce(pts, pts, k)
+            refs[k] = (oi, od, np.asarray(orc.cov_estimate(pts, oi), np.float32).reshape(-1, 16))
+        return refs[k]
+
+    return pts, reference
+
+
+# the lane kernel (mode 0: k = 1 and its last k, 7) and the shell expansion of the wave-cooperative kernel under a short and a
+# longer list (mode 2), where the first ring rarely suffices
+@pytest.mark.parametrize("k, mode", [(1, 0), (7, 0), (3, 2), (10, 2)])
+def test_grid_self_knn_in_sparse_space(sp, orc, sparse_cloud, k, mode):
+    pts, reference = sparse_cloud
+    oi, od, ocov = reference(k)
+    grid = sp.GridKNN.build(dev(pts), points_per_cell=6.0)
+    grid._set_option("self_knn_mode", mode)
+    res, covs, _ = grid.self_knn(k, want_knn=True, want_covs=True)
+    assert np.array_equal(res.indices.cpu().numpy(), oi) and np.array_equal(res.distances.cpu().numpy(), od)
+    assert np.array_equal(covs.cpu().numpy().reshape(-1, 16), ocov)
+
+
+def test_grid_self_knn_mode_switch_accepts_only_its_values(sp, orc):
+    grid = sp.GridKNN.build(dev(cloud(orc, 3, 500, 2.0)))
+    for mode in (0, 2, 3):
+        grid._set_option("self_knn_mode", mode)
+    for mode in (1, 4, -1):  # (1 was the LDS-tile kernel)
+        with pytest.raises(sp.SpError):
+            grid._set_option("self_knn_mode", mode)
