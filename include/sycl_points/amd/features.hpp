@@ -3,8 +3,8 @@
 //   algorithms/filter/voxel_downsampling.hpp     : filter::VoxelGrid
 //   algorithms/filter/polar_downsampling.hpp     : filter::PolarGrid
 //   algorithms/common/coordinate_system.hpp      : CoordinateSystem, coordinate_system_from_string
-//   algorithms/filter/preprocess_filter.hpp      : filter::PreprocessFilter (box_filter, random_sampling, farthest_point_sampling,
-//                                                  angle_incidence_filter)
+//   algorithms/filter/preprocess_filter.hpp      : filter::PreprocessFilter (box_filter, random_sampling, weighted_random_sampling,
+//                                                  mixed_random_sampling, farthest_point_sampling, angle_incidence_filter)
 //   algorithms/filter/intensity_correction.hpp   : intensity_correction::correct_intensity
 //   algorithms/filter/intensity_gaussian.hpp     : intensity_gaussian::smooth_intensity
 //   algorithms/filter/intensity_local_mean_norm.hpp : intensity_local_mean_norm::normalize
@@ -16,8 +16,12 @@
 #include <utility>
 #include <vector>
 #include <cctype>
+#include <cmath>
+#include <limits>
 #include <numeric>
 #include <random>
+#include <stdexcept>
+#include <unordered_map>
 
 #include "knn.hpp"
 
@@ -569,11 +573,11 @@ private:
 class PreprocessFilter {
 public:
     using Ptr = std::shared_ptr<PreprocessFilter>;
-    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), by_flags_(queue), mt_(1234), fps_mt_(1234) {
+    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), by_flags_(queue), mt_(1234), fps_mt_(1234), weighted_mt_(1234), mixed_mt_(1234) {
         flags_ = std::make_shared<shared_vector<uint8_t>>(queue);
     }
     /// preprocess_filter.hpp:46-51: every sampling operator has a generator of its own; the call seeds them all
-    void set_random_seed(uint_fast32_t seed) { mt_.seed(seed); fps_mt_.seed(seed); }
+    void set_random_seed(uint_fast32_t seed) { mt_.seed(seed); fps_mt_.seed(seed); weighted_mt_.seed(seed); mixed_mt_.seed(seed); }
 
     /// preprocess_operator/box_filter_operator.hpp:24-54 (K10 on the device, compaction on the device)
     void box_filter(const PointCloudShared& source, PointCloudShared& output, float min_distance = 1.0f,
@@ -641,16 +645,95 @@ public:
         if (rc == SP_ERR_RUNTIME) rc = run();
         throw_on_error(rc);
         apply_flags(source, output);
-        if (output.has_timestamps()) {
-            const auto& off = *output.timestamp_offsets;
-            output.end_time_ms = off.empty() ? output.start_time_ms
-                                             : output.start_time_ms + static_cast<double>(*std::max_element(off.begin(), off.end()));
-        } else {
-            output.start_time_ms = 0.0;
-            output.end_time_ms = 0.0;
-        }
+        sampled_time_range(output);
     }
     void farthest_point_sampling(PointCloudShared& data, size_t sampling_num) { farthest_point_sampling(data, data, sampling_num); }
+    /// preprocess_operator/weighted_sampling_operator.hpp:29-95 — Efraimidis-Spirakis without replacement. The reference's host loop
+    /// over every point (a log, a draw and a heap step each) is the device's here (sp_weight_check, sp_weighted_sample_flags); the
+    /// host only draws, one per positive weight, from the operator's own generator (weighted_mt_), and reads two words back. The
+    /// checks, their order and their texts are the reference's. The kept rows move through the flags path with the count known.
+    void weighted_random_sampling(const PointCloudShared& source, PointCloudShared& output, const shared_vector<float>& weights,
+                                  size_t sampling_num) {
+        const size_t N = source.size();
+        if (N <= sampling_num) {
+            if (&source != &output) output = PointCloudShared(source);
+            return;
+        }
+        if (weights.size() != N)
+            throw std::invalid_argument("[PreprocessFilter::weighted_random_sampling] weights size must match points");
+        hipStream_t st = queue_.stream();
+        const float* const w = weights.device_data();
+        const WeightReport rep = check_weights(w, N, st);
+        if (rep.first_invalid != kNoInvalidWeight)
+            throw std::invalid_argument("[PreprocessFilter::weighted_random_sampling] weights must be finite and non-negative");
+        if (rep.positive == 0)
+            throw std::invalid_argument("[PreprocessFilter::weighted_random_sampling] at least one weight must be positive");
+        if (sampling_num > rep.positive)
+            throw std::invalid_argument("[PreprocessFilter::weighted_random_sampling] sampling_num exceeds positive-weight points");
+        weighted_flags(w, N, sampling_num, rep.positive, weighted_mt_, st);
+        apply_flags(source, output, sampling_num);
+        sampled_time_range(output);
+    }
+    void weighted_random_sampling(PointCloudShared& data, const shared_vector<float>& weights, size_t sampling_num) {
+        weighted_random_sampling(data, data, weights, sampling_num);
+    }
+    /// preprocess_operator/mixed_random_sampling_operator.hpp:28-105 — floor(sampling_num * weighted_ratio) points by their weights
+    /// (as above, on mixed_mt_; fewer positive weights than that: all of them), the rest uniformly among the others: the
+    /// reference's partial Fisher-Yates over the list of unselected indices draws from the same generator afterwards. The host
+    /// runs it on POSITIONS in that list (a sparse map of the swapped slots, not N entries); the device finds the point each
+    /// position stands for (sp_uniform_fill_flags). weighted_ratio == 0 draws what random_sampling draws with the same seed.
+    void mixed_random_sampling(const PointCloudShared& source, PointCloudShared& output, const shared_vector<float>& weights,
+                               size_t sampling_num, float weighted_ratio) {
+        const size_t N = source.size();
+        if (N <= sampling_num) {
+            if (&source != &output) output = PointCloudShared(source);
+            return;
+        }
+        if (weights.size() != N) throw std::invalid_argument("[PreprocessFilter::mixed_random_sampling] weights size must match points");
+        if (!std::isfinite(weighted_ratio) || weighted_ratio < 0.0f || weighted_ratio > 1.0f)
+            throw std::invalid_argument("[PreprocessFilter::mixed_random_sampling] weighted_ratio must be within [0.0, 1.0]");
+        // the share drawn by weight: floor of the product in double (:44-45)
+        const size_t by_weight = static_cast<size_t>(std::floor(double(sampling_num) * double(weighted_ratio)));
+        hipStream_t st = queue_.stream();
+        const float* const w = weights.device_data();
+        const WeightReport rep = check_weights(w, N, st);
+        if (rep.first_invalid != kNoInvalidWeight) {
+            // the reference meets the weight inside its loop (:57-62): the positive weights before it have taken their draws
+            if (by_weight != 0 && rep.first_invalid != 0) draw_weighted(check_weights(w, rep.first_invalid, st).positive, mixed_mt_);
+            throw std::invalid_argument("[PreprocessFilter::mixed_random_sampling] weights must be finite and non-negative");
+        }
+        // (by_weight == 0 consumes no draw, :63; fewer positive weights than the target: all are kept, all have drawn)
+        const size_t selected = std::min(by_weight, rep.positive);
+        if (selected != 0) weighted_flags(w, N, by_weight, rep.positive, mixed_mt_, st);
+        else hip_check(hipMemsetAsync(flags_->device_data_for_write(N), 0, N, st), "memset");
+        const size_t R = N - selected, U = std::min(sampling_num - selected, R);
+        if (U != 0) {
+            std::unordered_map<size_t, size_t> moved;  // the slots of `remaining` that a swap has touched
+            moved.reserve(2 * U);
+            auto at = [&](size_t k) { const auto it = moved.find(k); return it == moved.end() ? k : it->second; };
+            std::vector<uint32_t> positions(U);
+            for (size_t i = 0; i < U; ++i) {
+                std::uniform_int_distribution<size_t> dist(i, R - 1);
+                const size_t j = dist(mixed_mt_);
+                const size_t vi = at(i), vj = at(j);
+                moved[i] = vj;
+                moved[j] = vi;
+                positions[i] = static_cast<uint32_t>(vj);
+            }
+            std::sort(positions.begin(), positions.end());
+            const size_t ws_bytes = sp_uniform_fill_workspace_bytes(N);
+            detail::DeviceScratch ws(ws_bytes, st), pos(U * sizeof(uint32_t), st);
+            ws.stream_ordered = pos.stream_ordered = true;  // (used on st only)
+            hip_check(hipMemcpyAsync(pos.p, positions.data(), U * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D");  // (pageable: staged before the call returns)
+            throw_on_error(sp_uniform_fill_flags(flags_->device_data_for_write(N), N, static_cast<const uint32_t*>(pos.p), U, ws.p,
+                                                 ws_bytes, st));
+        }
+        apply_flags(source, output, selected + U);
+        sampled_time_range(output);
+    }
+    void mixed_random_sampling(PointCloudShared& data, const shared_vector<float>& weights, size_t sampling_num, float weighted_ratio) {
+        mixed_random_sampling(data, data, weights, sampling_num, weighted_ratio);
+    }
     /// preprocess_filter.hpp:147-160, 276-279 + preprocess_operator/angle_incidence_filter_operator.hpp:23-110: the flags on the
     /// device (sp_angle_incidence_flags: the cloud's normals, else extract_normal of its covariances), then every attribute through
     /// the flags path on the same stream: nothing waits in between, one count is read back. An empty source returns before any
@@ -667,6 +750,46 @@ public:
     }
 
 private:
+    /// filter_by_flags' time stamps (preprocess_filter.hpp:211-224): end = start + the largest kept offset; none: start = end = 0
+    static void sampled_time_range(PointCloudShared& output) {
+        if (output.has_timestamps()) {
+            const auto& off = *output.timestamp_offsets;
+            output.end_time_ms = off.empty() ? output.start_time_ms
+                                             : output.start_time_ms + static_cast<double>(*std::max_element(off.begin(), off.end()));
+        } else {
+            output.start_time_ms = 0.0;
+            output.end_time_ms = 0.0;
+        }
+    }
+    static constexpr size_t kNoInvalidWeight = 0xffffffffu;
+    struct WeightReport { size_t positive, first_invalid; };
+    /// sp_weight_check over the first n weights and its two words read back (it synchronises the stream)
+    WeightReport check_weights(const float* w, size_t n, hipStream_t st) {
+        detail::DeviceScratch report(8, st);
+        throw_on_error(sp_weight_check(w, n, static_cast<uint32_t*>(report.p), st));
+        uint32_t local[2];
+        void* const pinned = detail::pinned_block_4k();  // (a copy into pageable memory is staged inside the runtime)
+        uint32_t* const h = pinned ? static_cast<uint32_t*>(pinned) : local;
+        hip_check(hipMemcpyAsync(h, report.p, 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        return WeightReport{h[0], h[1]};
+    }
+    /// `count` draws of the weighted part, in the reference's order (one per positive weight, index ascending)
+    void draw_weighted(size_t count, std::mt19937& mt) {
+        std::uniform_real_distribution<float> dist(std::numeric_limits<float>::min(), 1.0f);
+        draws_.resize(count);
+        for (size_t j = 0; j < count; ++j) draws_[j] = dist(mt);
+    }
+    /// flags_ = the m points of the largest keys (all `positive` ones when there are fewer), with `positive` fresh draws of mt
+    void weighted_flags(const float* w, size_t N, size_t m, size_t positive, std::mt19937& mt, hipStream_t st) {
+        draw_weighted(positive, mt);
+        const size_t ws_bytes = sp_weighted_sample_workspace_bytes(N);
+        detail::DeviceScratch ws(ws_bytes, st), u(positive * sizeof(float), st);
+        ws.stream_ordered = u.stream_ordered = true;  // (used on st only)
+        hip_check(hipMemcpyAsync(u.p, draws_.data(), positive * sizeof(float), hipMemcpyHostToDevice, st), "H2D");  // (pageable: staged before the call returns)
+        throw_on_error(sp_weighted_sample_flags(w, static_cast<const float*>(u.p), N, m, flags_->device_data_for_write(N), nullptr,
+                                                ws.p, ws_bytes, st));
+    }
     /// output = the rows `picked` of every attribute of source (sp_gather_rows_multi)
     void gather_rows(const PointCloudShared& source, PointCloudShared& output, const std::vector<uint32_t>& picked) {
         const size_t M = picked.size();
@@ -778,6 +901,8 @@ private:
     shared_vector_ptr<uint8_t> flags_;
     std::mt19937 mt_;
     std::mt19937 fps_mt_;  // farthest point sampling's own generator (preprocess_filter.hpp:46-51)
+    std::mt19937 weighted_mt_, mixed_mt_;  // and the weighted and the mixed sampler's
+    std::vector<float> draws_;             // the weighted draws of the current call (its capacity is kept)
 };
 
 }  // namespace filter

@@ -837,7 +837,12 @@ inline RegistrationAligner make_registration_aligner(const Registration::Ptr& re
 }  // namespace pipeline
 
 /// registration_pipeline_params.hpp:11-43
-struct RegistrationRandomSamplingParams { bool enable = true; size_t num = 1000; };
+struct RegistrationRandomSamplingParams {
+    bool enable = true;
+    size_t num = 1000;
+    bool use_intensities = false;  // sample by the source's intensities (mixed_random_sampling) when it has them
+    float weighted_ratio = 0.8f;   // the share of `num` drawn by weight on that path
+};
 struct RegistrationRobustScheduleParams {
     bool auto_scale = false;
     float init_scale = 10.0f, min_scale = 0.5f, rotation_init_scale = 10.0f, rotation_min_scale = 0.5f;
@@ -1044,8 +1049,11 @@ private:
             input_ = std::make_shared<PointCloudShared>(source.queue);
         }
         const auto& rs = params_.random_sampling;
-        if (rs.enable && source.size() > rs.num) filter_->random_sampling(source, *input_, rs.num);
-        else *input_ = source;  // shallow (registration_pipeline.hpp:138)
+        if (rs.enable && source.size() > rs.num) {
+            if (rs.use_intensities && source.has_intensity())
+                filter_->mixed_random_sampling(source, *input_, *source.intensities, rs.num, rs.weighted_ratio);
+            else filter_->random_sampling(source, *input_, rs.num);
+        } else *input_ = source;  // shallow (registration_pipeline.hpp:138)
     }
     RegistrationPipelineParams params_;
     Registration::Ptr registration_;

@@ -457,6 +457,37 @@ int sp_farthest_point_sampling(const float* points, size_t n, size_t sampling_nu
                                void* stream);
 int sp_fps_status(const void* workspace, void* stream);
 
+/* Weighted and mixed random sampling (filter/preprocess_operator/weighted_sampling_operator.hpp:29-95,
+ * mixed_random_sampling_operator.hpp:28-105). The reference loops over every point on the host (a std::log, a std::mt19937 draw
+ * and a std::priority_queue step per positive weight, then a pass over all flags); here the host only draws, in the order the
+ * reference draws, and the per-point work, the selection and the flags are the device's. All pointers but none are device
+ * memory; every call only enqueues on `stream` (graph-capturable). n == 0 or >= 2^32, a null pointer, a short workspace, m == 0
+ * or > n, n_positions == 0 or > n -> SP_ERR_INVALID_ARGUMENT before any HIP call.
+ *   sp_weight_check  the checks of :43-61 (mixed: :57-62) in one pass: report_dev[0] = the number of weights > 0, report_dev[1]
+ *                    = the lowest index of a weight that is not finite or < 0, 0xffffffff when there is none. The caller reads
+ *                    the two words back: the only read-back a sampling call needs.
+ *   sp_weighted_sample_flags  the loop of :67-90 (mixed: :51-80), Efraimidis-Spirakis. u_by_rank[j] is the draw of the j-th
+ *                    point with a positive weight, in index order (std::uniform_real_distribution<float>(FLT_MIN, 1) on the
+ *                    operator's generator; at least as many entries as there are positive weights). key = log(u) / w with the
+ *                    correctly rounded binary32 logarithm and the IEEE division; the m largest keys are kept:
+ *                    flags_out[i] = 1 keep / 0 remove. Equal keys at the threshold are kept as the reference's min-heap of
+ *                    (key, index) keeps them, which replaces its top only when top.key < key: with K the m-th largest key and
+ *                    c = m - #{key > K}, of the points with key == K that are among the first m points (index order) with
+ *                    key >= K, the c with the highest indices. Fewer than m positive weights: all of them are kept (:66-69 of
+ *                    the mixed operator). *selected_count_dev_opt = the number kept, min(m, positive weights). A pure function
+ *                    of (weights, u_by_rank, m). workspace: sp_weighted_sample_workspace_bytes(n), 4 bytes per point.
+ *   sp_uniform_fill_flags  the uniform part of the mixed operator (:82-99) once the host has run its partial Fisher-Yates on
+ *                    positions: for every p in positions_sorted (ascending, distinct) the p-th point, counted from 0 in index
+ *                    order, whose flag is not 1 gets flag 1; a p past the last such point selects nothing. workspace:
+ *                    sp_uniform_fill_workspace_bytes(n). */
+int sp_weight_check(const float* weights, size_t n, uint32_t* report_dev, void* stream);
+size_t sp_weighted_sample_workspace_bytes(size_t n);
+int sp_weighted_sample_flags(const float* weights, const float* u_by_rank, size_t n, size_t m, uint8_t* flags_out,
+                             uint32_t* selected_count_dev_opt, void* workspace, size_t workspace_bytes, void* stream);
+size_t sp_uniform_fill_workspace_bytes(size_t n);
+int sp_uniform_fill_flags(uint8_t* flags, size_t n, const uint32_t* positions_sorted, size_t n_positions, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------- registration */
 
 /* RegType (algorithms/registration/factor.hpp:18-32) and RobustLossType (algorithms/robust/robust.hpp:13-19). */

@@ -169,6 +169,11 @@ SIGNATURES = {
     "sp_fps_workspace_bytes": (_sz, [_sz, _sz]),
     "sp_farthest_point_sampling": (_i, [_vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_fps_status": (_i, [_vp, _vp]),
+    "sp_weight_check": (_i, [_vp, _sz, _vp, _vp]),
+    "sp_weighted_sample_workspace_bytes": (_sz, [_sz]),
+    "sp_weighted_sample_flags": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "sp_uniform_fill_workspace_bytes": (_sz, [_sz]),
+    "sp_uniform_fill_flags": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "sp_box_filter_compact_multi": (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_gicp_workspace_bytes": (_sz, [_sz]),
     "sp_gicp_linearize": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FactorParams), _vp, _vp, _sz, _vp]),

@@ -955,6 +955,47 @@ def farthest_point_sampling(points, sampling_num, first_index, form=None):
     return FpsResult(order, flags, d)
 
 
+def weight_check(weights):
+    """sp_weight_check: (the number of weights > 0, the lowest index of a weight that is not finite or < 0, or None) — the
+    checks of WeightedSamplingOperator::apply (weighted_sampling_operator.hpp:43-61) in one pass. Reads two words back."""
+    w = _dev_f32(weights)
+    report = torch.empty(2, dtype=torch.int32, device=w.device)
+    check(_lib.lib().sp_weight_check(_ptr(w), w.numel(), _ptr(report), _stream()))
+    positive, bad = (int(v) & 0xFFFFFFFF for v in report.cpu().tolist())
+    return positive, (None if bad == 0xFFFFFFFF else bad)
+
+
+def weighted_sample_flags(weights, u_by_rank, m):
+    """sp_weighted_sample_flags: the flags (uint8 [N], 1 keep) of the m largest keys log(u) / w, u_by_rank[j] being the draw of
+    the j-th positive weight (weighted_sampling_operator.hpp:67-90, ties as its heap keeps them), and the number kept. The
+    C++ facade draws u from the operator's generator; here the caller hands the draws in."""
+    L = _lib.lib()
+    w, u = _dev_f32(weights), _dev_f32(u_by_rank)
+    n = w.numel()
+    if u.numel() < int((w > 0).sum()):
+        raise SpError(1, "u_by_rank needs a draw for every positive weight")
+    flags = torch.empty(n, dtype=torch.uint8, device=w.device)
+    count = torch.empty(1, dtype=torch.int32, device=w.device)
+    nbytes = L.sp_weighted_sample_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=w.device)
+    check(L.sp_weighted_sample_flags(_ptr(w), _ptr(u), n, m, _ptr(flags), _ptr(count), _ptr(ws), nbytes, _stream()))
+    return flags, int(count.item())
+
+
+def uniform_fill_flags(flags, positions_sorted):
+    """sp_uniform_fill_flags, in place: for every p of positions_sorted (int32 or int64, ascending) the p-th point whose flag is
+    not 1 gets flag 1 (mixed_random_sampling_operator.hpp:82-99 once the host has drawn the positions). Returns flags."""
+    L = _lib.lib()
+    if not (flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous()):
+        raise SpError(1, "expected a contiguous uint8 CUDA tensor")
+    pos = positions_sorted.to(device=flags.device, dtype=torch.int32).contiguous()
+    n = flags.numel()
+    nbytes = L.sp_uniform_fill_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=flags.device)
+    check(L.sp_uniform_fill_flags(_ptr(flags), n, _ptr(pos), pos.numel(), _ptr(ws), nbytes, _stream()))
+    return flags
+
+
 class Communicator:
     """sp_comm: the library's own RCCL communicator (one process per GPU). The 128-byte unique id is made by rank 0
     (sp_comm_unique_id) and handed to the other ranks through whatever channel the application has — here a
