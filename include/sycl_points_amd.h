@@ -365,6 +365,89 @@ int sp_deskew_constant_velocity(const float* points, const float* covs, const fl
  * pipeline/velocity_update.hpp:71-72): the twist sp_deskew_constant_velocity takes. Poses column-major 4x4. Host only. */
 void sp_relative_twist_host(const float* prev_pose16, const float* cur_pose16, float* twist6_out);
 
+/* ------------------------------------------------------------------- IMU preintegration and IMU deskew */
+
+/* imu::IMUPreintegrationParams (algorithms/imu/imu_preintegration.hpp:138-166). */
+typedef struct sp_imu_params {
+    float gravity[3];  /* world frame, m/s^2; the reference's default is (0, 0, -9.80665) */
+    float accel_scale; /* applied to raw accelerations before the bias is subtracted */
+    float gyro_noise_density, accel_noise_density, gyro_bias_rw_density, accel_bias_rw_density;
+} sp_imu_params;
+/* imu::PreintegrationResult with its PreintegrationJacobians (imu_preintegration.hpp:98-135). Matrices column-major
+ * (Eigen .data() order); covariance: 15x15, [dp, dphi, dv, dba, dbg]. */
+typedef struct sp_imu_state {
+    float Delta_R[9], Delta_v[3], Delta_p[3], pad0;
+    double dt_total;
+    float J_R_bg[9], J_v_bg[9], J_v_ba[9], J_p_bg[9], J_p_ba[9];
+    float covariance[225];
+} sp_imu_state;
+
+/* imu::IMUPreintegration (imu_preintegration.hpp:180-529) on plain arrays; HOST only, no device is touched. bias6 is
+ * (gyro_bias, accel_bias). Kept as in the reference: the midpoint step; the first sample only primes the integrator;
+ * a sample whose stamp does not increase is dropped without replacing the previous one; a step with dt < 1e-9 is skipped;
+ * Delta_R is renormalised through a quaternion every 100 steps; the covariance step sym(F Sigma F^T + G Qd G^T) is skipped
+ * only when every noise density is zero and Sigma is zero (Eigen's isZero(): every |entry| <= 1e-5f). The reference's Eigen
+ * products are plain multiply-add sums, k ascending, chains of factors left to right (Eigen's own order is not pinned).
+ *   create   a handle in the state of the reference's constructor (no reset needed before the first sample)
+ *   reset    :202-212; NULL bias6 = zero bias, NULL covariance225 = zero, NULL R_world_body9 = identity
+ *   integrate  :217-230, one sample: absolute stamp in seconds, raw gyro (rad/s) and accel
+ *   num_measurements  the samples accepted since the reset (has_measurements() is > 0)
+ *   get      bias6 NULL: get_raw (:272); else get_corrected(bias6) (:244-269), the first-order bias correction with its
+ *            quaternion round trip (rotation_matrix_to_quaternion, normalize, quaternion_to_rotation_matrix)
+ *   predict_relative   predict_relative_transform (:307-330): T_body_i -> body_j, column-major 4x4
+ *   predict_transform  predict_transform (:280-295): T_world_body_j
+ * A null handle or a null argument not named optional above -> SP_ERR_INVALID_ARGUMENT. */
+int sp_imu_preint_create(const sp_imu_params* params, void** handle_out);
+void sp_imu_preint_destroy(void* handle);
+int sp_imu_preint_reset(void* handle, const float* bias6_host, const float* covariance225_host, const float* R_world_body9_host);
+int sp_imu_preint_integrate(void* handle, double timestamp, const float* gyro3_host, const float* accel3_host);
+int sp_imu_preint_num_measurements(void* handle);
+int sp_imu_preint_get(void* handle, const float* bias6_host, sp_imu_state* state_out);
+int sp_imu_preint_predict_relative(void* handle, const float* R_world_body9_host, const float* v_world3_host,
+                                   const float* bias6_host, float* T16_out_host);
+int sp_imu_preint_predict_transform(void* handle, const float* T_world_body16_host, const float* v_world3_host,
+                                    const float* bias6_host, float* T16_out_host);
+
+/* deskew::IMUDeskewStatus (algorithms/deskew/imu_deskew.hpp:32-38) */
+#define SP_IMU_DESKEW_SUCCESS 0
+#define SP_IMU_DESKEW_INSUFFICIENT_IMU_COVERAGE 1
+#define SP_IMU_DESKEW_NO_TIMESTAMPS 2
+#define SP_IMU_DESKEW_INVALID_SCAN_DURATION 3
+#define SP_IMU_DESKEW_EMPTY_CLOUD 4
+/* Steps 1-3 of deskew::deskew_point_cloud_imu (imu_deskew.hpp:158-285), HOST only: the samples within 50 ms of the scan
+ * window and the coverage checks; the virtual sample at scan_start_sec (the three lower_bound cases); the identity pose;
+ * then one pose per sample with float(stamp - scan_start_sec) >= 0, T_lidar_rel = T_il * T_imu_rel * T_il^-1 with T_imu_rel
+ * predict_relative_transform's, or (gyro_only != 0) get_corrected's Delta_R alone; the final coverage check. The rotation
+ * becomes a quaternion by the library's rotation_matrix_to_quaternion twin, not Eigen::Quaternionf's constructor (:265).
+ * stamps: n absolute seconds, ascending; gyro_accel: n rows of gyro xyz, accel xyz. traj_out: 8 floats per pose (q xyzw, t xyz,
+ * stamp in seconds from scan start: deskew::IMUTrajectoryPose), room for `capacity` poses; n + 1 always suffices.
+ * *status_out is an SP_IMU_DESKEW_* code (a scan_duration_sec <= 0 is INVALID_SCAN_DURATION); *n_traj_out is the number of
+ * poses on SUCCESS, else 0. A null argument or a capacity that is too small -> SP_ERR_INVALID_ARGUMENT. */
+int sp_imu_deskew_trajectory_host(const double* stamps_host, const float* gyro_accel_host, size_t n, double scan_start_sec,
+                                  double scan_duration_sec, const float* T_imu_to_lidar16_host, const float* bias6_host,
+                                  const sp_imu_params* params, const float* R_world_body9_host, const float* v_world3_host,
+                                  int gyro_only, float* traj_out_host, size_t capacity, size_t* n_traj_out, int* status_out);
+/* What sp_deskew_imu reads: n_traj - 1 rows of 16 floats, one per interval [i, i + 1] of the trajectory:
+ * t_lo, t_hi, q0[4], omega[3], t0[3], t1 - t0[3], 0. omega = so3_log(quat_mult(conj(q0), +-q1)), the sign by dot<4>(q0, q1) < 0:
+ * the first half of quat_slerp (imu_deskew.hpp:54-73), which the reference evaluates per point although it depends on the
+ * interval alone. HOST only. Null pointers or n_traj < 2 -> SP_ERR_INVALID_ARGUMENT. */
+int sp_imu_deskew_intervals_host(const float* traj_host, size_t n_traj, float* intervals_out_host);
+/* deskew::deskew_point_cloud_imu's kernel (imu_deskew.hpp:330-411). intervals: DEVICE memory, the rows of
+ * sp_imu_deskew_intervals_host, 16-byte aligned. Per point: t = t_ms * 1e-3f; a non-finite t copies the row (point, normal, all
+ * 16 floats of the covariance); otherwise the reference's bisection (lo = 0, hi = n_intervals, mid = (lo + hi) / 2,
+ * stamp[mid] <= t: the same interval as the reference for every table, ordered or not, and no index outside the table),
+ * alpha = (t_hi > t_lo) ? clamp((t - t_lo) / (t_hi - t_lo), 0, 1) : 0, q = quat_mult(q0, so3_exp(omega * alpha)),
+ * R = quaternion_to_rotation_matrix(q), p' = R p + fma(t1 - t0, alpha, t0) with w carried, n' = (R n, 0), C' = R (C3 R^T) in
+ * the top-left 3x3 of a zeroed 4x4. covs / normals may be NULL (together with their outputs). In place allowed
+ * (*_out == *_in): every row is read before it is written, so an in-place call returns the rotated normals and covariances -
+ * the reference, which zeroes its outputs before it reads its inputs, returns zeros there. A null points /
+ * timestamp_offsets_ms / points_out / intervals, covs or normals given without their output or the other way round,
+ * n_intervals < 1 or >= 2^31, n >= 2^32 -> SP_ERR_INVALID_ARGUMENT before any HIP call. n == 0: SP_OK, nothing enqueued.
+ * Enqueue only. */
+int sp_deskew_imu(const float* points, const float* covs, const float* normals, const float* timestamp_offsets_ms, size_t n,
+                  const float* intervals, size_t n_intervals, float* points_out, float* covs_out, float* normals_out,
+                  void* stream);
+
 /* ------------------------------------------------------------------- scan filters after kNN and covariances */
 
 /* AngleIncidenceFilterOperator::apply's kernel and checks (filter/preprocess_operator/angle_incidence_filter_operator.hpp:23-110):

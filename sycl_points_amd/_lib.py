@@ -84,8 +84,22 @@ class OptRequest(C.Structure):  # sp_opt_request
                 ("T_lin", C.c_float * 16), ("damping", C.c_float)]
 
 
+class ImuParams(C.Structure):  # sp_imu_params
+    _fields_ = [("gravity", C.c_float * 3), ("accel_scale", C.c_float), ("gyro_noise_density", C.c_float),
+                ("accel_noise_density", C.c_float), ("gyro_bias_rw_density", C.c_float), ("accel_bias_rw_density", C.c_float)]
+
+
+class ImuState(C.Structure):  # sp_imu_state
+    _fields_ = [("Delta_R", C.c_float * 9), ("Delta_v", C.c_float * 3), ("Delta_p", C.c_float * 3), ("pad0", C.c_float),
+                ("dt_total", C.c_double), ("J_R_bg", C.c_float * 9), ("J_v_bg", C.c_float * 9), ("J_v_ba", C.c_float * 9),
+                ("J_p_bg", C.c_float * 9), ("J_p_ba", C.c_float * 9), ("covariance", C.c_float * 225)]
+
+
+# deskew::IMUDeskewStatus (SP_IMU_DESKEW_*)
+IMU_DESKEW_STATUS = ("success", "insufficient_imu_coverage", "no_timestamps", "invalid_scan_duration", "empty_cloud")
 OPT_WANT_DONE, OPT_WANT_LINEARIZE, OPT_WANT_TRIAL = 0, 1, 2
 assert C.sizeof(Linearized) == 192
+assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
 _vp, _sz, _f, _i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
@@ -161,6 +175,18 @@ SIGNATURES = {
     "sp_intensity_correct": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp]),
     "sp_intensity_gaussian": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _f, _f, _f, _f, _vp, _vp]),
     "sp_relative_twist_host": (None, [_vp, _vp, _vp]),
+    "sp_imu_preint_create": (_i, [C.POINTER(ImuParams), C.POINTER(_vp)]),
+    "sp_imu_preint_destroy": (None, [_vp]),
+    "sp_imu_preint_reset": (_i, [_vp, _vp, _vp, _vp]),
+    "sp_imu_preint_integrate": (_i, [_vp, C.c_double, _vp, _vp]),
+    "sp_imu_preint_num_measurements": (_i, [_vp]),
+    "sp_imu_preint_get": (_i, [_vp, _vp, C.POINTER(ImuState)]),
+    "sp_imu_preint_predict_relative": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sp_imu_preint_predict_transform": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sp_imu_deskew_trajectory_host": (_i, [_vp, _vp, _sz, C.c_double, C.c_double, _vp, _vp, C.POINTER(ImuParams), _vp, _vp, _i, _vp,
+                                           _sz, C.POINTER(_sz), C.POINTER(_i)]),
+    "sp_imu_deskew_intervals_host": (_i, [_vp, _sz, _vp]),
+    "sp_deskew_imu": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "sp_box_filter_flags": (_i, [_vp, _sz, _f, _f, _vp, _vp]),
     "sp_compact_workspace_bytes": (_sz, [_sz]),
     "sp_compact_by_flags": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -9,6 +9,7 @@ Names, argument meaning and error behaviour follow the reference (paths relative
 device memory, streams and torch.distributed only — all compute goes through libsycl_points_amd.so.
 """
 import ctypes as C
+import enum
 import weakref
 from dataclasses import dataclass, field
 
@@ -807,6 +808,218 @@ def deskew_point_cloud_constant_velocity(cloud, previous_pose, current_pose, int
         if hasattr(cloud, k):
             setattr(out, k, getattr(cloud, k))
     return out
+
+
+# ------------------------------------------------------------------ IMU preintegration / IMU deskew
+@dataclass
+class IMUPreintegrationParams:
+    """imu::IMUPreintegrationParams (algorithms/imu/imu_preintegration.hpp:138-166)"""
+    gravity: tuple = (0.0, 0.0, -9.80665)
+    accel_scale: float = 1.0
+    gyro_noise_density: float = 0.0
+    accel_noise_density: float = 0.0
+    gyro_bias_rw_density: float = 0.0
+    accel_bias_rw_density: float = 0.0
+
+    def _c(self):
+        return _lib.ImuParams((C.c_float * 3)(*[float(g) for g in self.gravity]), self.accel_scale, self.gyro_noise_density,
+                              self.accel_noise_density, self.gyro_bias_rw_density, self.accel_bias_rw_density)
+
+
+class IMUDeskewStatus(enum.IntEnum):
+    """deskew::IMUDeskewStatus (algorithms/deskew/imu_deskew.hpp:32-38)"""
+    success = 0
+    insufficient_imu_coverage = 1
+    no_timestamps = 2
+    invalid_scan_duration = 3
+    empty_cloud = 4
+
+
+@dataclass
+class PreintegrationResult:
+    """imu::PreintegrationResult with its Jacobians (imu_preintegration.hpp:98-135), numpy arrays in the usual row-major view"""
+    Delta_R: np.ndarray
+    Delta_v: np.ndarray
+    Delta_p: np.ndarray
+    dt_total: float
+    J_R_bg: np.ndarray
+    J_v_bg: np.ndarray
+    J_v_ba: np.ndarray
+    J_p_bg: np.ndarray
+    J_p_ba: np.ndarray
+    covariance: np.ndarray
+
+
+def _f32(a, n):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1))
+    if a.size != n:
+        raise SpError(1, f"expected {n} values, got {a.size}")
+    return a
+
+
+def _bias6(bias):
+    return np.zeros(6, np.float32) if bias is None else _f32(bias, 6)
+
+
+def _hp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class IMUPreintegration:
+    """imu::IMUPreintegration (imu_preintegration.hpp:180-529): the C library's host integrator (sp_imu_preint_*), so the
+    arithmetic exists once. A bias is six values, (gyro_bias, accel_bias); matrices are row-major numpy arrays."""
+
+    def __init__(self, params=None):
+        self.params = params or IMUPreintegrationParams()
+        self._h = C.c_void_p()
+        check(_lib.lib().sp_imu_preint_create(C.byref(self.params._c()), C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.lib().sp_imu_preint_destroy(self._h)
+            self._h = None
+
+    def reset(self, bias=None, initial_covariance=None, R_world_body=None):
+        cov = None if initial_covariance is None else _f32(np.asarray(initial_covariance, np.float32).T, 225)
+        R = None if R_world_body is None else _f32(np.asarray(R_world_body, np.float32).T, 9)
+        check(_lib.lib().sp_imu_preint_reset(self._h, _hp(_bias6(bias)), _hp(cov), _hp(R)))
+
+    def integrate(self, timestamp, gyro, accel):
+        check(_lib.lib().sp_imu_preint_integrate(self._h, float(timestamp), _hp(_f32(gyro, 3)), _hp(_f32(accel, 3))))
+
+    def integrate_batch(self, stamps, gyro, accel):
+        for t, g, a in zip(stamps, gyro, accel):
+            self.integrate(t, g, a)
+
+    def _get(self, bias):
+        st = _lib.ImuState()
+        check(_lib.lib().sp_imu_preint_get(self._h, None if bias is None else _hp(_bias6(bias)), C.byref(st)))
+        m3 = lambda f: np.array(f, np.float32).reshape(3, 3).T.copy()  # noqa: E731  (column-major at the C ABI)
+        return PreintegrationResult(m3(st.Delta_R), np.array(st.Delta_v, np.float32), np.array(st.Delta_p, np.float32),
+                                    float(st.dt_total), m3(st.J_R_bg), m3(st.J_v_bg), m3(st.J_v_ba), m3(st.J_p_bg), m3(st.J_p_ba),
+                                    np.array(st.covariance, np.float32).reshape(15, 15).T.copy())
+
+    def get_raw(self):
+        return self._get(None)
+
+    def get_corrected(self, new_bias):
+        return self._get(_bias6(new_bias))
+
+    def predict_relative_transform(self, R_world_body_i, v_world_i, current_bias=None):
+        T = np.zeros(16, np.float32)
+        check(_lib.lib().sp_imu_preint_predict_relative(self._h, _hp(_f32(np.asarray(R_world_body_i, np.float32).T, 9)),
+                                                        _hp(_f32(v_world_i, 3)), _hp(_bias6(current_bias)), _hp(T)))
+        return T.reshape(4, 4).T.copy()
+
+    def predict_transform(self, T_world_body_i, v_world_i, current_bias=None):
+        T = np.zeros(16, np.float32)
+        check(_lib.lib().sp_imu_preint_predict_transform(self._h, _hp(_f32(_T16(T_world_body_i), 16)), _hp(_f32(v_world_i, 3)),
+                                                         _hp(_bias6(current_bias)), _hp(T)))
+        return T.reshape(4, 4).T.copy()
+
+    def get_dt_total(self):
+        return self.get_raw().dt_total
+
+    def has_measurements(self):
+        return _lib.lib().sp_imu_preint_num_measurements(self._h) > 0
+
+    def get_params(self):
+        return self.params
+
+
+def interpolate_measurement(before, after, timestamp):
+    """imu::interpolate_measurement (imu_preintegration.hpp:32-42); a measurement is (timestamp, gyro[3], accel[3])."""
+    span = after[0] - before[0]
+    if span <= 0.0:
+        return before
+    alpha = min(max((timestamp - before[0]) / span, 0.0), 1.0)
+    mix = lambda a, b: ((1.0 - alpha) * np.asarray(a, np.float32).astype(np.float64)  # noqa: E731
+                        + alpha * np.asarray(b, np.float32).astype(np.float64)).astype(np.float32)
+    return (timestamp, mix(before[1], after[1]), mix(before[2], after[2]))
+
+
+def build_measurement_window(measurements, start_timestamp, end_timestamp):
+    """imu::build_measurement_window (imu_preintegration.hpp:55-87): the samples of (start, end] with one interpolated at
+    either boundary when bracketing samples exist."""
+    window = []
+    if end_timestamp <= start_timestamp:
+        return window
+    before_start = None
+    for m in measurements:
+        if m[0] <= start_timestamp:
+            before_start = m
+            continue
+        if m[0] > end_timestamp:
+            if not window and before_start is not None:
+                window.append(interpolate_measurement(before_start, m, start_timestamp))
+            if window and window[-1][0] < end_timestamp:
+                window.append(interpolate_measurement(window[-1], m, end_timestamp))
+            break
+        if not window and before_start is not None:
+            window.append(interpolate_measurement(before_start, m, start_timestamp) if before_start[0] < start_timestamp
+                          else before_start)
+        window.append(m)
+    return window
+
+
+def imu_deskew_trajectory(stamps, gyro, accel, scan_start_sec, scan_duration_sec, T_imu_to_lidar, bias=None, params=None,
+                          R_world_body=None, v_world=None, gyro_only=False):
+    """Steps 1-3 of deskew::deskew_point_cloud_imu (deskew/imu_deskew.hpp:158-285) on the host (sp_imu_deskew_trajectory_host):
+    (trajectory, status), the trajectory an (m, 8) float32 array of q xyzw, t xyz, seconds from scan start, or None."""
+    stamps = np.ascontiguousarray(np.asarray(stamps, np.float64).reshape(-1))
+    n = stamps.size
+    ga = np.ascontiguousarray(np.concatenate([np.asarray(gyro, np.float32).reshape(n, 3), np.asarray(accel, np.float32).reshape(n, 3)],
+                                             axis=1))
+    traj = np.zeros((n + 1, 8), np.float32)
+    m, status = C.c_size_t(0), C.c_int(0)
+    R = np.eye(3, dtype=np.float32) if R_world_body is None else np.asarray(R_world_body, np.float32)
+    v = np.zeros(3, np.float32) if v_world is None else v_world
+    check(_lib.lib().sp_imu_deskew_trajectory_host(_hp(stamps), _hp(ga), n, float(scan_start_sec), float(scan_duration_sec),
+                                                   _hp(_f32(_T16(T_imu_to_lidar), 16)), _hp(_bias6(bias)),
+                                                   C.byref((params or IMUPreintegrationParams())._c()), _hp(_f32(R.T, 9)),
+                                                   _hp(_f32(v, 3)), int(bool(gyro_only)), _hp(traj), n + 1, C.byref(m),
+                                                   C.byref(status)))
+    status = IMUDeskewStatus(status.value)
+    return (traj[:m.value].copy() if status == IMUDeskewStatus.success else None), status
+
+
+def imu_deskew_intervals(trajectory):
+    """The (m - 1, 16) interval rows sp_deskew_imu reads (sp_imu_deskew_intervals_host)."""
+    traj = np.ascontiguousarray(trajectory, np.float32)
+    rows = np.zeros((traj.shape[0] - 1, 16), np.float32)
+    check(_lib.lib().sp_imu_deskew_intervals_host(_hp(traj), traj.shape[0], _hp(rows)))
+    return rows
+
+
+def deskew_point_cloud_imu(cloud, stamps, gyro, accel, scan_start_sec, T_imu_to_lidar, bias=None, params=None, R_world_body=None,
+                           v_world=None, gyro_only=False):
+    """deskew::deskew_point_cloud_imu (deskew/imu_deskew.hpp:122-417): (a new cloud, status) with every point moved from the
+    sensor frame at its time stamp (timestamp_offsets, ms) into the frame at scan start along the trajectory the IMU samples give;
+    normals and covariances are rotated with it, the other attributes are shared. The scan lasts
+    (end_time_ms - start_time_ms) * 1e-3 seconds, both attributes of the cloud. (None, status) where the reference returns false."""
+    n = cloud.size()
+    if n == 0:
+        return None, IMUDeskewStatus.empty_cloud
+    if not cloud.has_timestamps():
+        return None, IMUDeskewStatus.no_timestamps
+    duration = (float(getattr(cloud, "end_time_ms", 0.0)) - float(getattr(cloud, "start_time_ms", 0.0))) * 1e-3
+    traj, status = imu_deskew_trajectory(stamps, gyro, accel, scan_start_sec, duration, T_imu_to_lidar, bias, params, R_world_body,
+                                         v_world, gyro_only)
+    if traj is None:
+        return None, status
+    p = _dev_f32(cloud.points, 4)
+    ts = _dev_f32(cloud.timestamp_offsets)
+    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
+    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
+    rows = torch.from_numpy(imu_deskew_intervals(traj)).to(p.device)  # a pageable copy: stream-ordered, returns when it is staged
+    out = PointCloudShared(torch.empty_like(p), None if covs is None else torch.empty_like(covs),
+                           None if nrm is None else torch.empty_like(nrm), cloud.rgb, cloud.intensities, cloud.timestamp_offsets,
+                           device=p.device)
+    check(_lib.lib().sp_deskew_imu(_ptr(p), _ptr(covs), _ptr(nrm), _ptr(ts), n, _ptr(rows), rows.shape[0], _ptr(out.points),
+                                   _ptr(out.covs), _ptr(out.normals), _stream()))
+    for k in ("start_time_ms", "end_time_ms"):
+        setattr(out, k, getattr(cloud, k))
+    return out, status
 
 
 def box_filter_flags(points, min_distance, max_distance):
