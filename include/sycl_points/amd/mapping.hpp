@@ -1,7 +1,9 @@
 // sycl_points facade for MI355X — algorithms/mapping/voxel_hash_map.hpp:22-250 (VoxelHashMap) over the sp_vhm_* entry
 // points. Same public surface as the reference: constructor (queue, voxel_size), the five setters / getters, clear,
 // add_point_cloud(cloud, sensor_pose), downsampling(result, center, distance), compute_overlap_ratio, remove_old_data.
-// The table lives in HBM inside the library object; clouds go in and come out through their device mirrors.
+// algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 (OccupancyGridMap) over the sp_ogm_* entry points: the reference's public
+// signatures without extract_visible_points, which the reference marks experimental and no pipeline calls.
+// The tables live in HBM inside the library objects; clouds go in and come out through their device mirrors.
 #pragma once
 #include "core.hpp"
 
@@ -79,6 +81,94 @@ public:
 private:
     sycl_utils::DeviceQueue queue_;
     sp_voxel_hash_map* h_ = nullptr;
+};
+
+class OccupancyGridMap {
+public:
+    using Ptr = std::shared_ptr<OccupancyGridMap>;
+
+    OccupancyGridMap(const sycl_utils::DeviceQueue& queue, const float voxel_size) : queue_(queue) {
+        throw_on_error(sp_ogm_create(voxel_size, queue_.stream(), &h_));  // voxel_size <= 0: std::invalid_argument
+    }
+    ~OccupancyGridMap() { sp_ogm_destroy(h_); }
+    OccupancyGridMap(const OccupancyGridMap&) = delete;
+    OccupancyGridMap& operator=(const OccupancyGridMap&) = delete;
+
+    /// occupancy_grid_map.hpp:42-69
+    void clear() { throw_on_error(sp_ogm_clear(h_, queue_.stream())); }
+
+    void set_voxel_size(const float voxel_size) { throw_on_error(sp_ogm_set(h_, SP_OGM_VOXEL_SIZE, voxel_size)); }
+    float voxel_size() const { return sp_ogm_get(h_, SP_OGM_VOXEL_SIZE); }
+
+    /// occupancy_grid_map.hpp:85-93 — 0.5 where the map holds no voxel
+    float voxel_probability(const Eigen::Vector3f& position) const {
+        const float p[3] = {position.x(), position.y(), position.z()};
+        float r = 0.5f;
+        throw_on_error(sp_ogm_voxel_probability(h_, p, &r, queue_.stream()));
+        return r;
+    }
+
+    void set_log_odds_hit(const float value) { throw_on_error(sp_ogm_set(h_, SP_OGM_LOG_ODDS_HIT, value)); }
+    void set_log_odds_miss(const float value) { throw_on_error(sp_ogm_set(h_, SP_OGM_LOG_ODDS_MISS, value)); }
+    void set_free_space_updates_enabled(const bool enabled) {
+        throw_on_error(sp_ogm_set(h_, SP_OGM_FREE_SPACE_UPDATES, enabled ? 1.0f : 0.0f));
+    }
+    void set_voxel_pruning_enabled(const bool enabled) { throw_on_error(sp_ogm_set(h_, SP_OGM_VOXEL_PRUNING, enabled ? 1.0f : 0.0f)); }
+    void set_log_odds_limits(const float minimum, const float maximum) {  // minimum > maximum: std::invalid_argument
+        throw_on_error(sp_ogm_set_log_odds_limits(h_, minimum, maximum));
+    }
+    void set_occupancy_threshold(const float probability) {  // outside (0, 1): std::invalid_argument
+        throw_on_error(sp_ogm_set(h_, SP_OGM_OCCUPANCY_THRESHOLD, probability));
+    }
+    void set_stale_frame_threshold(const uint32_t threshold) {
+        throw_on_error(sp_ogm_set(h_, SP_OGM_STALE_FRAME_THRESHOLD, (float)threshold));
+    }
+
+    /// occupancy_grid_map.hpp:129-163 — cloud in the sensor frame, sensor_pose in the map frame.
+    void add_point_cloud(const PointCloudShared& cloud, const Eigen::Isometry3f& sensor_pose) {
+        if (!cloud.points || cloud.points->empty()) return;
+        const size_t N = cloud.size();
+        throw_on_error(sp_ogm_add_point_cloud(
+            h_, cloud.points_device(), cloud.covs_device(),
+            cloud.has_rgb() ? reinterpret_cast<const float*>(cloud.rgb->device_data()) : nullptr,
+            cloud.has_intensity() ? cloud.intensities->device_data() : nullptr, N, sensor_pose.matrix().data(), queue_.stream()));
+    }
+
+    /// occupancy_grid_map.hpp:169-181 — occupied voxels within max_distance (L-infinity) of the sensor, in table-slot order.
+    void extract_occupied_points(PointCloudShared& result, const Eigen::Isometry3f& sensor_pose,
+                                 const float max_distance = 100.0f) const {
+        const size_t cap = sp_ogm_info(h_, SP_OGM_INFO_VOXEL_NUM);
+        if (cap == 0) { result.clear(); return; }
+        const bool has_cov = sp_ogm_info(h_, SP_OGM_INFO_HAS_COV), has_rgb = sp_ogm_info(h_, SP_OGM_INFO_HAS_RGB),
+                   has_int = sp_ogm_info(h_, SP_OGM_INFO_HAS_INTENSITY);
+        const Eigen::Vector3f t = sensor_pose.translation();
+        const float c[3] = {t.x(), t.y(), t.z()};
+        size_t n = 0;
+        throw_on_error(sp_ogm_extract_occupied_points(
+            h_, c, max_distance, reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
+            has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
+            has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
+            has_int ? result.intensities->device_data_for_write(cap) : nullptr, nullptr, cap, &n, queue_.stream()));
+        result.points->set_device_size(n);
+        if (has_cov) result.covs->set_device_size(n); else result.covs->clear();
+        if (has_rgb) result.rgb->set_device_size(n); else result.rgb->clear();
+        if (has_int) result.intensities->set_device_size(n); else result.intensities->clear();
+        result.normals->clear();
+        result.timestamp_offsets->clear();
+    }
+
+    /// occupancy_grid_map.hpp:417-472
+    float compute_overlap_ratio(const PointCloudShared& cloud, const Eigen::Isometry3f& sensor_pose) const {
+        if (!cloud.points || cloud.points->empty()) return 0.0f;
+        float r = 0.0f;
+        throw_on_error(sp_ogm_overlap_ratio(h_, cloud.points_device(), cloud.size(), sensor_pose.matrix().data(), &r,
+                                            queue_.stream()));
+        return r;
+    }
+
+private:
+    sycl_utils::DeviceQueue queue_;
+    sp_occupancy_grid_map* h_ = nullptr;
 };
 
 }  // namespace mapping

@@ -1041,6 +1041,58 @@ int sp_vhm_overlap_ratio(const sp_voxel_hash_map* map, const float* points, size
                          float* ratio_out_host, void* stream);
 int sp_vhm_remove_old_data(sp_voxel_hash_map* map, void* stream);
 
+/* ---------------------------------------------------------------- OccupancyGridMap (mapping/occupancy_grid_map.hpp:27-190, 417)
+ * The other submap of Submap::build_submap: the VoxelHashMap table (same key, same double hashing, same capacity ladder; 128
+ * probes; removed slots keep a `deleted` key) whose voxels also carry a log-odds occupancy. Per voxel: sums of the map-frame hit
+ * points, of log(R C R^T), of rgb and of intensity, hit_count, miss_count, log_odds, the frame of the last update.
+ *   sp_ogm_create        constructor; voxel_size <= 0 -> SP_ERR_INVALID_ARGUMENT (std::invalid_argument, :73-76)
+ *   sp_ogm_set / _get    the setters (:73-124) and rehash_threshold_; defaults :1658-1680. SP_OGM_LOG_ODDS_MIN above the maximum,
+ *                        SP_OGM_LOG_ODDS_MAX below the minimum and an occupancy threshold outside (0, 1) are SP_ERR_INVALID_ARGUMENT.
+ *                        SP_OGM_OCCUPANCY_THRESHOLD is given and returned as a probability and kept as log-odds.
+ *   sp_ogm_set_log_odds_limits  set_log_odds_limits(minimum, maximum) in one call (:107-113)
+ *   sp_ogm_add_point_cloud  add_point_cloud (:129-163): n == 0 returns at once; else [rehash] -> hits (centroid sums, hit_count,
+ *                        covariance in the log-Euclidean encoding, rgb, intensity) -> [free-space carving: one miss for every
+ *                        cell a ray crosses between the sensor's cell and the hit cell, the hit cell excluded, after growing the
+ *                        table for the estimated number of visits] -> log_odds += hits * log_odds_hit + misses * log_odds_miss,
+ *                        clamped -> [prune voxels not updated for more than stale_frame_threshold frames] -> ++frame.
+ *                        The ray walk takes exactly |dix| + |diy| + |diz| steps; rays with a non-finite end point, an end point
+ *                        outside the 21-bit cell range, or shorter than sqrt(FLT_EPSILON) post nothing, and nothing is carved
+ *                        from a sensor position outside that range.
+ *   sp_ogm_extract_occupied_points  extract_occupied_points (:169-181, 1530-1639): voxels with hit_count > 0, log_odds >= the
+ *                        threshold and a centroid within max_distance (L-infinity) of sensor_xyz -> mean point (w = 1), exp of
+ *                        the mean log-covariance, mean rgb / intensity, in table-slot order. Attribute outputs are written only
+ *                        when the map holds that attribute; out arrays must hold sp_ogm_info(SP_OGM_INFO_VOXEL_NUM) entries.
+ *   sp_ogm_overlap_ratio compute_overlap_ratio (:417-472)
+ *   sp_ogm_voxel_probability  voxel_probability (:85-93): 0.5 where the map has no voxel
+ *   sp_ogm_export        every live slot, in slot order, for tests and debugging: key, hit_count, miss_count, log_odds, the frame
+ *                        of the last update, the sums (xyz 3 floats, covariance 6, rgb 4, intensity 1 per row). Each output may be
+ *                        NULL; those given must hold sp_ogm_info(SP_OGM_INFO_VOXEL_NUM) rows.
+ * Like the reference's methods these calls wait for their kernels. All array arguments are device pointers; *_host are host. */
+typedef struct sp_occupancy_grid_map sp_occupancy_grid_map;
+enum { SP_OGM_VOXEL_SIZE = 0, SP_OGM_LOG_ODDS_HIT = 1, SP_OGM_LOG_ODDS_MISS = 2, SP_OGM_LOG_ODDS_MIN = 3, SP_OGM_LOG_ODDS_MAX = 4,
+       SP_OGM_OCCUPANCY_THRESHOLD = 5, SP_OGM_FREE_SPACE_UPDATES = 6, SP_OGM_VOXEL_PRUNING = 7, SP_OGM_STALE_FRAME_THRESHOLD = 8,
+       SP_OGM_REHASH_THRESHOLD = 9 };
+enum { SP_OGM_INFO_VOXEL_NUM = 0, SP_OGM_INFO_CAPACITY = 1, SP_OGM_INFO_FRAME_INDEX = 2, SP_OGM_INFO_HAS_COV = 3,
+       SP_OGM_INFO_HAS_RGB = 4, SP_OGM_INFO_HAS_INTENSITY = 5 };
+int sp_ogm_create(float voxel_size, void* stream, sp_occupancy_grid_map** out);
+void sp_ogm_destroy(sp_occupancy_grid_map* map);
+int sp_ogm_set(sp_occupancy_grid_map* map, int param, float value);
+int sp_ogm_set_log_odds_limits(sp_occupancy_grid_map* map, float minimum, float maximum);
+float sp_ogm_get(const sp_occupancy_grid_map* map, int param);
+size_t sp_ogm_info(const sp_occupancy_grid_map* map, int what);
+int sp_ogm_clear(sp_occupancy_grid_map* map, void* stream);
+int sp_ogm_add_point_cloud(sp_occupancy_grid_map* map, const float* points, const float* covs, const float* rgb,
+                           const float* intensities, size_t n, const float* sensor_pose_host16, void* stream);
+int sp_ogm_extract_occupied_points(sp_occupancy_grid_map* map, const float* sensor_xyz_host3, float max_distance,
+                                   float* points_out, float* covs_out, float* rgb_out, float* intensities_out,
+                                   uint64_t* keys_out_opt, size_t out_capacity, size_t* n_out_host, void* stream);
+int sp_ogm_overlap_ratio(const sp_occupancy_grid_map* map, const float* points, size_t n, const float* sensor_pose_host16,
+                         float* ratio_out_host, void* stream);
+int sp_ogm_voxel_probability(const sp_occupancy_grid_map* map, const float* xyz_host3, float* probability_out_host, void* stream);
+int sp_ogm_export(sp_occupancy_grid_map* map, uint64_t* keys_out, uint32_t* hit_count_out, uint32_t* miss_count_out,
+                  float* log_odds_out, uint32_t* last_updated_out, float* sum_xyz_out, float* cov_sums_out, float* rgb_sums_out,
+                  float* intensity_sums_out, size_t out_capacity, size_t* n_out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,6 +272,18 @@ SIGNATURES = {
     "sp_vhm_downsampling": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "sp_vhm_overlap_ratio": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_f), _vp]),
     "sp_vhm_remove_old_data": (_i, [_vp, _vp]),
+    "sp_ogm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
+    "sp_ogm_destroy": (None, [_vp]),
+    "sp_ogm_set": (_i, [_vp, _i, _f]),
+    "sp_ogm_set_log_odds_limits": (_i, [_vp, _f, _f]),
+    "sp_ogm_get": (_f, [_vp, _i]),
+    "sp_ogm_info": (_sz, [_vp, _i]),
+    "sp_ogm_clear": (_i, [_vp, _vp]),
+    "sp_ogm_add_point_cloud": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sp_ogm_extract_occupied_points": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sp_ogm_overlap_ratio": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_f), _vp]),
+    "sp_ogm_voxel_probability": (_i, [_vp, _vp, C.POINTER(_f), _vp]),
+    "sp_ogm_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
 }
 
 

@@ -1378,6 +1378,122 @@ class VoxelHashMap:
         check(_lib.lib().sp_vhm_remove_old_data(self._h, _stream()))
 
 
+class OccupancyGridMap:
+    """algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 over the sp_ogm_* entry points: the log-odds submap in HBM, with
+    free-space carving along the rays from the sensor. add_point_cloud takes a PointCloudShared in the sensor frame and the sensor
+    pose (4x4, map frame); extract_occupied_points returns a PointCloudShared of the occupied voxels' means (plus `.keys`, the voxel
+    keys in output order: rows are in table-slot order, align them by key). extract_visible_points is not provided."""
+    _PARAM = {"voxel_size": 0, "log_odds_hit": 1, "log_odds_miss": 2, "log_odds_min": 3, "log_odds_max": 4,
+              "occupancy_threshold": 5, "free_space_updates_enabled": 6, "voxel_pruning_enabled": 7, "stale_frame_threshold": 8,
+              "rehash_threshold": 9}
+    _INFO = {"voxel_num": 0, "capacity": 1, "frame_index": 2, "has_cov": 3, "has_rgb": 4, "has_intensity": 5}
+
+    def __init__(self, voxel_size, device="cuda"):
+        self.device = torch.device(device)
+        h = C.c_void_p()
+        check(_lib.lib().sp_ogm_create(float(voxel_size), _stream(), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().sp_ogm_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _set(self, name, value):
+        check(_lib.lib().sp_ogm_set(self._h, self._PARAM[name], float(value)))
+
+    def _get(self, name):
+        return float(_lib.lib().sp_ogm_get(self._h, self._PARAM[name]))
+
+    def info(self, name):
+        return int(_lib.lib().sp_ogm_info(self._h, self._INFO[name]))
+
+    def set_voxel_size(self, v): self._set("voxel_size", v)  # noqa: E704
+    def voxel_size(self): return self._get("voxel_size")  # noqa: E704
+    def set_log_odds_hit(self, v): self._set("log_odds_hit", v)  # noqa: E704
+    def set_log_odds_miss(self, v): self._set("log_odds_miss", v)  # noqa: E704
+    def set_free_space_updates_enabled(self, on): self._set("free_space_updates_enabled", bool(on))  # noqa: E704
+    def set_voxel_pruning_enabled(self, on): self._set("voxel_pruning_enabled", bool(on))  # noqa: E704
+    def set_occupancy_threshold(self, probability): self._set("occupancy_threshold", probability)  # noqa: E704
+    def set_stale_frame_threshold(self, v): self._set("stale_frame_threshold", int(v))  # noqa: E704
+    def set_rehash_threshold(self, v): self._set("rehash_threshold", v)  # noqa: E704
+
+    def set_log_odds_limits(self, minimum, maximum):
+        check(_lib.lib().sp_ogm_set_log_odds_limits(self._h, float(minimum), float(maximum)))
+
+    def get(self, name):
+        """the value of a setting by name (occupancy_threshold as a probability)"""
+        return self._get(name)
+
+    def clear(self):
+        check(_lib.lib().sp_ogm_clear(self._h, _stream()))
+
+    def add_point_cloud(self, cloud, sensor_pose=None):
+        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
+        n = cloud.size()
+        check(_lib.lib().sp_ogm_add_point_cloud(
+            self._h, _ptr(cloud.points) if n else None, _ptr(cloud.covs) if (n and cloud.has_cov()) else None,
+            _ptr(cloud.rgb) if (n and cloud.has_rgb()) else None,
+            _ptr(cloud.intensities) if (n and cloud.has_intensity()) else None, n, T.ctypes.data_as(C.c_void_p), _stream()))
+
+    def extract_occupied_points(self, sensor_pose=None, max_distance=100.0):
+        cap = self.info("voxel_num")
+        dev = self.device
+        rows = max(cap, 1)
+        pts = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        covs = torch.empty((rows, 16), dtype=torch.float32, device=dev) if self.info("has_cov") else None
+        rgb = torch.empty((rows, 4), dtype=torch.float32, device=dev) if self.info("has_rgb") else None
+        inten = torch.empty(rows, dtype=torch.float32, device=dev) if self.info("has_intensity") else None
+        keys = torch.empty(rows, dtype=torch.int64, device=dev)
+        T = np.asarray(identity() if sensor_pose is None else sensor_pose, np.float32).reshape(4, 4)
+        c = np.ascontiguousarray(T[:3, 3]).copy()
+        n_out = C.c_size_t(0)
+        check(_lib.lib().sp_ogm_extract_occupied_points(self._h, c.ctypes.data_as(C.c_void_p), float(max_distance), _ptr(pts),
+                                                        _ptr(covs), _ptr(rgb), _ptr(inten), _ptr(keys), cap, C.byref(n_out),
+                                                        _stream()))
+        n = n_out.value
+        out = PointCloudShared(pts[:n], covs=None if covs is None else covs[:n], rgb=None if rgb is None else rgb[:n],
+                               intensities=None if inten is None else inten[:n], device=dev)
+        out.keys = keys[:n]
+        return out
+
+    def compute_overlap_ratio(self, cloud, sensor_pose=None):
+        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
+        r = C.c_float(0.0)
+        n = cloud.size()
+        check(_lib.lib().sp_ogm_overlap_ratio(self._h, _ptr(cloud.points) if n else None, n, T.ctypes.data_as(C.c_void_p),
+                                              C.byref(r), _stream()))
+        return float(r.value)
+
+    def voxel_probability(self, position):
+        p = np.asarray(position, np.float32).reshape(-1)[:3].copy()
+        r = C.c_float(0.5)
+        check(_lib.lib().sp_ogm_voxel_probability(self._h, p.ctypes.data_as(C.c_void_p), C.byref(r), _stream()))
+        return float(r.value)
+
+    def export(self):
+        """every live voxel in table-slot order, as numpy arrays: keys (uint64), hit_count, miss_count, log_odds, last_updated,
+        sum_xyz (n, 3), cov_sums (n, 6: xx xy xz yy yz zz of the log-covariances), rgb_sums (n, 4), intensity_sums"""
+        cap = self.info("voxel_num")
+        dev = self.device
+        rows = max(cap, 1)
+        mk = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        keys, hits, miss = mk(rows, torch.int64), mk(rows, torch.int32), mk(rows, torch.int32)
+        lo, last, xyz = mk(rows, torch.float32), mk(rows, torch.int32), mk((rows, 3), torch.float32)
+        cov, rgb, inten = mk((rows, 6), torch.float32), mk((rows, 4), torch.float32), mk(rows, torch.float32)
+        n_out = C.c_size_t(0)
+        check(_lib.lib().sp_ogm_export(self._h, _ptr(keys), _ptr(hits), _ptr(miss), _ptr(lo), _ptr(last), _ptr(xyz), _ptr(cov),
+                                       _ptr(rgb), _ptr(inten), cap, C.byref(n_out), _stream()))
+        n = n_out.value
+        host = lambda t: t[:n].cpu().numpy()  # noqa: E731
+        return {"keys": host(keys).view(np.uint64), "hit_count": host(hits).view(np.uint32),
+                "miss_count": host(miss).view(np.uint32), "log_odds": host(lo), "last_updated": host(last).view(np.uint32),
+                "sum_xyz": host(xyz), "cov_sums": host(cov), "rgb_sums": host(rgb), "intensity_sums": host(inten)}
+
+
 class PreparedTarget:
     """Plane-regularised target covariances stored in the cell order of a GridKNN (sp_gicp_target_*): the target half of
     the prepared / fused GICP iteration. Holds a reference to the grid, which it borrows."""
