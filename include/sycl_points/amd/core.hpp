@@ -1064,4 +1064,44 @@ private:
     }
 };
 
+namespace detail {
+
+/// What a deskew kernel reads and writes; covariances and normals are null where the input has none.
+struct DeskewBuffers {
+    const float *points_in, *covs_in = nullptr, *normals_in = nullptr;
+    float *points_out, *covs_out = nullptr, *normals_out = nullptr;
+};
+
+/// The output side of both deskews (relative_pose_deskew.hpp:62-95, imu_deskew.hpp:297-325). Out of place the output takes the
+/// input's timing and the attributes the deskew does not touch (rgb, intensities), loses the normals and covariances the input
+/// does not have, and is sized for the kernel, which writes every row. In place (`&input == &output`) nothing is copied and the
+/// kernel reads and writes the same buffers.
+inline DeskewBuffers prepare_deskew_output(const PointCloudShared& input, PointCloudShared& output) {
+    const size_t N = input.size();
+    const bool cov = input.has_cov(), nrm = input.has_normal();
+    DeskewBuffers b;
+    if (&input == &output) {
+        b.points_in = b.points_out = reinterpret_cast<float*>(output.points->device_data_rw());
+        if (cov) b.covs_in = b.covs_out = reinterpret_cast<float*>(output.covs->device_data_rw());
+        if (nrm) b.normals_in = b.normals_out = reinterpret_cast<float*>(output.normals->device_data_rw());
+        return b;
+    }
+    output.start_time_ms = input.start_time_ms;
+    output.end_time_ms = input.end_time_ms;
+    *output.timestamp_offsets = *input.timestamp_offsets;
+    if (!nrm) output.normals->clear();
+    if (!cov) output.covs->clear();
+    if (input.has_rgb()) *output.rgb = *input.rgb; else output.rgb->clear();
+    if (input.has_intensity()) *output.intensities = *input.intensities; else output.intensities->clear();
+    b.points_in = input.points_device();
+    b.covs_in = input.covs_device();
+    b.normals_in = input.normals_device();
+    b.points_out = reinterpret_cast<float*>(output.points->device_data_for_write(N));
+    if (cov) b.covs_out = reinterpret_cast<float*>(output.covs->device_data_for_write(N));
+    if (nrm) b.normals_out = reinterpret_cast<float*>(output.normals->device_data_for_write(N));
+    return b;
+}
+
+}  // namespace detail
+
 }  // namespace sycl_points

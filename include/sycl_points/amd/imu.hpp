@@ -285,35 +285,10 @@ inline bool deskew_point_cloud_imu(const PointCloudShared& input_cloud, PointClo
     throw_on_error(sp_imu_deskew_intervals_host(reinterpret_cast<const float*>(traj.data()), n_traj, rows.data()));
     shared_vector<float> table(input_cloud.queue);
     table.assign(rows.data(), rows.size());
-    // step 5 (:297-325): the output mirrors the input's timing and the attributes the deskew does not touch
-    const bool in_place = &input_cloud == &output_cloud;
-    const bool cov = input_cloud.has_cov(), nrm = input_cloud.has_normal();
-    if (!in_place) {
-        output_cloud.start_time_ms = input_cloud.start_time_ms;
-        output_cloud.end_time_ms = input_cloud.end_time_ms;
-        *output_cloud.timestamp_offsets = *input_cloud.timestamp_offsets;
-        if (!nrm) output_cloud.normals->clear();
-        if (!cov) output_cloud.covs->clear();
-        if (input_cloud.has_rgb()) *output_cloud.rgb = *input_cloud.rgb; else output_cloud.rgb->clear();
-        if (input_cloud.has_intensity()) *output_cloud.intensities = *input_cloud.intensities; else output_cloud.intensities->clear();
-    }
-    // step 6: the kernel
-    const float* ts = input_cloud.timestamp_offsets->device_data();
-    const float *pin, *cin = nullptr, *nin = nullptr;
-    float *pout, *cout = nullptr, *nout = nullptr;
-    if (in_place) {
-        pin = pout = reinterpret_cast<float*>(output_cloud.points->device_data_rw());
-        if (cov) cin = cout = reinterpret_cast<float*>(output_cloud.covs->device_data_rw());
-        if (nrm) nin = nout = reinterpret_cast<float*>(output_cloud.normals->device_data_rw());
-    } else {
-        pin = input_cloud.points_device();
-        cin = input_cloud.covs_device();
-        nin = input_cloud.normals_device();
-        pout = reinterpret_cast<float*>(output_cloud.points->device_data_for_write(N));  // (resize: every row is written)
-        if (cov) cout = reinterpret_cast<float*>(output_cloud.covs->device_data_for_write(N));
-        if (nrm) nout = reinterpret_cast<float*>(output_cloud.normals->device_data_for_write(N));
-    }
-    throw_on_error(sp_deskew_imu(pin, cin, nin, ts, N, table.device_data(), n_traj - 1, pout, cout, nout, input_cloud.queue.stream()));
+    // step 5 (:297-325): the output mirrors the input's timing and the attributes the deskew does not touch; step 6: the kernel
+    const sycl_points::detail::DeskewBuffers b = sycl_points::detail::prepare_deskew_output(input_cloud, output_cloud);
+    throw_on_error(sp_deskew_imu(b.points_in, b.covs_in, b.normals_in, input_cloud.timestamp_offsets->device_data(), N, table.device_data(),
+                                 n_traj - 1, b.points_out, b.covs_out, b.normals_out, input_cloud.queue.stream()));
     sycl_utils::events(input_cloud.queue.stream()).wait_and_throw();  // :413
     set_status(IMUDeskewStatus::success);
     return true;

@@ -780,6 +780,22 @@ def relative_twist(previous_pose, current_pose):
     return tw
 
 
+def _deskew_buffers(cloud):
+    """What both deskews hand their kernel: (points, stamps, covs or None, normals or None, out). `out` has fresh points,
+    covariances and normals, shares the cloud's rgb, intensities and stamps, and carries its start / end time where it has them."""
+    p = _dev_f32(cloud.points, 4)
+    ts = _dev_f32(cloud.timestamp_offsets)
+    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
+    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
+    out = PointCloudShared(torch.empty_like(p), None if covs is None else torch.empty_like(covs),
+                           None if nrm is None else torch.empty_like(nrm), cloud.rgb, cloud.intensities, cloud.timestamp_offsets,
+                           device=p.device)
+    for k in ("start_time_ms", "end_time_ms"):
+        if hasattr(cloud, k):
+            setattr(out, k, getattr(cloud, k))
+    return p, ts, covs, nrm, out
+
+
 def deskew_point_cloud_constant_velocity(cloud, previous_pose, current_pose, inter_scan_duration_seconds=-1.0):
     """deskew::deskew_point_cloud_constant_velocity (deskew/relative_pose_deskew.hpp:36-178): a new cloud with every point moved
     from the sensor frame at its time stamp (timestamp_offsets, ms) into the frame of `current_pose`, assuming constant body
@@ -794,19 +810,10 @@ def deskew_point_cloud_constant_velocity(cloud, previous_pose, current_pose, int
         duration = np.float32((float(getattr(cloud, "end_time_ms", 0.0)) - float(getattr(cloud, "start_time_ms", 0.0))) * 1e-3)
     if not duration > 0.0:
         return None
-    p = _dev_f32(cloud.points, 4)
-    ts = _dev_f32(cloud.timestamp_offsets)
-    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
-    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
-    out = PointCloudShared(torch.empty_like(p), None if covs is None else torch.empty_like(covs),
-                           None if nrm is None else torch.empty_like(nrm), cloud.rgb, cloud.intensities, cloud.timestamp_offsets,
-                           device=p.device)
+    p, ts, covs, nrm, out = _deskew_buffers(cloud)
     tw = relative_twist(previous_pose, current_pose)
     check(_lib.lib().sp_deskew_constant_velocity(_ptr(p), _ptr(covs), _ptr(nrm), _ptr(ts), n, tw.ctypes.data_as(C.c_void_p),
                                                  float(duration), _ptr(out.points), _ptr(out.covs), _ptr(out.normals), _stream()))
-    for k in ("start_time_ms", "end_time_ms"):
-        if hasattr(cloud, k):
-            setattr(out, k, getattr(cloud, k))
     return out
 
 
@@ -1007,18 +1014,10 @@ def deskew_point_cloud_imu(cloud, stamps, gyro, accel, scan_start_sec, T_imu_to_
                                          v_world, gyro_only)
     if traj is None:
         return None, status
-    p = _dev_f32(cloud.points, 4)
-    ts = _dev_f32(cloud.timestamp_offsets)
-    covs = _dev_f32(cloud.covs, 16) if cloud.has_cov() else None
-    nrm = _dev_f32(cloud.normals, 4) if cloud.has_normal() else None
+    p, ts, covs, nrm, out = _deskew_buffers(cloud)
     rows = torch.from_numpy(imu_deskew_intervals(traj)).to(p.device)  # a pageable copy: stream-ordered, returns when it is staged
-    out = PointCloudShared(torch.empty_like(p), None if covs is None else torch.empty_like(covs),
-                           None if nrm is None else torch.empty_like(nrm), cloud.rgb, cloud.intensities, cloud.timestamp_offsets,
-                           device=p.device)
     check(_lib.lib().sp_deskew_imu(_ptr(p), _ptr(covs), _ptr(nrm), _ptr(ts), n, _ptr(rows), rows.shape[0], _ptr(out.points),
                                    _ptr(out.covs), _ptr(out.normals), _stream()))
-    for k in ("start_time_ms", "end_time_ms"):
-        setattr(out, k, getattr(cloud, k))
     return out, status
 
 

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "registration_device.h"
+#include "sp_cov_normal.h"
 
 namespace sp {
 namespace {
@@ -26,23 +27,6 @@ struct PointTerm {
     float residual_norm;  // fed to the robust kernel
     float genz_weight;
 };
-
-__device__ __forceinline__ Mat3 load_cov3(const float4* __restrict__ c) {
-    const float4 c0 = c[0], c1 = c[1], c2 = c[2];
-    Mat3 C;
-    C.m[0][0] = c0.x; C.m[1][0] = c0.y; C.m[2][0] = c0.z;
-    C.m[0][1] = c1.x; C.m[1][1] = c1.y; C.m[2][1] = c1.z;
-    C.m[0][2] = c2.x; C.m[1][2] = c2.y; C.m[2][2] = c2.z;
-    return C;
-}
-__device__ __forceinline__ Mat3 identity3() {
-    Mat3 I;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) I.m[i][j] = (i == j) ? 1.0f : 0.0f;
-    return I;
-}
 
 // compute_se3_jacobian (factor.hpp:69-84): rows 0..2 of [R*skew(p) | -R]; row 3 is zero and never stored.
 __device__ __forceinline__ void se3_jacobian(const Rigid& T, float px, float py, float pz, float J[3][6]) {
@@ -160,9 +144,9 @@ __device__ __forceinline__ Corr gather(unsigned i, const float4* __restrict__ sr
     const int ti = nn_idx[i];
     c.s = src[i];
     c.t = tgt[ti];
-    if (REG == SP_REG_GICP) c.scov = scov ? load_cov3(scov + 4 * (size_t)i) : identity3();
+    if (REG == SP_REG_GICP) c.scov = scov ? load_cov(scov + 4 * (size_t)i) : identity3();
     if (REG == SP_REG_GICP || REG == SP_REG_POINT_TO_DISTRIBUTION || REG == SP_REG_GENZ)
-        c.tcov = tcov ? load_cov3(tcov + 4 * (size_t)ti) : identity3();
+        c.tcov = tcov ? load_cov(tcov + 4 * (size_t)ti) : identity3();
     if (REG == SP_REG_POINT_TO_PLANE || REG == SP_REG_GENZ)
         c.tn = tnrm ? tnrm[ti] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return c;
@@ -301,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(KParams P, float* __r
         rot.D = rot.J[0] = rot.J[1] = rot.J[2] = 0.0f;
         if (P.rot_enable) {
             const int ti = P.nn_idx[i];
-            rot = rotation_divergence<true>(T, load_cov3(P.scov + 4 * (size_t)i), load_cov3(P.tcov + 4 * (size_t)ti));
+            rot = rotation_divergence<true>(T, load_cov(P.scov + 4 * (size_t)i), load_cov(P.tcov + 4 * (size_t)ti));
             const float rn = sqrtf(0.5f * rot.D * rot.D);
             rw = P.rot_weight * robust_weight<LOSS>(rn, P.rot_scale);
             err += P.rot_weight * robust_error<LOSS>(rn, P.rot_scale);
@@ -342,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void error_kernel(KParams P, float* __restr
         if (P.rot_enable) {  // registration.hpp:758-766
             const int ti = P.nn_idx[i];
             const RotTerm rot =
-                rotation_divergence<false>(T, load_cov3(P.scov + 4 * (size_t)i), load_cov3(P.tcov + 4 * (size_t)ti));
+                rotation_divergence<false>(T, load_cov(P.scov + 4 * (size_t)i), load_cov(P.tcov + 4 * (size_t)ti));
             err += P.rot_weight * robust_error<LOSS>(sqrtf(0.5f * rot.D * rot.D), P.rot_scale);
         }
         acc[0] += err;
@@ -391,7 +375,7 @@ __global__ void genz_counts_kernel(const float4* __restrict__ tcov, const int32_
     unsigned inl = 0, pl = 0;
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         if (nn_d2[i] > max_d2) continue;
-        if (genz_planar(load_cov3(tcov + 4 * (size_t)nn_idx[i]), thr)) ++pl;
+        if (genz_planar(load_cov(tcov + 4 * (size_t)nn_idx[i]), thr)) ++pl;
         ++inl;
     }
     inl = wave_sum_u32(inl);
@@ -434,7 +418,7 @@ __global__ __launch_bounds__(kBlock) void prepare_cov_kernel(const float4* __res
     if (i >= n) return;
     // row i of the output belongs to the point whose original index is order_pts[i].w / order_idx[i] (or i itself)
     const unsigned src = order_pts ? __float_as_uint(order_pts[i].w) : (order_idx ? order_idx[i] : i);
-    const Mat3 C = load_cov3(covs + 4 * (size_t)src);
+    const Mat3 C = load_cov(covs + 4 * (size_t)src);
     const Mat3 P = P2D ? inverse(C) : plane_regularize(C);
     out[2 * (size_t)i] = make_float4(P.m[0][0], (P.m[0][1] + P.m[1][0]) * 0.5f, (P.m[0][2] + P.m[2][0]) * 0.5f, P.m[1][1]);
     // third slot of the second half-row (target side only): the point's squared safe radius (fused_point)
@@ -509,7 +493,7 @@ __global__ __launch_bounds__(kBlock) void prepare_source_kernel(const float4* __
     const float4 p = pts[src];
     out_pts[i] = p.x; out_pts[stride + i] = p.y; out_pts[2 * (size_t)stride + i] = p.z;
     if (!covs) return;  // point-to-distribution: the covariance planes are never read
-    const Mat3 P = plane_regularize(load_cov3(covs + 4 * (size_t)src));
+    const Mat3 P = plane_regularize(load_cov(covs + 4 * (size_t)src));
     out_covp[i] = P.m[0][0];
     out_covp[stride + i] = (P.m[0][1] + P.m[1][0]) * 0.5f;
     out_covp[2 * (size_t)stride + i] = (P.m[0][2] + P.m[2][0]) * 0.5f;

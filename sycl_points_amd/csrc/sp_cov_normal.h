@@ -7,14 +7,15 @@
 
 namespace sp {
 
-__device__ __forceinline__ Mat3 load_cov(const float4* __restrict__ in) {
-    const float4 c0 = in[0], c1 = in[1], c2 = in[2];
+// the 3x3 block of a stored covariance's first three columns (column-major storage: C(i, k) is component i of column k)
+__device__ __forceinline__ Mat3 cov_of_columns(const float4 c0, const float4 c1, const float4 c2) {
     Mat3 C;
     C.m[0][0] = c0.x; C.m[1][0] = c0.y; C.m[2][0] = c0.z;
     C.m[0][1] = c1.x; C.m[1][1] = c1.y; C.m[2][1] = c1.z;
     C.m[0][2] = c2.x; C.m[1][2] = c2.y; C.m[2][2] = c2.z;
     return C;
 }
+__device__ __forceinline__ Mat3 load_cov(const float4* __restrict__ in) { return cov_of_columns(in[0], in[1], in[2]); }
 
 __device__ __forceinline__ void store_cov(float4* __restrict__ out, const Mat3& C) {
     out[0] = make_float4(C.m[0][0], C.m[1][0], C.m[2][0], 0.0f);  // column 0

@@ -193,6 +193,42 @@ static void in_place_returns_rotated_attributes() {
     CHECK(inplace.has_timestamps() && inplace.size() == 5000);
 }
 
+// The output side of the call, which the IMU deskew shares: out of place, an output cloud that held other rows and attributes
+// ends up with the input's rgb, stamps and times and without the attributes the input does not have; in place leaves them alone
+static void output_takes_the_attributes_the_deskew_does_not_touch() {
+    PointCloudShared cloud(*Q);
+    for (int i = 0; i < 8; ++i) {
+        cloud.points->push_back(PointType(float(i), 1.0f, 2.0f, 1.0f));
+        cloud.rgb->push_back(RGBType(0.125f * float(i), 0.5f, 0.25f, 1.0f));
+        cloud.timestamp_offsets->push_back(12.5f * float(i));
+    }
+    cloud.start_time_ms = 1000.0;
+    cloud.end_time_ms = 1100.0;
+    PointCloudShared out(*Q);
+    for (int i = 0; i < 5; ++i) {
+        out.points->push_back(PointType(0, 0, 0, 1));
+        out.normals->push_back(Normal(0, 0, 1, 0));
+        out.covs->push_back(Covariance::Zero());
+        out.rgb->push_back(RGBType(1, 1, 1, 1));
+        out.intensities->push_back(7.0f);
+    }
+    const std::vector<RGBType, Eigen::aligned_allocator<RGBType>> rgb(cloud.rgb->host().begin(), cloud.rgb->host().end());
+    const std::vector<float> stamps(cloud.timestamp_offsets->host().begin(), cloud.timestamp_offsets->host().end());
+    auto untouched = [&](const PointCloudShared& c) {
+        return c.size() == 8 && c.normals->empty() && c.covs->empty() && c.intensities->empty() && c.rgb->size() == 8 &&
+               c.timestamp_offsets->size() == 8 && std::memcmp(c.rgb->host().data(), rgb.data(), 8 * sizeof(RGBType)) == 0 &&
+               std::memcmp(c.timestamp_offsets->host().data(), stamps.data(), 8 * sizeof(float)) == 0 && c.start_time_ms == 1000.0 &&
+               c.end_time_ms == 1100.0;
+    };
+    const double a[6] = {0.02, -0.03, 0.05, 1.0, 0.5, -0.2};
+    const Eigen::Isometry3f prev = Eigen::Isometry3f::Identity(), cur = to_iso(exp64(a));
+    CHECK(alg::deskew::deskew_point_cloud_constant_velocity(cloud, out, prev, cur, 0.1f));
+    CHECK(untouched(out));
+    CHECK(alg::deskew::deskew_point_cloud_constant_velocity(cloud, cloud, prev, cur, 0.1f));
+    CHECK(untouched(cloud));
+    CHECK(same_bytes(cloud.points->host().data(), out.points->host().data(), 8 * sizeof(PointType)));
+}
+
 // ------------------------------------------------------------------------------------------------ RegistrationPipelineTest
 namespace {
 class DummyKNN : public alg::knn::KNNBase {  // test_registration_pipeline.cpp:16-23
@@ -558,6 +594,7 @@ int main() {
     RUN(deskews_points_with_constant_velocity);
     RUN(handles_non_positive_scan_duration);
     RUN(in_place_returns_rotated_attributes);
+    RUN(output_takes_the_attributes_the_deskew_does_not_touch);
     RUN(accessors_return_null_before_align);
     RUN(velocity_update_aligner_exposes_most_recent_deskewed_point_cloud);
     RUN(velocity_update_aligner_falls_back_without_timestamps);

@@ -423,6 +423,43 @@ static void normals_and_covariances_rotated_also_in_place() {
         CHECK(std::memcmp((*cloud.normals)[i].data(), (*out.normals)[i].data(), 16) == 0);
     }
 }
+// The output side of the call, which the constant-velocity deskew shares: out of place, an output cloud that held other rows and
+// attributes ends up with the input's rgb, stamps and times and without the attributes the input does not have; in place leaves
+// them alone
+static void output_takes_the_attributes_the_deskew_does_not_touch() {
+    PointCloudShared cloud(*Q);
+    for (int i = 0; i < 8; ++i) {
+        cloud.points->push_back(PointType(float(i), 1.0f, 2.0f, 1.0f));
+        cloud.rgb->push_back(RGBType(0.125f * float(i), 0.5f, 0.25f, 1.0f));
+        cloud.timestamp_offsets->push_back(12.5f * float(i));
+    }
+    cloud.start_time_ms = 1000.0;
+    cloud.end_time_ms = 1100.0;
+    PointCloudShared out(*Q);
+    for (int i = 0; i < 5; ++i) {
+        out.points->push_back(PointType(0, 0, 0, 1));
+        out.normals->push_back(Normal(0, 0, 1, 0));
+        out.covs->push_back(Covariance::Zero());
+        out.rgb->push_back(RGBType(1, 1, 1, 1));
+        out.intensities->push_back(7.0f);
+    }
+    const std::vector<RGBType, Eigen::aligned_allocator<RGBType>> rgb(cloud.rgb->host().begin(), cloud.rgb->host().end());
+    const std::vector<float> stamps(cloud.timestamp_offsets->host().begin(), cloud.timestamp_offsets->host().end());
+    auto untouched = [&](const PointCloudShared& c) {
+        return c.size() == 8 && c.normals->empty() && c.covs->empty() && c.intensities->empty() && c.rgb->size() == 8 &&
+               c.timestamp_offsets->size() == 8 && std::memcmp(c.rgb->host().data(), rgb.data(), 8 * sizeof(RGBType)) == 0 &&
+               std::memcmp(c.timestamp_offsets->host().data(), stamps.data(), 8 * sizeof(float)) == 0 && c.start_time_ms == 1000.0 &&
+               c.end_time_ms == 1100.0;
+    };
+    const auto buf = make_imu_buffer(1.0 - 0.02, 0.14, 24, V3(0, 0, kPi / 2.0f), V3::Zero());
+    CHECK(dsk::deskew_point_cloud_imu(cloud, out, buf, 1.0, Eigen::Isometry3f::Identity(), imu::IMUBias(), no_gravity(), M3::Identity(),
+                                      V3::Zero()));
+    CHECK(untouched(out));
+    CHECK(dsk::deskew_point_cloud_imu(cloud, cloud, buf, 1.0, Eigen::Isometry3f::Identity(), imu::IMUBias(), no_gravity(), M3::Identity(),
+                                      V3::Zero()));
+    CHECK(untouched(cloud));
+    CHECK(std::memcmp(cloud.points->host().data(), out.points->host().data(), 8 * sizeof(PointType)) == 0);
+}
 static void matches_constant_velocity_approximately() {
     const float omega_z = kPi / 4.0f;
     TransformMatrix end = TransformMatrix::Identity();
@@ -463,6 +500,7 @@ int main() {
     RUN(gyro_only_ignores_acceleration_and_velocity);
     RUN(status_cases);
     RUN(normals_and_covariances_rotated_also_in_place);
+    RUN(output_takes_the_attributes_the_deskew_does_not_touch);
     RUN(matches_constant_velocity_approximately);
     std::printf("%d checks, %d failed\n", g_checks, g_failed);
     return g_failed == 0 ? 0 : 1;
