@@ -11,6 +11,44 @@ namespace sycl_points {
 namespace algorithms {
 namespace mapping {
 
+namespace detail {
+
+/// The averaged export of either map (sp_vhm_downsampling, sp_ogm_extract_occupied_points: one shape): `result`'s device arrays sized
+/// for the map's voxels, written by the entry point, cut to the rows that came out; an attribute the map does not hold is cleared.
+static_assert(+SP_VHM_INFO_VOXEL_NUM == +SP_OGM_INFO_VOXEL_NUM && +SP_VHM_INFO_HAS_COV == +SP_OGM_INFO_HAS_COV &&
+              +SP_VHM_INFO_HAS_RGB == +SP_OGM_INFO_HAS_RGB && +SP_VHM_INFO_HAS_INTENSITY == +SP_OGM_INFO_HAS_INTENSITY);
+template <class Handle>
+void mean_rows(int (*entry_point)(Handle*, const float*, float, float*, float*, float*, float*, uint64_t*, size_t, size_t*, void*),
+               size_t (*info)(const Handle*, int), Handle* h, const float (&xyz)[3], const float distance, PointCloudShared& result,
+               void* stream) {
+    const size_t cap = info(h, SP_VHM_INFO_VOXEL_NUM);
+    if (cap == 0) { result.clear(); return; }
+    const bool has_cov = info(h, SP_VHM_INFO_HAS_COV), has_rgb = info(h, SP_VHM_INFO_HAS_RGB), has_int = info(h, SP_VHM_INFO_HAS_INTENSITY);
+    size_t n = 0;
+    throw_on_error(entry_point(h, xyz, distance, reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
+                               has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
+                               has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
+                               has_int ? result.intensities->device_data_for_write(cap) : nullptr, nullptr, cap, &n, stream));
+    result.points->set_device_size(n);
+    if (has_cov) result.covs->set_device_size(n); else result.covs->clear();
+    if (has_rgb) result.rgb->set_device_size(n); else result.rgb->clear();
+    if (has_int) result.intensities->set_device_size(n); else result.intensities->clear();
+    result.normals->clear();
+    result.timestamp_offsets->clear();
+}
+
+/// compute_overlap_ratio of either map over its sp_*_overlap_ratio entry point
+template <class Handle>
+float overlap_ratio(int (*entry_point)(const Handle*, const float*, size_t, const float*, float*, void*), const Handle* h,
+                    const PointCloudShared& cloud, const Eigen::Isometry3f& sensor_pose, void* stream) {
+    if (!cloud.points || cloud.points->empty()) return 0.0f;
+    float r = 0.0f;
+    throw_on_error(entry_point(h, cloud.points_device(), cloud.size(), sensor_pose.matrix().data(), &r, stream));
+    return r;
+}
+
+}  // namespace detail
+
 class VoxelHashMap {
 public:
     using Ptr = std::shared_ptr<VoxelHashMap>;
@@ -48,32 +86,13 @@ public:
 
     /// voxel_hash_map.hpp:146-190 — voxel means whose centroid lies in the box center +- distance.
     void downsampling(PointCloudShared& result, const Eigen::Vector3f& center, const float distance = 100.0f) {
-        const size_t cap = sp_vhm_info(h_, SP_VHM_INFO_VOXEL_NUM);
-        if (cap == 0) { result.clear(); return; }
-        const bool has_cov = sp_vhm_info(h_, SP_VHM_INFO_HAS_COV), has_rgb = sp_vhm_info(h_, SP_VHM_INFO_HAS_RGB),
-                   has_int = sp_vhm_info(h_, SP_VHM_INFO_HAS_INTENSITY);
         const float c[3] = {center.x(), center.y(), center.z()};
-        size_t n = 0;
-        throw_on_error(sp_vhm_downsampling(
-            h_, c, distance, reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
-            has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
-            has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
-            has_int ? result.intensities->device_data_for_write(cap) : nullptr, nullptr, cap, &n, queue_.stream()));
-        result.points->set_device_size(n);
-        if (has_cov) result.covs->set_device_size(n); else result.covs->clear();
-        if (has_rgb) result.rgb->set_device_size(n); else result.rgb->clear();
-        if (has_int) result.intensities->set_device_size(n); else result.intensities->clear();
-        result.normals->clear();
-        result.timestamp_offsets->clear();
+        detail::mean_rows(sp_vhm_downsampling, sp_vhm_info, h_, c, distance, result, queue_.stream());
     }
 
     /// voxel_hash_map.hpp:196-246
     float compute_overlap_ratio(const PointCloudShared& cloud, const Eigen::Isometry3f& sensor_pose) const {
-        if (!cloud.points || cloud.points->empty()) return 0.0f;
-        float r = 0.0f;
-        throw_on_error(sp_vhm_overlap_ratio(h_, cloud.points_device(), cloud.size(), sensor_pose.matrix().data(), &r,
-                                            queue_.stream()));
-        return r;
+        return detail::overlap_ratio(sp_vhm_overlap_ratio, h_, cloud, sensor_pose, queue_.stream());
     }
 
     void remove_old_data() { throw_on_error(sp_vhm_remove_old_data(h_, queue_.stream())); }
@@ -137,33 +156,14 @@ public:
     /// occupancy_grid_map.hpp:169-181 — occupied voxels within max_distance (L-infinity) of the sensor, in table-slot order.
     void extract_occupied_points(PointCloudShared& result, const Eigen::Isometry3f& sensor_pose,
                                  const float max_distance = 100.0f) const {
-        const size_t cap = sp_ogm_info(h_, SP_OGM_INFO_VOXEL_NUM);
-        if (cap == 0) { result.clear(); return; }
-        const bool has_cov = sp_ogm_info(h_, SP_OGM_INFO_HAS_COV), has_rgb = sp_ogm_info(h_, SP_OGM_INFO_HAS_RGB),
-                   has_int = sp_ogm_info(h_, SP_OGM_INFO_HAS_INTENSITY);
         const Eigen::Vector3f t = sensor_pose.translation();
         const float c[3] = {t.x(), t.y(), t.z()};
-        size_t n = 0;
-        throw_on_error(sp_ogm_extract_occupied_points(
-            h_, c, max_distance, reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
-            has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
-            has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
-            has_int ? result.intensities->device_data_for_write(cap) : nullptr, nullptr, cap, &n, queue_.stream()));
-        result.points->set_device_size(n);
-        if (has_cov) result.covs->set_device_size(n); else result.covs->clear();
-        if (has_rgb) result.rgb->set_device_size(n); else result.rgb->clear();
-        if (has_int) result.intensities->set_device_size(n); else result.intensities->clear();
-        result.normals->clear();
-        result.timestamp_offsets->clear();
+        detail::mean_rows(sp_ogm_extract_occupied_points, sp_ogm_info, h_, c, max_distance, result, queue_.stream());
     }
 
     /// occupancy_grid_map.hpp:417-472
     float compute_overlap_ratio(const PointCloudShared& cloud, const Eigen::Isometry3f& sensor_pose) const {
-        if (!cloud.points || cloud.points->empty()) return 0.0f;
-        float r = 0.0f;
-        throw_on_error(sp_ogm_overlap_ratio(h_, cloud.points_device(), cloud.size(), sensor_pose.matrix().data(), &r,
-                                            queue_.stream()));
-        return r;
+        return detail::overlap_ratio(sp_ogm_overlap_ratio, h_, cloud, sensor_pose, queue_.stream());
     }
 
 private:

@@ -1295,35 +1295,83 @@ class Exchange:
             pass
 
 
-class VoxelHashMap:
-    """algorithms/mapping/voxel_hash_map.hpp:22-250 over the sp_vhm_* entry points: submap accumulation in HBM.
-    add_point_cloud takes a PointCloudShared in the sensor frame and the sensor pose (4x4, map frame); downsampling
-    returns a PointCloudShared of the voxel means inside the query box (plus `.voxel_keys`, the keys in output order)."""
-    _PARAM = {"voxel_size": 0, "max_staleness": 1, "remove_old_data_cycle": 2, "rehash_threshold": 3, "min_num_point": 4}
-    _INFO = {"voxel_num": 0, "capacity": 1, "staleness_counter": 2, "has_cov": 3, "has_rgb": 4, "has_intensity": 5}
+class _HashedVoxelMap:
+    """What VoxelHashMap and OccupancyGridMap share: the handle of an sp_vhm_* / sp_ogm_* object (the entry points differ only in
+    the prefix), settings and infos by name, clear, add_point_cloud, compute_overlap_ratio and the averaged export."""
+    _PREFIX = _PARAM = _INFO = None
 
     def __init__(self, voxel_size, device="cuda"):
         self.device = torch.device(device)
         h = C.c_void_p()
-        check(_lib.lib().sp_vhm_create(float(voxel_size), _stream(), C.byref(h)))
+        check(self._fn("create")(float(voxel_size), _stream(), C.byref(h)))
         self._h = h
 
     def __del__(self):
         try:
             if self._h:
-                _lib.lib().sp_vhm_destroy(self._h)
+                self._fn("destroy")(self._h)
                 self._h = None
         except Exception:
             pass
 
+    def _fn(self, name):
+        return getattr(_lib.lib(), f"{self._PREFIX}_{name}")
+
     def _set(self, name, value):
-        check(_lib.lib().sp_vhm_set(self._h, self._PARAM[name], float(value)))
+        check(self._fn("set")(self._h, self._PARAM[name], float(value)))
 
     def _get(self, name):
-        return float(_lib.lib().sp_vhm_get(self._h, self._PARAM[name]))
+        return float(self._fn("get")(self._h, self._PARAM[name]))
 
     def info(self, name):
-        return int(_lib.lib().sp_vhm_info(self._h, self._INFO[name]))
+        return int(self._fn("info")(self._h, self._INFO[name]))
+
+    def clear(self):
+        check(self._fn("clear")(self._h, _stream()))
+
+    def add_point_cloud(self, cloud, sensor_pose=None):
+        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
+        n = cloud.size()
+        check(self._fn("add_point_cloud")(
+            self._h, _ptr(cloud.points) if n else None, _ptr(cloud.covs) if (n and cloud.has_cov()) else None,
+            _ptr(cloud.rgb) if (n and cloud.has_rgb()) else None,
+            _ptr(cloud.intensities) if (n and cloud.has_intensity()) else None, n, T.ctypes.data_as(C.c_void_p), _stream()))
+
+    def compute_overlap_ratio(self, cloud, sensor_pose=None):
+        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
+        r = C.c_float(0.0)
+        n = cloud.size()
+        check(self._fn("overlap_ratio")(self._h, _ptr(cloud.points) if n else None, n, T.ctypes.data_as(C.c_void_p), C.byref(r),
+                                        _stream()))
+        return float(r.value)
+
+    def _mean_rows(self, entry_point, xyz3, distance):
+        """the voxel means `entry_point` keeps around xyz3, as a PointCloudShared, and their keys in the same order"""
+        cap = self.info("voxel_num")
+        dev = self.device
+        rows = max(cap, 1)
+        pts = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        covs = torch.empty((rows, 16), dtype=torch.float32, device=dev) if self.info("has_cov") else None
+        rgb = torch.empty((rows, 4), dtype=torch.float32, device=dev) if self.info("has_rgb") else None
+        inten = torch.empty(rows, dtype=torch.float32, device=dev) if self.info("has_intensity") else None
+        keys = torch.empty(rows, dtype=torch.int64, device=dev)
+        c = np.ascontiguousarray(xyz3, np.float32).copy()
+        n_out = C.c_size_t(0)
+        check(self._fn(entry_point)(self._h, c.ctypes.data_as(C.c_void_p), float(distance), _ptr(pts), _ptr(covs), _ptr(rgb),
+                                    _ptr(inten), _ptr(keys), cap, C.byref(n_out), _stream()))
+        n = n_out.value
+        out = PointCloudShared(pts[:n], covs=None if covs is None else covs[:n], rgb=None if rgb is None else rgb[:n],
+                               intensities=None if inten is None else inten[:n], device=dev)
+        return out, keys[:n]
+
+
+class VoxelHashMap(_HashedVoxelMap):
+    """algorithms/mapping/voxel_hash_map.hpp:22-250 over the sp_vhm_* entry points: submap accumulation in HBM.
+    add_point_cloud takes a PointCloudShared in the sensor frame and the sensor pose (4x4, map frame); downsampling
+    returns a PointCloudShared of the voxel means inside the query box (plus `.voxel_keys`, the keys in output order)."""
+    _PREFIX = "sp_vhm"
+    _PARAM = {"voxel_size": 0, "max_staleness": 1, "remove_old_data_cycle": 2, "rehash_threshold": 3, "min_num_point": 4}
+    _INFO = {"voxel_num": 0, "capacity": 1, "staleness_counter": 2, "has_cov": 3, "has_rgb": 4, "has_intensity": 5}
 
     def set_voxel_size(self, v): self._set("voxel_size", v)  # noqa: E704
     def get_voxel_size(self): return self._get("voxel_size")  # noqa: E704
@@ -1336,79 +1384,25 @@ class VoxelHashMap:
     def set_min_num_point(self, v): self._set("min_num_point", v)  # noqa: E704
     def get_min_num_point(self): return int(self._get("min_num_point"))  # noqa: E704
 
-    def clear(self):
-        check(_lib.lib().sp_vhm_clear(self._h, _stream()))
-
-    def add_point_cloud(self, cloud, sensor_pose=None):
-        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
-        n = cloud.size()
-        check(_lib.lib().sp_vhm_add_point_cloud(
-            self._h, _ptr(cloud.points) if n else None, _ptr(cloud.covs) if (n and cloud.has_cov()) else None,
-            _ptr(cloud.rgb) if (n and cloud.has_rgb()) else None,
-            _ptr(cloud.intensities) if (n and cloud.has_intensity()) else None, n, T.ctypes.data_as(C.c_void_p), _stream()))
-
     def downsampling(self, center=(0.0, 0.0, 0.0), distance=100.0):
-        cap = self.info("voxel_num")
-        dev = self.device
-        pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-        covs = torch.empty((max(cap, 1), 16), dtype=torch.float32, device=dev) if self.info("has_cov") else None
-        rgb = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev) if self.info("has_rgb") else None
-        inten = torch.empty(max(cap, 1), dtype=torch.float32, device=dev) if self.info("has_intensity") else None
-        keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-        c = np.asarray(center, np.float32).copy()
-        n_out = C.c_size_t(0)
-        check(_lib.lib().sp_vhm_downsampling(self._h, c.ctypes.data_as(C.c_void_p), float(distance), _ptr(pts), _ptr(covs),
-                                             _ptr(rgb), _ptr(inten), _ptr(keys), cap, C.byref(n_out), _stream()))
-        n = n_out.value
-        out = PointCloudShared(pts[:n], covs=None if covs is None else covs[:n], rgb=None if rgb is None else rgb[:n],
-                               intensities=None if inten is None else inten[:n], device=dev)
-        out.voxel_keys = keys[:n]
+        out, keys = self._mean_rows("downsampling", center, distance)
+        out.voxel_keys = keys
         return out
-
-    def compute_overlap_ratio(self, cloud, sensor_pose=None):
-        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
-        r = C.c_float(0.0)
-        n = cloud.size()
-        check(_lib.lib().sp_vhm_overlap_ratio(self._h, _ptr(cloud.points) if n else None, n, T.ctypes.data_as(C.c_void_p),
-                                              C.byref(r), _stream()))
-        return float(r.value)
 
     def remove_old_data(self):
         check(_lib.lib().sp_vhm_remove_old_data(self._h, _stream()))
 
 
-class OccupancyGridMap:
+class OccupancyGridMap(_HashedVoxelMap):
     """algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 over the sp_ogm_* entry points: the log-odds submap in HBM, with
     free-space carving along the rays from the sensor. add_point_cloud takes a PointCloudShared in the sensor frame and the sensor
     pose (4x4, map frame); extract_occupied_points returns a PointCloudShared of the occupied voxels' means (plus `.keys`, the voxel
     keys in output order: rows are in table-slot order, align them by key). extract_visible_points is not provided."""
+    _PREFIX = "sp_ogm"
     _PARAM = {"voxel_size": 0, "log_odds_hit": 1, "log_odds_miss": 2, "log_odds_min": 3, "log_odds_max": 4,
               "occupancy_threshold": 5, "free_space_updates_enabled": 6, "voxel_pruning_enabled": 7, "stale_frame_threshold": 8,
               "rehash_threshold": 9}
     _INFO = {"voxel_num": 0, "capacity": 1, "frame_index": 2, "has_cov": 3, "has_rgb": 4, "has_intensity": 5}
-
-    def __init__(self, voxel_size, device="cuda"):
-        self.device = torch.device(device)
-        h = C.c_void_p()
-        check(_lib.lib().sp_ogm_create(float(voxel_size), _stream(), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().sp_ogm_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def _set(self, name, value):
-        check(_lib.lib().sp_ogm_set(self._h, self._PARAM[name], float(value)))
-
-    def _get(self, name):
-        return float(_lib.lib().sp_ogm_get(self._h, self._PARAM[name]))
-
-    def info(self, name):
-        return int(_lib.lib().sp_ogm_info(self._h, self._INFO[name]))
 
     def set_voxel_size(self, v): self._set("voxel_size", v)  # noqa: E704
     def voxel_size(self): return self._get("voxel_size")  # noqa: E704
@@ -1427,45 +1421,11 @@ class OccupancyGridMap:
         """the value of a setting by name (occupancy_threshold as a probability)"""
         return self._get(name)
 
-    def clear(self):
-        check(_lib.lib().sp_ogm_clear(self._h, _stream()))
-
-    def add_point_cloud(self, cloud, sensor_pose=None):
-        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
-        n = cloud.size()
-        check(_lib.lib().sp_ogm_add_point_cloud(
-            self._h, _ptr(cloud.points) if n else None, _ptr(cloud.covs) if (n and cloud.has_cov()) else None,
-            _ptr(cloud.rgb) if (n and cloud.has_rgb()) else None,
-            _ptr(cloud.intensities) if (n and cloud.has_intensity()) else None, n, T.ctypes.data_as(C.c_void_p), _stream()))
-
     def extract_occupied_points(self, sensor_pose=None, max_distance=100.0):
-        cap = self.info("voxel_num")
-        dev = self.device
-        rows = max(cap, 1)
-        pts = torch.empty((rows, 4), dtype=torch.float32, device=dev)
-        covs = torch.empty((rows, 16), dtype=torch.float32, device=dev) if self.info("has_cov") else None
-        rgb = torch.empty((rows, 4), dtype=torch.float32, device=dev) if self.info("has_rgb") else None
-        inten = torch.empty(rows, dtype=torch.float32, device=dev) if self.info("has_intensity") else None
-        keys = torch.empty(rows, dtype=torch.int64, device=dev)
         T = np.asarray(identity() if sensor_pose is None else sensor_pose, np.float32).reshape(4, 4)
-        c = np.ascontiguousarray(T[:3, 3]).copy()
-        n_out = C.c_size_t(0)
-        check(_lib.lib().sp_ogm_extract_occupied_points(self._h, c.ctypes.data_as(C.c_void_p), float(max_distance), _ptr(pts),
-                                                        _ptr(covs), _ptr(rgb), _ptr(inten), _ptr(keys), cap, C.byref(n_out),
-                                                        _stream()))
-        n = n_out.value
-        out = PointCloudShared(pts[:n], covs=None if covs is None else covs[:n], rgb=None if rgb is None else rgb[:n],
-                               intensities=None if inten is None else inten[:n], device=dev)
-        out.keys = keys[:n]
+        out, keys = self._mean_rows("extract_occupied_points", T[:3, 3], max_distance)
+        out.keys = keys
         return out
-
-    def compute_overlap_ratio(self, cloud, sensor_pose=None):
-        T = _T16(identity() if sensor_pose is None else sensor_pose).copy()
-        r = C.c_float(0.0)
-        n = cloud.size()
-        check(_lib.lib().sp_ogm_overlap_ratio(self._h, _ptr(cloud.points) if n else None, n, T.ctypes.data_as(C.c_void_p),
-                                              C.byref(r), _stream()))
-        return float(r.value)
 
     def voxel_probability(self, position):
         p = np.asarray(position, np.float32).reshape(-1)[:3].copy()

@@ -1,9 +1,9 @@
 // OccupancyGridMap for gfx950 — the log-odds submap of Submap::build_submap (replaces mapping/occupancy_grid_map.hpp:27-190, 417-472,
 // 482-1687 but extract_visible_points).
 //
-// The table is VoxelHashMap's (sp_voxel_table.h: key, double hashing, capacity ladder) with 128 probes and a `deleted` key for pruned
-// slots: six parallel arrays in HBM (key u64 | core 32 B {sum xyz, log_odds, hit_count, miss_count, and the part of either count
-// already applied to log_odds} | log-covariance sums 24 B | colour sums 16 B | intensity sum | frame of the last update).
+// The table is sp_voxel_table.h's, as VoxelHashMap's, with 128 probes, a `deleted` key for pruned slots and a 32-byte core {sum xyz,
+// log_odds, hit_count, miss_count, and the part of either count already applied to log_odds}; the host state, the compaction
+// scratch and the overlap kernel are there too.
 // add_point_cloud is the reference's five steps: [rehash] -> hits, one lane per point -> carving, one lane per ray -> apply -> prune.
 // Where this differs from the reference, on purpose:
 //   * the ray walk is a counted loop of exactly |dix| + |diy| + |diz| steps in which an axis that has reached the target's cell no
@@ -19,10 +19,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "radix_sort.h"
 #include "sp_voxel_table.h"
-
-void sp_set_error(const char* msg);
 
 namespace sp {
 namespace {
@@ -30,7 +27,6 @@ namespace {
 constexpr uint64_t kDeletedKey = ~0ull - 1;  // VoxelConstants::deleted_coord
 constexpr unsigned kOgmMaxProbe = 128;       // occupancy_grid_map.hpp:1679
 constexpr int kCellOffset = 1 << 20, kCellMask = (1 << 21) - 1;
-constexpr unsigned long long kNoSlot = ~0ull;
 
 struct OgmCore {  // 32 bytes
     float sx, sy, sz, log_odds;
@@ -38,15 +34,7 @@ struct OgmCore {  // 32 bytes
     uint32_t hits_applied, misses_applied; // the part of the totals log_odds already holds
 };
 
-struct OgmTable {
-    uint64_t* key;
-    OgmCore* core;
-    CovSum* cov;
-    float4* color;
-    float* intensity;
-    uint32_t* last_update;
-    unsigned long long capacity;
-};
+using OgmTable = VoxelTable<OgmCore>;
 
 __device__ __forceinline__ bool live(uint64_t k) { return k != kInvalidKey && k != kDeletedKey; }
 
@@ -60,6 +48,7 @@ __device__ __forceinline__ uint64_t cell_key(int x, int y, int z) {
 // The slot search of global_reduction (:795-818): the first free or pruned slot is claimed with one compare-and-swap; a swap that
 // loses to the same key uses that slot, one that loses to another key moves on with the probe loop. Never more than kOgmMaxProbe
 // probes and never a second swap on one slot; an entry that finds no slot is dropped, as in the reference.
+// Not VoxelHashMap's insert(), on purpose: this one loads first, probes 128 times and reuses `deleted` slots.
 __device__ __forceinline__ unsigned long long find_or_claim(const OgmTable& t, uint64_t h, unsigned* __restrict__ voxel_num) {
     for (unsigned p = 0; p < kOgmMaxProbe; ++p) {
         const unsigned long long s = slot_id(h, p, t.capacity);
@@ -73,21 +62,6 @@ __device__ __forceinline__ unsigned long long find_or_claim(const OgmTable& t, u
         if (seen == h) return s;
     }
     return kNoSlot;
-}
-
-// the lookup of find_voxel / compute_overlap_ratio (:591-609, 448-465)
-__device__ __forceinline__ unsigned long long find_slot(const OgmTable& t, uint64_t h) {
-    for (unsigned p = 0; p < kOgmMaxProbe; ++p) {
-        const unsigned long long s = slot_id(h, p, t.capacity);
-        const uint64_t k = t.key[s];
-        if (k == h) return s;
-        if (k == kInvalidKey) return kNoSlot;
-    }
-    return kNoSlot;
-}
-
-__device__ __forceinline__ void stamp(const OgmTable& t, unsigned long long s, uint32_t frame) {
-    __hip_atomic_store(t.last_update + s, frame, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // :806, 815
 }
 
 // integrate_points (:1072-1233): load_entry + global_reduction, one lane per point. The reference's work-group pre-combination of
@@ -111,19 +85,10 @@ __global__ __launch_bounds__(kBlock) void ogm_hit_kernel(OgmTable t, const float
         fadd(&c->sy, wy);
         fadd(&c->sz, wz);
         atomicAdd(&c->hit_count, 1u);
-        if (map_has_cov && covs) {
-            const CovSum cv = encode_cov(covs + 4 * (size_t)i, T);
-            float* d = reinterpret_cast<float*>(t.cov + s);
-            fadd(d + 0, cv.xx); fadd(d + 1, cv.xy); fadd(d + 2, cv.xz);
-            fadd(d + 3, cv.yy); fadd(d + 4, cv.yz); fadd(d + 5, cv.zz);
-        }
-        if (map_has_rgb && rgb) {
-            const float4 col = rgb[i];
-            float* d = reinterpret_cast<float*>(t.color + s);
-            fadd(d + 0, col.x); fadd(d + 1, col.y); fadd(d + 2, col.z); fadd(d + 3, col.w);
-        }
+        if (map_has_cov && covs) add_cov_sums(t, s, encode_cov(covs + 4 * (size_t)i, T));
+        if (map_has_rgb && rgb) add_color_sums(t, s, rgb[i]);
         if (map_has_intensity && inten) fadd(t.intensity + s, inten[i]);
-        stamp(t, s, frame);
+        stamp(t, s, frame);  // :806, 815
     }
 }
 
@@ -265,7 +230,8 @@ __global__ __launch_bounds__(kBlock) void ogm_prune_kernel(OgmTable t, uint32_t 
     atomicAdd(voxel_num, 1u);
 }
 
-// rehash (:652-782): every live slot re-enters the new table through free slots only
+// rehash (:652-782): every live slot re-enters the new table through free slots only: claimed once, then copied.
+// Not VoxelHashMap's rehash kernel, on purpose: that one merges entries with atomic adds, which a table with tombstones never needs.
 __global__ __launch_bounds__(kBlock) void ogm_rehash_kernel(OgmTable old_t, OgmTable new_t, bool has_cov, bool has_rgb,
                                                             bool has_intensity, unsigned* __restrict__ voxel_num) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
@@ -286,7 +252,8 @@ __global__ __launch_bounds__(kBlock) void ogm_rehash_kernel(OgmTable old_t, OgmT
     }
 }
 
-// flags for the two compactions: every live slot (export), or the occupied voxels near the sensor (:1568-1589)
+// flags for the two compactions: every live slot (export), or the occupied voxels near the sensor (:1568-1589).
+// Each map's flag kernel tests its own condition: not shared.
 __global__ __launch_bounds__(kBlock) void ogm_flag_kernel(OgmTable t, bool occupied_only, float threshold, float sx, float sy,
                                                           float sz, float max_dist, unsigned* __restrict__ flags) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
@@ -305,24 +272,13 @@ __global__ __launch_bounds__(kBlock) void ogm_flag_kernel(OgmTable t, bool occup
 }
 
 __global__ __launch_bounds__(kBlock) void ogm_extract_kernel(OgmTable t, const unsigned* __restrict__ flags,
-                                                             const unsigned* __restrict__ pos, unsigned out_capacity,
-                                                             float4* __restrict__ pts_out, float4* __restrict__ cov_out,
-                                                             float4* __restrict__ rgb_out, float* __restrict__ inten_out,
-                                                             uint64_t* __restrict__ keys_out) {
+                                                             const unsigned* __restrict__ pos, unsigned out_capacity, MeanRows out) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= t.capacity || !flags[i]) return;
     const unsigned o = pos[i];
     if (o >= out_capacity) return;
     const OgmCore c = t.core[i];
-    const float inv = 1.0f / (float)c.hit_count;
-    pts_out[o] = make_float4(c.sx * inv, c.sy * inv, c.sz * inv, 1.0f);
-    if (cov_out) decode_cov(t.cov[i], inv, cov_out + 4 * (size_t)o);
-    if (rgb_out) {
-        const float4 k = t.color[i];
-        rgb_out[o] = make_float4(k.x * inv, k.y * inv, k.z * inv, k.w * inv);
-    }
-    if (inten_out) inten_out[o] = t.intensity[i] * inv;
-    if (keys_out) keys_out[o] = t.key[i];
+    write_mean_row(t, i, o, c.hit_count, c.sx, c.sy, c.sz, out);
 }
 
 __global__ __launch_bounds__(kBlock) void ogm_export_kernel(OgmTable t, const unsigned* __restrict__ flags,
@@ -356,155 +312,50 @@ __global__ __launch_bounds__(kBlock) void ogm_export_kernel(OgmTable t, const un
     if (inten) inten[o] = t.intensity[i];
 }
 
-// compute_overlap_ratio (:417-472)
-__global__ __launch_bounds__(kBlock) void ogm_overlap_kernel(OgmTable t, const float4* __restrict__ pts, unsigned n, Mat4Arg pose,
-                                                             float inv, float threshold, unsigned* __restrict__ hits) {
-    const Rigid T = load_rigid_colmajor(pose.m);
-    unsigned mine = 0;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        const float4 p = pts[i];
-        float wx, wy, wz;
-        transform_point(T, p.x, p.y, p.z, wx, wy, wz);
-        const uint64_t h = voxel_key3(wx, wy, wz, inv);
-        if (h == kInvalidKey) continue;
-        const unsigned long long s = find_slot(t, h);
-        if (s == kNoSlot) continue;
-        const OgmCore c = t.core[s];
-        if (c.hit_count > 0u && !(c.log_odds < threshold)) ++mine;
-    }
-    mine = wave_sum_u32(mine);
-    if ((threadIdx.x & (kWave - 1)) == 0 && mine) atomicAdd(hits, mine);
-}
+// compute_overlap_ratio (:417-472): a voxel counts when it was hit and is occupied
+struct Occupied {
+    float threshold;
+    __device__ bool operator()(const OgmCore& c) const { return c.hit_count > 0u && !(c.log_odds < threshold); }
+};
 
 // find_voxel (:591-609) for one key: out[0] = 1 and out[1] = the log-odds' bits when the map holds the voxel
 __global__ void ogm_lookup_kernel(OgmTable t, uint64_t key, unsigned* __restrict__ out) {
-    const unsigned long long s = find_slot(t, key);
+    const unsigned long long s = find_slot<kOgmMaxProbe>(t.key, t.capacity, key);
     out[0] = s != kNoSlot;
     out[1] = s != kNoSlot ? __float_as_uint(t.core[s].log_odds) : 0u;
 }
 
-__global__ void ogm_fill_keys_kernel(uint64_t* keys, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) keys[i] = kInvalidKey;
-}
-__global__ void ogm_seed_kernel(unsigned* counter, unsigned v0, unsigned v1, unsigned v2) {
-    counter[0] = v0; counter[1] = v1; counter[2] = v2;
-}
-
-constexpr OgmTable kNoTable{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-
 }  // namespace
 }  // namespace sp
 
-struct sp_occupancy_grid_map {  // defaults: occupancy_grid_map.hpp:1658-1680
-    float voxel_size = 0.1f, voxel_size_inv = 10.0f;
+struct sp_occupancy_grid_map : sp::VoxelMapState<sp::OgmCore> {  // defaults: occupancy_grid_map.hpp:1658-1680
     float log_odds_hit = 0.85f, log_odds_miss = -0.4f, min_log_odds = -4.0f, max_log_odds = 4.0f;
-    float occupancy_probability = 0.5f, occupancy_threshold_log_odds = 0.0f;
+    float occupancy_probability = 0.5f, occupancy_threshold_log_odds = 0.0f;  // log(0.5 / (1 - 0.5))
     bool free_space_updates = true, voxel_pruning = true;
-    bool has_cov = false, has_rgb = false, has_intensity = false;
     uint32_t frame_index = 0, stale_frame_threshold = 100;
-    float rehash_threshold = 0.7f;
-    size_t voxel_num = 0;
-    sp::OgmTable t = sp::kNoTable;
-    unsigned* counter = nullptr;  // device, 4 words: voxel count / overlap hits / lookup result | visit estimate (2) + origin hit
-    unsigned *flags = nullptr, *pos = nullptr;  // compaction scratch, sized to the capacity
-    size_t scratch_cap = 0;
-    void* scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
+    // the counter beyond its first word: the lookup's result takes two, the visit estimate (64 bits) + origin hit three
 };
 
 namespace sp {
 namespace {
 
-void free_table(OgmTable& t) {
-    (void)hipFree(t.key); (void)hipFree(t.core); (void)hipFree(t.cov); (void)hipFree(t.color); (void)hipFree(t.intensity);
-    (void)hipFree(t.last_update);
-    t = kNoTable;
-}
-
-// allocate_storage (:619-632): keys invalid, everything else zero
-int alloc_table(OgmTable& t, size_t cap, hipStream_t st) {
-    hipError_t e = hipMalloc(&t.key, cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&t.core, cap * sizeof(OgmCore));
-    if (e == hipSuccess) e = hipMalloc(&t.cov, cap * sizeof(CovSum));
-    if (e == hipSuccess) e = hipMalloc(&t.color, cap * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(&t.intensity, cap * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&t.last_update, cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(t.core, 0, cap * sizeof(OgmCore), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.cov, 0, cap * sizeof(CovSum), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.color, 0, cap * sizeof(float4), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.intensity, 0, cap * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.last_update, 0, cap * sizeof(uint32_t), st);
-    if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); free_table(t); return SP_ERR_HIP; }
-    t.capacity = cap;
-    ogm_fill_keys_kernel<<<div_up(cap, kBlock), kBlock, 0, st>>>(t.key, cap);
-    return launch_status();
-}
-
-int read_counter(const sp_occupancy_grid_map* m, hipStream_t st, unsigned* out, int words = 1) {
-    if (hipMemcpyAsync(out, m->counter, words * sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) return SP_ERR_HIP;
-    return hip_status(hipStreamSynchronize(st));  // the reference waits here too
-}
-int write_counter(const sp_occupancy_grid_map* m, hipStream_t st, unsigned v0, unsigned v1 = 0, unsigned v2 = 0) {
-    ogm_seed_kernel<<<1, 1, 0, st>>>(m->counter, v0, v1, v2);  // the values travel in the kernarg segment
-    return launch_status();
-}
-
-int rehash(sp_occupancy_grid_map* m, size_t new_cap, hipStream_t st) {
-    if (m->t.capacity >= new_cap) return SP_OK;
-    OgmTable old_t = m->t, new_t = kNoTable;
-    int rc = alloc_table(new_t, new_cap, st);
-    if (rc != SP_OK) return rc;
-    if ((rc = write_counter(m, st, 0)) != SP_OK) { free_table(new_t); return rc; }
-    ogm_rehash_kernel<<<div_up(old_t.capacity, kBlock), kBlock, 0, st>>>(old_t, new_t, m->has_cov, m->has_rgb, m->has_intensity,
-                                                                        m->counter);
-    unsigned cnt = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-    if (rc != SP_OK) { free_table(new_t); return rc; }
-    m->t = new_t;
-    free_table(old_t);
-    m->voxel_num = cnt;
-    return SP_OK;
+auto rehash_launch(const sp_occupancy_grid_map* m, hipStream_t st) {
+    return [=](const OgmTable& old_t, const OgmTable& new_t) {
+        ogm_rehash_kernel<<<div_up(old_t.capacity, kBlock), kBlock, 0, st>>>(old_t, new_t, m->has_cov, m->has_rgb, m->has_intensity,
+                                                                            m->counter);
+    };
 }
 
 float probability_to_log_odds(float p) { return std::log(p / (1.0f - p)); }  // :559-561
 
-// the slot-order compaction both exports use: flags -> exclusive scan; *total_out = the number of flagged slots
-int ensure_scratch(sp_occupancy_grid_map* m) {
-    const size_t cap = (size_t)m->t.capacity;
-    if (m->scratch_cap >= cap) return SP_OK;
-    (void)hipFree(m->flags); (void)hipFree(m->pos); (void)hipFree(m->scan_tmp);
-    m->flags = m->pos = nullptr; m->scan_tmp = nullptr; m->scratch_cap = 0;
-    const size_t tmp = exclusive_scan_u32_workspace_bytes(cap + 1);
-    hipError_t e = hipMalloc(&m->flags, (cap + 1) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&m->pos, (cap + 1) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&m->scan_tmp, tmp ? tmp : 16);
-    if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); return SP_ERR_HIP; }
-    m->scan_tmp_bytes = tmp;
-    m->scratch_cap = cap;
-    return SP_OK;
-}
+// the slot-order compaction both exports use, up to the scan
 int flag_and_scan(sp_occupancy_grid_map* m, bool occupied_only, const float* sensor3, float max_distance, hipStream_t st) {
-    int rc = ensure_scratch(m);
+    int rc = m->ensure_scratch();
     if (rc != SP_OK) return rc;
-    const size_t cap = (size_t)m->t.capacity;
-    ogm_flag_kernel<<<div_up(cap, kBlock), kBlock, 0, st>>>(m->t, occupied_only, m->occupancy_threshold_log_odds,
-                                                           sensor3 ? sensor3[0] : 0.0f, sensor3 ? sensor3[1] : 0.0f,
-                                                           sensor3 ? sensor3[2] : 0.0f, max_distance, m->flags);
-    if (hipMemsetAsync(m->flags + cap, 0, sizeof(unsigned), st) != hipSuccess) return SP_ERR_HIP;
-    if (exclusive_scan_u32(m->flags, m->pos, cap + 1, nullptr, m->scan_tmp, m->scan_tmp_bytes, st) != SP_OK) {
-        sp_set_error("[OccupancyGridMap] scan failed");
-        return SP_ERR_HIP;
-    }
-    return SP_OK;
-}
-int read_total(sp_occupancy_grid_map* m, hipStream_t st, size_t* n_out) {
-    unsigned total = 0;
-    if (hipMemcpyAsync(&total, m->pos + m->t.capacity, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) return SP_ERR_HIP;
-    const int rc = hip_status(hipStreamSynchronize(st));
-    if (rc == SP_OK) *n_out = total;
-    return rc;
+    ogm_flag_kernel<<<div_up((size_t)m->t.capacity, kBlock), kBlock, 0, st>>>(
+        m->t, occupied_only, m->occupancy_threshold_log_odds, sensor3 ? sensor3[0] : 0.0f, sensor3 ? sensor3[1] : 0.0f,
+        sensor3 ? sensor3[2] : 0.0f, max_distance, m->flags);
+    return m->scan_flags(st);
 }
 
 // update_free_space (:1235-1455)
@@ -518,13 +369,13 @@ int carve(sp_occupancy_grid_map* m, const float4* pts, unsigned n, const float* 
     const int oix = (int)fx, oiy = (int)fy, oiz = (int)fz;
     const uint64_t origin_key = (uint64_t)(oix + kCellOffset) | ((uint64_t)(oiy + kCellOffset) << 21) |
                                 ((uint64_t)(oiz + kCellOffset) << 42);
-    int rc = write_counter(m, st, 0, 0, 0);
+    int rc = m->write_counter(st, 0, 0, 0);
     if (rc != SP_OK) return rc;
     const Mat4Arg pose = pose_arg(pose16);
     ogm_estimate_kernel<<<stream_grid(n), kBlock, 0, st>>>(pts, n, pose, inv, ox, oy, oz, oix, oiy, oiz, origin_key, m->counter);
     unsigned est[3] = {0, 0, 0};
     rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, est, 3);
+    if (rc == SP_OK) rc = m->read_counter(st, est, 3);
     if (rc != SP_OK) return rc;
     const unsigned long long expected = (unsigned long long)est[0] | ((unsigned long long)est[1] << 32);
     if (expected == 0) return SP_OK;  // :1343-1346
@@ -536,61 +387,25 @@ int carve(sp_occupancy_grid_map* m, const float4* pts, unsigned n, const float* 
         if (next <= cap) break;
         cap = next;
     }
-    if ((rc = rehash(m, cap, st)) != SP_OK) return rc;
-    if ((rc = write_counter(m, st, (unsigned)m->voxel_num)) != SP_OK) return rc;
+    if ((rc = m->grow(cap, st, rehash_launch(m, st))) != SP_OK) return rc;
+    if ((rc = m->write_counter(st, (unsigned)m->voxel_num)) != SP_OK) return rc;
     ogm_walk_kernel<<<stream_grid(n), kBlock, 0, st>>>(m->t, pts, n, pose, inv, ox, oy, oz, est[2] != 0, m->frame_index, m->counter);
-    unsigned cnt = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-    if (rc == SP_OK) m->voxel_num = cnt;
-    return rc;
+    return m->read_voxel_num(st);
 }
 
 }  // namespace
 }  // namespace sp
 
 extern "C" int sp_ogm_create(float voxel_size, void* stream, sp_occupancy_grid_map** out) {
-    using namespace sp;
-    if (!out) return SP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!(voxel_size > 0.0f)) {
-        sp_set_error("voxel_size must be positive.");  // occupancy_grid_map.hpp:74-76
-        return SP_ERR_INVALID_ARGUMENT;
-    }
-    sp_occupancy_grid_map* m = new sp_occupancy_grid_map();
-    m->voxel_size = voxel_size;
-    m->voxel_size_inv = 1.0f / voxel_size;
-    m->occupancy_threshold_log_odds = probability_to_log_odds(0.5f);
-    hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMalloc(&m->counter, 4 * sizeof(unsigned)));
-    if (rc == SP_OK) rc = alloc_table(m->t, kCapacityCandidates[0], st);
-    if (rc == SP_OK) rc = hip_status(hipStreamSynchronize(st));
-    if (rc != SP_OK) { sp_ogm_destroy(m); return rc; }
-    *out = m;
-    return SP_OK;
+    return sp::create_map(voxel_size, stream, out);
 }
-
-extern "C" void sp_ogm_destroy(sp_occupancy_grid_map* m) {
-    if (!m) return;
-    sp::free_table(m->t);
-    (void)hipFree(m->counter); (void)hipFree(m->flags); (void)hipFree(m->pos); (void)hipFree(m->scan_tmp);
-    delete m;
-}
+extern "C" void sp_ogm_destroy(sp_occupancy_grid_map* m) { sp::destroy_map(m); }
 
 extern "C" int sp_ogm_clear(sp_occupancy_grid_map* m, void* stream) {  // :42-69
-    using namespace sp;
     if (!m) return SP_ERR_INVALID_ARGUMENT;
-    hipStream_t st = as_stream(stream);
-    OgmTable fresh = kNoTable;
-    int rc = alloc_table(fresh, kCapacityCandidates[0], st);
-    if (rc == SP_OK) rc = hip_status(hipStreamSynchronize(st));
-    if (rc != SP_OK) return rc;
-    free_table(m->t);
-    m->t = fresh;
-    m->voxel_num = 0;
-    m->frame_index = 0;
-    m->has_cov = m->has_rgb = m->has_intensity = false;
-    return SP_OK;
+    const int rc = m->reset_to_first_capacity(sp::as_stream(stream));
+    if (rc == SP_OK) m->frame_index = 0;
+    return rc;
 }
 
 extern "C" int sp_ogm_set_log_odds_limits(sp_occupancy_grid_map* m, float minimum, float maximum) {  // :107-113
@@ -663,39 +478,27 @@ extern "C" int sp_ogm_add_point_cloud(sp_occupancy_grid_map* m, const float* poi
     using namespace sp;
     if (!m || (n && !points)) return SP_ERR_INVALID_ARGUMENT;
     if (n >= (1ull << 32)) { sp_set_error("[OccupancyGridMap] more than 2^32 points"); return SP_ERR_INVALID_ARGUMENT; }
-    if (n == 0) return SP_OK;  // :130-132: no rehash, no pruning, no new frame
+    if (n == 0) return SP_OK;  // :130-132: no rehash, no pruning, no new frame (unlike VoxelHashMap, where an empty cloud is a frame)
     hipStream_t st = as_stream(stream);
-    int rc = SP_OK;
-    if (m->rehash_threshold < (float)m->voxel_num / (float)m->t.capacity) {  // ensure_rehash (:634-641)
-        const size_t next = next_capacity((size_t)m->t.capacity);
-        if (next > m->t.capacity && (rc = rehash(m, next, st)) != SP_OK) return rc;
-    }
-    m->has_cov |= covs != nullptr;
-    m->has_rgb |= rgb != nullptr;
-    m->has_intensity |= intensities != nullptr;
+    int rc = m->ensure_rehash(st, rehash_launch(m, st));  // :634-641
+    if (rc != SP_OK) return rc;
+    m->note_attributes(covs, rgb, intensities);
     const float4* pts = reinterpret_cast<const float4*>(points);
-    if ((rc = write_counter(m, st, (unsigned)m->voxel_num)) != SP_OK) return rc;
+    if ((rc = m->write_counter(st, (unsigned)m->voxel_num)) != SP_OK) return rc;
     ogm_hit_kernel<<<stream_grid(n), kBlock, 0, st>>>(m->t, pts, reinterpret_cast<const float4*>(covs),
                                                      reinterpret_cast<const float4*>(rgb), intensities, (unsigned)n,
                                                      pose_arg(sensor_pose_host16), m->voxel_size_inv, m->has_cov, m->has_rgb,
                                                      m->has_intensity, m->frame_index, m->counter);
-    unsigned cnt = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-    if (rc != SP_OK) return rc;
-    m->voxel_num = cnt;
+    if ((rc = m->read_voxel_num(st)) != SP_OK) return rc;
     if (m->free_space_updates && m->log_odds_miss != 0.0f)
         if ((rc = carve(m, pts, (unsigned)n, sensor_pose_host16, st)) != SP_OK) return rc;
     const unsigned cap_blocks = div_up((size_t)m->t.capacity, kBlock);
     ogm_apply_kernel<<<cap_blocks, kBlock, 0, st>>>(m->t, m->log_odds_hit, m->log_odds_miss, m->min_log_odds, m->max_log_odds);
     if ((rc = launch_status()) != SP_OK) return rc;
     if (m->voxel_pruning && m->frame_index >= m->stale_frame_threshold) {  // :1490-1492
-        if ((rc = write_counter(m, st, 0)) != SP_OK) return rc;
+        if ((rc = m->write_counter(st, 0)) != SP_OK) return rc;
         ogm_prune_kernel<<<cap_blocks, kBlock, 0, st>>>(m->t, m->frame_index, m->stale_frame_threshold, m->counter);
-        rc = launch_status();
-        if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-        if (rc != SP_OK) return rc;
-        m->voxel_num = cnt;
+        if ((rc = m->read_voxel_num(st)) != SP_OK) return rc;
     } else if ((rc = hip_status(hipStreamSynchronize(st))) != SP_OK) {  // the reference waits for the apply kernel (:1482)
         return rc;
     }
@@ -719,12 +522,8 @@ extern "C" int sp_ogm_extract_occupied_points(sp_occupancy_grid_map* m, const fl
     int rc = flag_and_scan(m, true, sensor_xyz_host3, max_distance, st);
     if (rc != SP_OK) return rc;
     ogm_extract_kernel<<<div_up((size_t)m->t.capacity, kBlock), kBlock, 0, st>>>(
-        m->t, m->flags, m->pos, (unsigned)out_capacity, reinterpret_cast<float4*>(points_out),
-        m->has_cov ? reinterpret_cast<float4*>(covs_out) : nullptr, m->has_rgb ? reinterpret_cast<float4*>(rgb_out) : nullptr,
-        m->has_intensity ? intensities_out : nullptr, keys_out_opt);
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_total(m, st, n_out_host);
-    return rc;
+        m->t, m->flags, m->pos, (unsigned)out_capacity, m->mean_rows(points_out, covs_out, rgb_out, intensities_out, keys_out_opt));
+    return m->read_total(st, n_out_host);
 }
 
 extern "C" int sp_ogm_export(sp_occupancy_grid_map* m, uint64_t* keys_out, uint32_t* hit_count_out, uint32_t* miss_count_out,
@@ -744,29 +543,14 @@ extern "C" int sp_ogm_export(sp_occupancy_grid_map* m, uint64_t* keys_out, uint3
     ogm_export_kernel<<<div_up((size_t)m->t.capacity, kBlock), kBlock, 0, st>>>(
         m->t, m->flags, m->pos, (unsigned)out_capacity, keys_out, hit_count_out, miss_count_out, log_odds_out, last_updated_out,
         sum_xyz_out, cov_sums_out, rgb_sums_out, intensity_sums_out);
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_total(m, st, n_out_host);
-    return rc;
+    return m->read_total(st, n_out_host);
 }
 
 extern "C" int sp_ogm_overlap_ratio(const sp_occupancy_grid_map* m, const float* points, size_t n, const float* sensor_pose_host16,
                                     float* ratio_out_host, void* stream) {
-    using namespace sp;
-    if (!m || !ratio_out_host) return SP_ERR_INVALID_ARGUMENT;
-    *ratio_out_host = 0.0f;
-    if (n == 0 || !points || m->voxel_num == 0) return SP_OK;  // :418-420
-    if (n >= (1ull << 32)) { sp_set_error("[OccupancyGridMap] more than 2^32 points"); return SP_ERR_INVALID_ARGUMENT; }
-    hipStream_t st = as_stream(stream);
-    int rc = write_counter(m, st, 0);
-    if (rc != SP_OK) return rc;
-    ogm_overlap_kernel<<<stream_grid(n), kBlock, 0, st>>>(m->t, reinterpret_cast<const float4*>(points), (unsigned)n,
-                                                          pose_arg(sensor_pose_host16), m->voxel_size_inv,
-                                                          m->occupancy_threshold_log_odds, m->counter);
-    unsigned hits = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &hits);
-    if (rc == SP_OK) *ratio_out_host = (float)hits / (float)n;
-    return rc;
+    if (!m) return SP_ERR_INVALID_ARGUMENT;
+    return m->overlap_ratio<sp::kOgmMaxProbe>(sp::Occupied{m->occupancy_threshold_log_odds}, points, n, sensor_pose_host16,
+                                              ratio_out_host, sp::as_stream(stream));
 }
 
 // voxel_probability (:85-93): compute_key (:569-589) on the host, the probe on the device, the logistic on the host
@@ -785,7 +569,7 @@ extern "C" int sp_ogm_voxel_probability(const sp_occupancy_grid_map* m, const fl
     ogm_lookup_kernel<<<1, 1, 0, st>>>(m->t, key, m->counter);
     unsigned res[2] = {0, 0};
     int rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, res, 2);
+    if (rc == SP_OK) rc = m->read_counter(st, res, 2);
     if (rc != SP_OK || !res[0]) return rc;
     float lo;
     static_assert(sizeof(lo) == sizeof(res[1]), "");

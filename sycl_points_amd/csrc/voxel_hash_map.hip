@@ -1,10 +1,9 @@
 // VoxelHashMap for gfx950 — submap accumulation either side of the hot path (replaces
 // algorithms/mapping/voxel_hash_map.hpp:22-1072).
 //
-// The table lives in HBM as six parallel arrays (key u64 | core {sum xyz, count} 16 B | log-covariance sums 24 B | colour
-// sums 16 B | intensity sum | last update), open addressing with the reference's double hashing (compute_slot_id, :587-592,
-// 100 probes). One lane per input point: transform into the map frame (the reference's fma chain), compute_voxel_bit (the
-// K9 key), rotate + log-map the covariance, claim or find the slot with a 64-bit compare-and-swap and add with relaxed
+// The table is sp_voxel_table.h's with a 16-byte core {sum xyz, count} and 100 probes; the host state, the compaction scratch and
+// the overlap kernel are there too. One lane per input point: transform into the map frame (the reference's fma chain),
+// compute_voxel_bit (the K9 key), rotate + log-map the covariance, claim or find the slot with a 64-bit compare-and-swap and add with relaxed
 // device-scope atomics (global_atomic_add_f32 executes at the memory side on gfx950; ~1.3 TB/s of added bytes chip-wide,
 // MI355X_MICROARCH.md "Global float atomics"). The reference pre-reduces inside a work-group with a bitonic sort before its
 // atomics; here that step is dropped: 60 B of atomics per point at 1M points is ~50 us, less than the sort.
@@ -13,31 +12,21 @@
 // Host-side control flow (rehash schedule, staleness counter, has_* flags) follows :117-141 line by line; like the
 // reference, add_point_cloud waits for its kernel and reads the voxel count back.
 
-#include "radix_sort.h"
 #include "sp_voxel_table.h"
-
-void sp_set_error(const char* msg);
 
 namespace sp {
 namespace {
 
 constexpr unsigned kMaxProbe = 100;      // voxel_hash_map.hpp:505
 
-struct Table {
-    uint64_t* key;
-    float4* core;        // sum_x, sum_y, sum_z, count (uint32 bits)
-    CovSum* cov;         // sums of log(C) (upper triangle)
-    float4* color;
-    float* intensity;
-    uint32_t* last_update;
-    unsigned long long capacity;
-};
+using Table = VoxelTable<float4>;  // core: sum_x, sum_y, sum_z, count (uint32 bits)
 
 // global_reduction (:549-585): claim the first free slot or find the key's slot within kMaxProbe probes, then add.
 // An entry that finds neither is dropped, as in the reference.
+// Not OccupancyGridMap's find_or_claim, on purpose: this one swaps first, probes 100 times and knows no `deleted` key.
 __device__ __forceinline__ void insert(const Table& t, uint64_t h, float sx, float sy, float sz, unsigned count,
                                        const CovSum& cv, bool has_cov, const float4 col, bool has_rgb, float inten,
-                                       bool has_intensity, uint32_t stamp, unsigned* __restrict__ voxel_num) {
+                                       bool has_intensity, uint32_t when, unsigned* __restrict__ voxel_num) {
     if (h == kInvalidKey) return;
     for (unsigned p = 0; p < kMaxProbe; ++p) {
         const unsigned long long s = slot_id(h, p, t.capacity);
@@ -49,17 +38,8 @@ __device__ __forceinline__ void insert(const Table& t, uint64_t h, float sx, flo
         fadd(core + 1, sy);
         fadd(core + 2, sz);
         atomicAdd(reinterpret_cast<unsigned*>(core + 3), count);
-        if (has_cov) {
-            float* c = reinterpret_cast<float*>(t.cov + s);
-            fadd(c + 0, cv.xx); fadd(c + 1, cv.xy); fadd(c + 2, cv.xz);
-            fadd(c + 3, cv.yy); fadd(c + 4, cv.yz); fadd(c + 5, cv.zz);
-        }
-        if (has_rgb) {
-            float* c = reinterpret_cast<float*>(t.color + s);
-            fadd(c + 0, col.x); fadd(c + 1, col.y); fadd(c + 2, col.z); fadd(c + 3, col.w);
-        }
-        if (has_intensity) fadd(t.intensity + s, inten);
-        __hip_atomic_store(t.last_update + s, stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // :325-328
+        add_attributes(t, s, cv, has_cov, col, has_rgb, inten, has_intensity);
+        stamp(t, s, when);  // :325-328
         return;
     }
 }
@@ -85,7 +65,9 @@ __global__ __launch_bounds__(kBlock) void vhm_add_kernel(Table t, const float4* 
     }
 }
 
-// rehash (:845-931): every live slot of the old table re-enters the new one with its own time stamp
+// rehash (:845-931): every live slot of the old table re-enters the new one with its own time stamp.
+// Not OccupancyGridMap's rehash kernel, on purpose: a table whose probe chains vhm_remove_kernel has cut can hold one key twice, and
+// re-entering through insert() merges the two entries with its atomic adds.
 __global__ __launch_bounds__(kBlock) void vhm_rehash_kernel(Table old_t, Table new_t, bool has_cov, bool has_rgb,
                                                             bool has_intensity, unsigned* __restrict__ voxel_num) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
@@ -113,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void vhm_remove_kernel(Table t, uint32_t re
     t.last_update[i] = 0;
 }
 
-// should_include_voxel (:402-418)
+// should_include_voxel (:402-418). Each map's flag kernel tests its own condition: not shared.
 __global__ __launch_bounds__(kBlock) void vhm_flag_kernel(Table t, uint32_t min_num_point, float mnx, float mny, float mnz,
                                                           float mxx, float mxy, float mxz, unsigned* __restrict__ flags) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
@@ -131,145 +113,49 @@ __global__ __launch_bounds__(kBlock) void vhm_flag_kernel(Table t, uint32_t min_
 
 // compute_averaged_attributes (:330-386) into the compacted outputs (slot order)
 __global__ __launch_bounds__(kBlock) void vhm_export_kernel(Table t, const unsigned* __restrict__ flags,
-                                                            const unsigned* __restrict__ pos, unsigned out_capacity,
-                                                            float4* __restrict__ pts_out, float4* __restrict__ cov_out,
-                                                            float4* __restrict__ rgb_out, float* __restrict__ inten_out,
-                                                            uint64_t* __restrict__ keys_out) {
+                                                            const unsigned* __restrict__ pos, unsigned out_capacity, MeanRows out) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= t.capacity || !flags[i]) return;
     const unsigned o = pos[i];
     if (o >= out_capacity) return;
     const float4 c = t.core[i];
-    const float inv = 1.0f / (float)__float_as_uint(c.w);
-    pts_out[o] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
-    if (cov_out) {
-        decode_cov(t.cov[i], inv, cov_out + 4 * (size_t)o);  // column-major 4x4, 3x3 block used
-    }
-    if (rgb_out) {
-        const float4 k = t.color[i];
-        rgb_out[o] = make_float4(k.x * inv, k.y * inv, k.z * inv, k.w * inv);
-    }
-    if (inten_out) inten_out[o] = t.intensity[i] * inv;
-    if (keys_out) keys_out[o] = t.key[i];
+    write_mean_row(t, i, o, __float_as_uint(c.w), c.x, c.y, c.z, out);
 }
 
-// compute_overlap_ratio (:196-246)
-__global__ __launch_bounds__(kBlock) void vhm_overlap_kernel(Table t, const float4* __restrict__ pts, unsigned n,
-                                                             Mat4Arg pose, float inv, uint32_t min_num_point,
-                                                             unsigned* __restrict__ hits) {
-    const Rigid T = load_rigid_colmajor(pose.m);
-    unsigned mine = 0;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        const float4 p = pts[i];
-        float wx, wy, wz;
-        transform_point(T, p.x, p.y, p.z, wx, wy, wz);
-        const uint64_t h = voxel_key3(wx, wy, wz, inv);
-        if (h == kInvalidKey) continue;
-        for (unsigned pr = 0; pr < kMaxProbe; ++pr) {
-            const unsigned long long s = slot_id(h, pr, t.capacity);
-            const uint64_t k = t.key[s];
-            if (k == h) { if (__float_as_uint(t.core[s].w) >= min_num_point) ++mine; break; }
-            if (k == kInvalidKey) break;
-        }
-    }
-    mine = wave_sum_u32(mine);
-    if ((threadIdx.x & (kWave - 1)) == 0 && mine) atomicAdd(hits, mine);  // integer: exact, order-independent
-}
-
-__global__ void vhm_fill_keys_kernel(uint64_t* keys, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) keys[i] = kInvalidKey;
-}
+// compute_overlap_ratio (:196-246): a voxel counts from min_num_point points on
+struct EnoughPoints {
+    uint32_t min_num_point;
+    __device__ bool operator()(const float4& core) const { return __float_as_uint(core.w) >= min_num_point; }
+};
 
 }  // namespace
 }  // namespace sp
 
-struct sp_voxel_hash_map {
-    float voxel_size = 0.0f, voxel_size_inv = 0.0f;
+struct sp_voxel_hash_map : sp::VoxelMapState<float4> {
     uint32_t max_staleness = 100, remove_old_data_cycle = 10, min_num_point = 1, staleness_counter = 0;
-    float rehash_threshold = 0.7f;
-    size_t voxel_num = 0;
-    bool has_cov = false, has_rgb = false, has_intensity = false;
-    sp::Table t{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    unsigned* counter = nullptr;        // device: voxel count / hit count of the running call
-    unsigned *flags = nullptr, *pos = nullptr;  // export scratch, sized to the capacity
-    size_t scratch_cap = 0;
-    void* scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
 };
 
 namespace sp {
 namespace {
 
-void free_table(Table& t) {
-    (void)hipFree(t.key); (void)hipFree(t.core); (void)hipFree(t.cov); (void)hipFree(t.color); (void)hipFree(t.intensity);
-    (void)hipFree(t.last_update);
-    t = Table{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+void drop_flags_when_empty(sp_voxel_hash_map* m) {  // update_voxel_num_and_flags (:519-526), after a count was read back
+    if (m->voxel_num == 0) m->has_cov = m->has_rgb = m->has_intensity = false;
 }
 
-// allocate_storage (:528-544): keys invalid, everything else zero
-int alloc_table(Table& t, size_t cap, hipStream_t st) {
-    hipError_t e = hipMalloc(&t.key, cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&t.core, cap * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(&t.cov, cap * sizeof(CovSum));
-    if (e == hipSuccess) e = hipMalloc(&t.color, cap * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(&t.intensity, cap * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&t.last_update, cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(t.core, 0, cap * sizeof(float4), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.cov, 0, cap * sizeof(CovSum), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.color, 0, cap * sizeof(float4), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.intensity, 0, cap * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(t.last_update, 0, cap * sizeof(uint32_t), st);
-    if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); free_table(t); return SP_ERR_HIP; }
-    t.capacity = cap;
-    vhm_fill_keys_kernel<<<div_up(cap, kBlock), kBlock, 0, st>>>(t.key, cap);
-    return launch_status();
-}
-
-void set_voxel_num(sp_voxel_hash_map* m, size_t n) {  // update_voxel_num_and_flags (:519-526)
-    m->voxel_num = n;
-    if (n == 0) m->has_cov = m->has_rgb = m->has_intensity = false;
-}
-
-int read_counter(sp_voxel_hash_map* m, hipStream_t st, unsigned* out) {
-    if (hipMemcpyAsync(out, m->counter, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) return SP_ERR_HIP;
-    return hip_status(hipStreamSynchronize(st));  // the reference waits here too (wait_and_throw + shared read)
-}
-__global__ void vhm_seed_counter_kernel(unsigned* counter, unsigned v) { *counter = v; }
-int write_counter(sp_voxel_hash_map* m, hipStream_t st, unsigned v) {
-    // the value travels in the kernarg segment: nothing is read from a host variable after this returns
-    vhm_seed_counter_kernel<<<1, 1, 0, st>>>(m->counter, v);
-    return launch_status();
-}
-
-int rehash(sp_voxel_hash_map* m, size_t new_cap, hipStream_t st) {
-    if (m->t.capacity >= new_cap) return SP_OK;
-    Table old_t = m->t, new_t{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    int rc = alloc_table(new_t, new_cap, st);
-    if (rc != SP_OK) return rc;
-    if ((rc = write_counter(m, st, 0)) != SP_OK) { free_table(new_t); return rc; }
-    vhm_rehash_kernel<<<div_up(old_t.capacity, kBlock), kBlock, 0, st>>>(old_t, new_t, m->has_cov, m->has_rgb,
-                                                                        m->has_intensity, m->counter);
-    unsigned cnt = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-    if (rc != SP_OK) { free_table(new_t); return rc; }
-    m->t = new_t;
-    free_table(old_t);
-    set_voxel_num(m, cnt);
-    return SP_OK;
+auto rehash_launch(const sp_voxel_hash_map* m, hipStream_t st) {
+    return [=](const Table& old_t, const Table& new_t) {
+        vhm_rehash_kernel<<<div_up(old_t.capacity, kBlock), kBlock, 0, st>>>(old_t, new_t, m->has_cov, m->has_rgb, m->has_intensity,
+                                                                            m->counter);
+    };
 }
 
 int remove_old(sp_voxel_hash_map* m, hipStream_t st) {
     if (m->staleness_counter <= m->max_staleness) return SP_OK;
-    int rc = write_counter(m, st, 0);
+    int rc = m->write_counter(st, 0);
     if (rc != SP_OK) return rc;
     vhm_remove_kernel<<<div_up(m->t.capacity, kBlock), kBlock, 0, st>>>(m->t, m->staleness_counter - m->max_staleness,
                                                                       m->counter);
-    unsigned cnt = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-    if (rc == SP_OK) set_voxel_num(m, cnt);
+    if ((rc = m->read_voxel_num(st)) == SP_OK) drop_flags_when_empty(m);
     return rc;
 }
 
@@ -277,46 +163,15 @@ int remove_old(sp_voxel_hash_map* m, hipStream_t st) {
 }  // namespace sp
 
 extern "C" int sp_vhm_create(float voxel_size, void* stream, sp_voxel_hash_map** out) {
-    using namespace sp;
-    if (!out) return SP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!(voxel_size > 0.0f)) {
-        sp_set_error("voxel_size must be positive.");  // voxel_hash_map.hpp:41-43
-        return SP_ERR_INVALID_ARGUMENT;
-    }
-    sp_voxel_hash_map* m = new sp_voxel_hash_map();
-    m->voxel_size = voxel_size;
-    m->voxel_size_inv = 1.0f / voxel_size;
-    hipStream_t st = as_stream(stream);
-    int rc = hip_status(hipMalloc(&m->counter, sizeof(unsigned)));
-    if (rc == SP_OK) rc = alloc_table(m->t, kCapacityCandidates[0], st);
-    if (rc == SP_OK) rc = hip_status(hipStreamSynchronize(st));
-    if (rc != SP_OK) { sp_vhm_destroy(m); return rc; }
-    *out = m;
-    return SP_OK;
+    return sp::create_map(voxel_size, stream, out);
 }
-
-extern "C" void sp_vhm_destroy(sp_voxel_hash_map* m) {
-    if (!m) return;
-    sp::free_table(m->t);
-    (void)hipFree(m->counter); (void)hipFree(m->flags); (void)hipFree(m->pos); (void)hipFree(m->scan_tmp);
-    delete m;
-}
+extern "C" void sp_vhm_destroy(sp_voxel_hash_map* m) { sp::destroy_map(m); }
 
 extern "C" int sp_vhm_clear(sp_voxel_hash_map* m, void* stream) {  // :83-113
-    using namespace sp;
     if (!m) return SP_ERR_INVALID_ARGUMENT;
-    hipStream_t st = as_stream(stream);
-    Table fresh{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    int rc = alloc_table(fresh, kCapacityCandidates[0], st);
-    if (rc == SP_OK) rc = hip_status(hipStreamSynchronize(st));
-    if (rc != SP_OK) return rc;
-    free_table(m->t);
-    m->t = fresh;
-    m->voxel_num = 0;
-    m->staleness_counter = 0;
-    m->has_cov = m->has_rgb = m->has_intensity = false;
-    return SP_OK;
+    const int rc = m->reset_to_first_capacity(sp::as_stream(stream));
+    if (rc == SP_OK) m->staleness_counter = 0;
+    return rc;
 }
 
 extern "C" int sp_vhm_set(sp_voxel_hash_map* m, int param, float value) {
@@ -370,25 +225,19 @@ extern "C" int sp_vhm_add_point_cloud(sp_voxel_hash_map* m, const float* points,
     if (!m || (n && !points)) return SP_ERR_INVALID_ARGUMENT;
     if (n >= (1ull << 32)) { sp_set_error("[VoxelHashMap] more than 2^32 points"); return SP_ERR_INVALID_ARGUMENT; }
     hipStream_t st = as_stream(stream);
-    int rc = SP_OK;
-    if (m->rehash_threshold < (float)m->voxel_num / (float)m->t.capacity) {
-        const size_t next = next_capacity((size_t)m->t.capacity);
-        if (next > m->t.capacity && (rc = rehash(m, next, st)) != SP_OK) return rc;
-    }
+    const unsigned long long cap = m->t.capacity;
+    int rc = m->ensure_rehash(st, rehash_launch(m, st));
+    if (rc != SP_OK) return rc;
+    if (m->t.capacity != cap) drop_flags_when_empty(m);
+    // Unlike OccupancyGridMap, an empty cloud still is a frame: the staleness counter advances and the removal pass may run.
     if (n > 0) {
-        m->has_cov |= covs != nullptr;
-        m->has_rgb |= rgb != nullptr;
-        m->has_intensity |= intensities != nullptr;
-        if ((rc = write_counter(m, st, (unsigned)m->voxel_num)) != SP_OK) return rc;
+        m->note_attributes(covs, rgb, intensities);
+        if ((rc = m->write_counter(st, (unsigned)m->voxel_num)) != SP_OK) return rc;
         vhm_add_kernel<<<stream_grid(n), kBlock, 0, st>>>(
             m->t, reinterpret_cast<const float4*>(points), reinterpret_cast<const float4*>(covs),
             reinterpret_cast<const float4*>(rgb), intensities, (unsigned)n, pose_arg(sensor_pose_host16), m->voxel_size_inv,
             m->has_cov, m->has_rgb, m->has_intensity, m->staleness_counter, m->counter);
-        unsigned cnt = 0;
-        rc = launch_status();
-        if (rc == SP_OK) rc = read_counter(m, st, &cnt);
-        if (rc != SP_OK) return rc;
-        m->voxel_num = cnt;
+        if ((rc = m->read_voxel_num(st)) != SP_OK) return rc;
     }
     if (m->remove_old_data_cycle > 0 && (m->staleness_counter % m->remove_old_data_cycle) == 0)
         if ((rc = remove_old(m, st)) != SP_OK) return rc;
@@ -409,55 +258,21 @@ extern "C" int sp_vhm_downsampling(sp_voxel_hash_map* m, const float* center_hos
         return SP_ERR_INVALID_ARGUMENT;
     }
     hipStream_t st = as_stream(stream);
-    const size_t cap = (size_t)m->t.capacity;
-    if (m->scratch_cap < cap) {
-        (void)hipFree(m->flags); (void)hipFree(m->pos); (void)hipFree(m->scan_tmp);
-        m->flags = m->pos = nullptr; m->scan_tmp = nullptr; m->scratch_cap = 0;
-        const size_t tmp = exclusive_scan_u32_workspace_bytes(cap + 1);
-        hipError_t e = hipMalloc(&m->flags, (cap + 1) * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc(&m->pos, (cap + 1) * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc(&m->scan_tmp, tmp ? tmp : 16);
-        if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); return SP_ERR_HIP; }
-        m->scan_tmp_bytes = tmp;
-        m->scratch_cap = cap;
-    }
-    vhm_flag_kernel<<<div_up(cap, kBlock), kBlock, 0, st>>>(m->t, m->min_num_point, center_host3[0] - distance,
-                                                           center_host3[1] - distance, center_host3[2] - distance,
-                                                           center_host3[0] + distance, center_host3[1] + distance,
-                                                           center_host3[2] + distance, m->flags);
-    if (hipMemsetAsync(m->flags + cap, 0, sizeof(unsigned), st) != hipSuccess) return SP_ERR_HIP;
-    if (exclusive_scan_u32(m->flags, m->pos, cap + 1, nullptr, m->scan_tmp, m->scan_tmp_bytes, st) != SP_OK) {
-        sp_set_error("[VoxelHashMap::downsampling] scan failed");
-        return SP_ERR_HIP;
-    }
-    vhm_export_kernel<<<div_up(cap, kBlock), kBlock, 0, st>>>(
-        m->t, m->flags, m->pos, (unsigned)out_capacity, reinterpret_cast<float4*>(points_out),
-        m->has_cov ? reinterpret_cast<float4*>(covs_out) : nullptr, m->has_rgb ? reinterpret_cast<float4*>(rgb_out) : nullptr,
-        m->has_intensity ? intensities_out : nullptr, keys_out_opt);
-    int rc = launch_status();
-    unsigned total = 0;
-    if (rc == SP_OK && hipMemcpyAsync(&total, m->pos + cap, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) rc = SP_ERR_HIP;
-    if (rc == SP_OK) rc = hip_status(hipStreamSynchronize(st));
-    if (rc == SP_OK) *n_out_host = total;
-    return rc;
+    int rc = m->ensure_scratch();
+    if (rc != SP_OK) return rc;
+    const unsigned blocks = div_up((size_t)m->t.capacity, kBlock);
+    vhm_flag_kernel<<<blocks, kBlock, 0, st>>>(m->t, m->min_num_point, center_host3[0] - distance, center_host3[1] - distance,
+                                               center_host3[2] - distance, center_host3[0] + distance, center_host3[1] + distance,
+                                               center_host3[2] + distance, m->flags);
+    if ((rc = m->scan_flags(st)) != SP_OK) return rc;
+    vhm_export_kernel<<<blocks, kBlock, 0, st>>>(m->t, m->flags, m->pos, (unsigned)out_capacity,
+                                                 m->mean_rows(points_out, covs_out, rgb_out, intensities_out, keys_out_opt));
+    return m->read_total(st, n_out_host);
 }
 
 extern "C" int sp_vhm_overlap_ratio(const sp_voxel_hash_map* m, const float* points, size_t n,
                                     const float* sensor_pose_host16, float* ratio_out_host, void* stream) {
-    using namespace sp;
-    if (!m || !ratio_out_host) return SP_ERR_INVALID_ARGUMENT;
-    *ratio_out_host = 0.0f;
-    if (n == 0 || !points || m->voxel_num == 0) return SP_OK;
-    hipStream_t st = as_stream(stream);
-    sp_voxel_hash_map* mm = const_cast<sp_voxel_hash_map*>(m);  // the counter scratch only
-    int rc = write_counter(mm, st, 0);
-    if (rc != SP_OK) return rc;
-    vhm_overlap_kernel<<<stream_grid(n), kBlock, 0, st>>>(m->t, reinterpret_cast<const float4*>(points), (unsigned)n,
-                                                          pose_arg(sensor_pose_host16), m->voxel_size_inv, m->min_num_point,
-                                                          m->counter);
-    unsigned hits = 0;
-    rc = launch_status();
-    if (rc == SP_OK) rc = read_counter(mm, st, &hits);
-    if (rc == SP_OK) *ratio_out_host = (float)hits / (float)n;
-    return rc;
+    if (!m) return SP_ERR_INVALID_ARGUMENT;
+    return m->overlap_ratio<sp::kMaxProbe>(sp::EnoughPoints{m->min_num_point}, points, n, sensor_pose_host16, ratio_out_host,
+                                           sp::as_stream(stream));
 }

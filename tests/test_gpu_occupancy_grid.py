@@ -383,6 +383,30 @@ def test_empty_and_absent_inputs(sp, cpu, R):
     assert m.info("voxel_num") == 0 and m.info("frame_index") == 0 and m.extract_occupied_points().size() == 0
 
 
+def test_export_scratch_regrows(sp, cpu, R):
+    """Two rounds of exports of one map object either side of a rehash: the compaction scratch (flags, positions, scan workspace) is
+    sized for 30 029 slots by the first round and has to grow for the 60 013 of the second. Hits only, one point per voxel at the
+    cell centres (exact in fp32: no centroid on a box face); rehash_threshold 0.01 grows the table at the first add that finds more
+    than 300 voxels: 64 voxels -> exports -> +250 (314) -> +150 (rehash first, then 464) -> exports."""
+    dev, ref = DevMap(sp, VOXEL), cpu.RestatedMap(R, VOXEL)
+    for m in (dev, ref):
+        m.set("free_space_updates_enabled", 0)
+        m.set("rehash_threshold", 0.01)
+    first = 0
+    for frames, voxels, capacity in (((64,), 64, 30029), ((250, 150), 464, 60013)):
+        for count in frames:
+            k = np.arange(first, first + count)
+            first += count
+            pts = cpu.P((np.stack([k % 8, (k // 8) % 8, k // 64], axis=1) + 0.5) * VOXEL)
+            rgb = np.stack([(k % 7) / 8.0, (k % 5) / 8.0, (k % 3) / 4.0, np.ones(count)], axis=1).astype(np.float32)
+            for m in (dev, ref):
+                m.add_point_cloud(pts, None, None, rgb, (k % 11).astype(np.float32))
+        assert compare_state(dev, ref, 4.0) == voxels  # export(): keys, counts, voxel_num, capacity exact
+        assert dev.info("capacity") == capacity
+        attribute_means(dev, ref, 4.0)  # extract_occupied_points: the same key set, the means
+        assert len(dev.extract_occupied_points(None, 1e6)["keys"]) == voxels  # one hit each: log-odds 0.85, occupied
+
+
 def test_cpp_facade(sp):
     """tests/cpp/test_occupancy_grid.cpp, built with tests/cpp/Makefile's flags and libraries (the Makefile is not changed): the
     reference's known answers and one carving case through sycl_points::algorithms::mapping::OccupancyGridMap"""

@@ -199,3 +199,41 @@ def test_frames_match_oracle(sp, orc, attrs):
             assert gm.compute_overlap_ratio(cloud(sp, q)) == pytest.approx(om.overlap_ratio(q), abs=2e-3)
     gm.clear()
     assert gm.info("voxel_num") == 0 and gm.info("capacity") == 30029 and gm.downsampling().size() == 0
+
+
+def one_per_voxel(first, count, voxel):
+    """points at the centres of cells first .. first + count - 1 of an 8 x 8 x n lattice: one point per voxel, exact in fp32, so
+    that no centroid sits on a box face; with colours and intensities that tell the voxels apart"""
+    k = np.arange(first, first + count)
+    cells = np.stack([k % 8, (k // 8) % 8, k // 64], axis=1)
+    rgb = np.stack([(k % 7) / 8.0, (k % 5) / 8.0, (k % 3) / 4.0, np.ones(len(k))], axis=1).astype(np.float32)
+    return P((cells + 0.5) * voxel), rgb, (k % 11).astype(np.float32)
+
+
+def test_export_scratch_regrows(sp, orc):
+    """Two exports of one map object either side of a rehash: the compaction scratch (flags, positions, scan workspace) is sized
+    for 30 029 slots by the first and has to grow for the 60 013 of the second. rehash_threshold 0.01 grows the table at the first
+    add that finds more than 300 voxels: 64 voxels -> export -> +250 (314) -> +150 (rehash first, then 464) -> export."""
+    voxel = 0.5
+    gm, om = sp.VoxelHashMap(voxel), orc.voxel_hash_map(voxel)
+    gm.set_rehash_threshold(0.01)
+    om.set("rehash_threshold", 0.01)
+    first = 0
+    for frames, voxels, capacity in (((64,), 64, 30029), ((250, 150), 464, 60013)):
+        for count in frames:
+            pts, rgb, inten = one_per_voxel(first, count, voxel)
+            first += count
+            gm.add_point_cloud(cloud(sp, pts, rgb=rgb, intensities=inten))
+            om.add_point_cloud(pts, np.eye(4, dtype=np.float32), covs=None, rgb=rgb, intensities=inten)
+        assert gm.info("voxel_num") == om.info("voxel_num") == voxels and gm.info("capacity") == om.info("capacity") == capacity
+        g, o = gm.downsampling(distance=100.0), om.downsampling((0.0, 0.0, 0.0), 100.0)
+        gk, gp, gr, gi = by_key(g.voxel_keys.cpu().numpy().view(np.uint64), g.points.cpu().numpy(), g.rgb.cpu().numpy(),
+                                g.intensities.cpu().numpy())
+        ok, op, orgb, oi = by_key(o["keys"], o["points"], o["rgb"], o["intensities"])
+        assert len(gk) == voxels and np.array_equal(gk, ok) and not g.has_cov()
+        assert np.abs(gp - op).max() <= 2e-6 * 4.0  # coordinates below 4
+        assert np.abs(gr - orgb).max() <= 2e-6 and np.abs(gi - oi).max() <= 2e-4
+        for thr, ratio in ((1, 1.0), (2, 0.0)):  # counts: every voxel holds one point
+            gm.set_min_num_point(thr)
+            assert gm.compute_overlap_ratio(cloud(sp, one_per_voxel(0, first, voxel)[0])) == ratio
+        gm.set_min_num_point(1)
