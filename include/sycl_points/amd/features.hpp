@@ -8,6 +8,8 @@
 //   algorithms/filter/intensity_correction.hpp   : intensity_correction::correct_intensity
 //   algorithms/filter/intensity_gaussian.hpp     : intensity_gaussian::smooth_intensity
 //   algorithms/filter/intensity_local_mean_norm.hpp : intensity_local_mean_norm::normalize
+//   algorithms/filter/intensity_zscore.hpp       : intensity_zscore::compute
+//   algorithms/filter/outlier_removal_filter.hpp : filter::OutlierRemoval (statistical, radius)
 //   algorithms/common/filter_by_flags.hpp        : filter::FilterByFlags
 //   algorithms/common/transform.hpp              : transform::transform, transform_copy
 #pragma once
@@ -17,6 +19,7 @@
 #include <vector>
 #include <cctype>
 #include <cmath>
+#include <iostream>
 #include <limits>
 #include <numeric>
 #include <random>
@@ -905,6 +908,118 @@ private:
     std::vector<float> draws_;             // the weighted draws of the current call (its capacity is kept)
 };
 
+/// filter/outlier_removal_filter.hpp:13-242. The kNN search is the caller's KDTree as it is; the flags come from
+/// sp_outlier_statistical_flags (three launches, no wait in between: the reference waits after each of its three kernels and reads a
+/// USM word on the host twice) or sp_outlier_radius_flags on the same stream, and every attribute the reference moves (:224-241)
+/// goes through ONE sp_compact_by_flags_multi, which also leaves the new indices calculate_indices() returns. One count is read back.
+/// Kept from the reference: the squared neighbour distances are averaged and compared as they are, radius() compares the squared
+/// distance with `radius` itself (:178-188), too few points print its message and leave the cloud untouched. mean_k == 0 on a
+/// non-empty cloud is std::invalid_argument here (the reference divides by zero and keeps every point).
+class OutlierRemoval {
+public:
+    using Ptr = std::shared_ptr<OutlierRemoval>;
+    explicit OutlierRemoval(const sycl_utils::DeviceQueue& queue) : queue_(queue), filter_(queue) {
+        flags_ = std::make_shared<shared_vector<uint8_t>>(queue);
+        indices_ = std::make_shared<shared_vector<int32_t>>(queue);
+        local_mean_distance_ = std::make_shared<shared_vector<float>>(queue);
+        stats_ = std::make_shared<shared_vector<float>>(queue);
+        neighbors_ = std::make_shared<knn::KNNResult>();
+    }
+
+    /// :38-145 — a point is removed when the mean of its mean_k squared neighbour distances is above
+    /// global mean + stddev_mul_thresh * global standard deviation of those means
+    void statistical(PointCloudShared& cloud, knn::KDTree& tree, size_t mean_k, float stddev_mul_thresh, bool remove_from_tree = false) {
+        const size_t N = cloud.size();
+        if (N < mean_k) {
+            std::cerr << "Not enough points in the cloud [ points = " << N << ", mean_k = " << mean_k << " ]" << std::endl;
+            return;
+        }
+        if (N == 0) return;
+        hipStream_t st = queue_.stream();
+        tree.knn_search_async(cloud, mean_k, *neighbors_);
+        const size_t ws_bytes = sp_outlier_workspace_bytes(N);
+        detail::DeviceScratch ws(ws_bytes, st);
+        throw_on_error(sp_outlier_statistical_flags(neighbors_->distances->device_data(), N, mean_k, mean_k, stddev_mul_thresh,
+                                                    flags_->device_data_for_write(N), local_mean_distance_->device_data_for_write(N),
+                                                    stats_->device_data_for_write(4), ws.p, ws_bytes, st));
+        filter_by_flags(cloud);  // (synchronises: the scratch is idle when it leaves scope)
+        if (remove_from_tree) tree.remove_nodes_by_flags(get_flags(), calculate_indices());
+    }
+
+    /// :155-199 — a point is removed when its min_k-th neighbour other than itself is farther than `radius` (compared as the
+    /// reference compares: the squared distance against the radius)
+    void radius(PointCloudShared& cloud, knn::KDTree& tree, size_t min_k, float radius, bool remove_from_tree = false) {
+        const size_t N = cloud.size();
+        if (N < min_k) {
+            std::cerr << "Not enough points in the cloud [ points = " << N << ", min_k = " << min_k << " ]" << std::endl;
+            return;
+        }
+        if (N == 0) return;
+        tree.knn_search_async(cloud, min_k + 1, *neighbors_);  // (the tree holds the point itself: :162-163)
+        throw_on_error(sp_outlier_radius_flags(neighbors_->distances->device_data(), N, min_k + 1, min_k, radius,
+                                               flags_->device_data_for_write(N), queue_.stream()));
+        filter_by_flags(cloud);
+        if (remove_from_tree) tree.remove_nodes_by_flags(get_flags(), calculate_indices());
+    }
+
+    /// INCLUDE_FLAG for the points of the last call that stayed, REMOVE_FLAG for the others (:203)
+    const shared_vector<uint8_t>& get_flags() const { return *flags_; }
+    /// the new index of every point of the last call, -1 for a removed one (:208-211): left by the compaction itself
+    const shared_vector<int32_t>& calculate_indices() const {
+        if (indices_->size() != flags_->size()) filter_.calculate_indices(*flags_, *indices_);
+        return *indices_;
+    }
+    /// MI355X extension: the statistical filter's per-point means of the last call, and {global mean, variance, threshold, n}
+    const shared_vector<float>& get_local_mean_distance() const { return *local_mean_distance_; }
+    const shared_vector<float>& get_statistics() const { return *stats_; }
+
+private:
+    /// :224-241 — covariances, normals, colours, intensities, time stamps and points by flags_: one scan, one launch per attribute
+    void filter_by_flags(PointCloudShared& data) {
+        const size_t N = data.size();
+        hipStream_t st = queue_.stream();
+        const void* rows[6];
+        void* dst[6];
+        size_t bytes[6];
+        int na = 0;
+        auto add = [&](auto& src_ptr) {
+            using V = std::remove_reference_t<decltype(*src_ptr)>;
+            auto out = std::make_shared<V>(queue_);
+            rows[na] = src_ptr->device_data();
+            dst[na] = out->device_data_for_write(N);
+            bytes[na] = sizeof(typename V::value_type);
+            ++na;
+            return out;
+        };
+        const auto covs = data.has_cov() ? add(data.covs) : nullptr;
+        const auto normals = data.has_normal() ? add(data.normals) : nullptr;
+        const auto rgb = data.has_rgb() ? add(data.rgb) : nullptr;
+        const auto intensities = data.has_intensity() ? add(data.intensities) : nullptr;
+        const auto stamps = data.has_timestamps() ? add(data.timestamp_offsets) : nullptr;
+        const auto points = add(data.points);
+        const size_t ws_bytes = sp_compact_workspace_bytes(N);
+        detail::DeviceScratch ws(ws_bytes, st), count(4, st);
+        throw_on_error(sp_compact_by_flags_multi(rows, bytes, dst, na, N, flags_->device_data(), indices_->device_data_for_write(N),
+                                                 static_cast<uint32_t*>(count.p), ws.p, ws_bytes, st));
+        const size_t M = detail::read_u32(count.p, st);
+        auto take = [&](auto& dst_ptr, const auto& out) {
+            if (!out) return;
+            out->set_device_size(M);
+            dst_ptr = out;
+        };
+        take(data.covs, covs); take(data.normals, normals); take(data.rgb, rgb); take(data.intensities, intensities);
+        take(data.timestamp_offsets, stamps); take(data.points, points);
+    }
+
+    sycl_utils::DeviceQueue queue_;
+    FilterByFlags filter_;
+    knn::KNNResult::Ptr neighbors_;
+    shared_vector_ptr<uint8_t> flags_;
+    shared_vector_ptr<int32_t> indices_;
+    shared_vector_ptr<float> local_mean_distance_;
+    shared_vector_ptr<float> stats_;
+};
+
 }  // namespace filter
 
 // ================================================================================================ intensity filters
@@ -969,6 +1084,26 @@ inline void normalize(PointCloudShared& cloud, const knn::KNNResult& neighbors, 
 }
 
 }  // namespace intensity_local_mean_norm
+
+namespace intensity_zscore {
+
+/// filter/intensity_zscore.hpp:40-72 — cloud.intensities replaced by (I - local mean) / local sigma over the neighbours of
+/// `neighbors` (0 where sigma < sigma_min): a fresh vector written by sp_intensity_zscore and swapped in. The reference's checks, in
+/// its order and with its texts, are the library's; an empty cloud returns before them.
+inline void compute(PointCloudShared& cloud, const knn::KNNResult& neighbors, float sigma_min = 0.01f) {
+    const size_t N = cloud.size();
+    if (N == 0) return;
+    const size_t k = neighbors.k;
+    const bool usable = cloud.has_intensity() && k >= 3 && neighbors.indices;  // (otherwise the library reports what is missing)
+    auto tmp = std::make_shared<IntensityContainerShared>(cloud.queue);
+    throw_on_error(sp_intensity_zscore(cloud.has_intensity() ? cloud.intensities->device_data() : nullptr,
+                                       usable ? neighbors.indices->device_data() : nullptr, N, k, k, sigma_min,
+                                       usable ? tmp->device_data_for_write(N) : nullptr, cloud.queue.stream()));
+    cloud.queue.wait();
+    std::swap(cloud.intensities, tmp);
+}
+
+}  // namespace intensity_zscore
 
 // ================================================================================================ transform
 namespace transform {

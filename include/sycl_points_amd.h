@@ -480,6 +480,41 @@ int sp_intensity_correct(const float* points, const float* normals, const float*
 int sp_intensity_gaussian(const float* points, const float* intensities_in, const int32_t* knn_indices, size_t n, size_t k_stride,
                           size_t k_use, float sigma_azimuth, float sigma_elevation, float sigma_range, float mean_min,
                           float* intensities_out, void* stream);
+/* intensity_zscore::kernel::compute (filter/intensity_zscore.hpp:17-32): over the first k_use entries of row i of knn_indices
+ * (rows of k_stride entries), sum I and sum I^2 in index order, mean = sum I / float(k_use),
+ * var = fmax(sum I^2 / float(k_use) - mean * mean, 0), sigma = sqrt(var); out[i] = 0 when sigma < sigma_min, else
+ * (I[i] - mean) / sigma. A neighbour index outside [0, n) contributes nothing and the divisor stays k_use (the reference reads out
+ * of bounds; KNNResult pads with -1). intensities_out must not be intensities_in (SP_ERR_INVALID_ARGUMENT): the kernel reads
+ * neighbours; the caller swaps the new array in (:55-71). A null intensities_in, k_use < 3 -> SP_ERR_RUNTIME with the reference's
+ * texts (:44, :52), in its order; a null knn_indices / intensities_out, k_use > k_stride, n >= 2^31 -> SP_ERR_INVALID_ARGUMENT.
+ * n == 0: SP_OK before any check (:42). Every error is returned before any HIP call. Enqueue only. */
+int sp_intensity_zscore(const float* intensities_in, const int32_t* knn_indices, size_t n, size_t k_stride, size_t k_use,
+                        float sigma_min, float* intensities_out, void* stream);
+
+/* ------------------------------------------------------------------- outlier filters on a kNN result of the cloud on itself */
+
+/* OutlierRemoval::statistical's three kernels (filter/outlier_removal_filter.hpp:54-137) as three launches on `stream`, without the
+ * reference's three waits and its host reads in between. knn_d2: n rows of k_stride SQUARED distances, ascending, FLT_MAX padding
+ * (a KNNResult's distances); they are summed as they are (:78-84), so a padded row sums to inf or a huge value, as the reference's.
+ *   mean_dist_out[i] = (d2[i][0] + ... + d2[i][k_use-1]) / float(k_use), in index order
+ *   g = sum_i mean_dist_out[i] / float(n),  var = sum_i (g - mean_dist_out[i])^2 / float(n),  thr = g + stddev_mul * sqrt(var)
+ *   flags_out[i] = mean_dist_out[i] > thr ? 0 (remove) : 1 (keep);   stats_out = {g, var, thr, float(n)} (device memory)
+ * The two sums over i run in a fixed order (per lane, inside a wave, over the waves, over at most 1024 workgroups) that depends
+ * on n and k_stride only: no float atomics, the same bits from every call on the same input (the reference's sycl::reduction has
+ * no specified order). workspace: sp_outlier_workspace_bytes(n) bytes of device memory, 16-byte aligned.
+ * n == 0: SP_OK, nothing enqueued. A null pointer, a workspace that is too small, k_use == 0, k_use > k_stride, k_stride > 2048,
+ * n >= 2^31 -> SP_ERR_INVALID_ARGUMENT before any HIP call. The caller compacts with sp_compact_by_flags_multi on the same stream.
+ * Enqueue only. */
+size_t sp_outlier_workspace_bytes(size_t n);
+int sp_outlier_statistical_flags(const float* knn_d2, size_t n, size_t k_stride, size_t k_use, float stddev_mul,
+                                 uint8_t* flags_out, float* mean_dist_out /* n floats */, float* stats_out /* 4 floats, device */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* OutlierRemoval::radius's kernel (filter/outlier_removal_filter.hpp:168-191): flags_out[i] = knn_d2[i][column] > radius ? 0 : 1
+ * with column = min_k of rows of min_k + 1 entries. The SQUARED distance is compared with `radius` itself, as the reference
+ * compares them (:178, :187-188). n == 0: SP_OK. A null pointer, column >= k_stride, n >= 2^31 -> SP_ERR_INVALID_ARGUMENT before
+ * any HIP call. Enqueue only. */
+int sp_outlier_radius_flags(const float* knn_d2, size_t n, size_t k_stride, size_t column, float radius, uint8_t* flags_out,
+                            void* stream);
 
 /* BoxFilterOperator kernel (filter/preprocess_operator/box_filter_operator.hpp:36-44, common.hpp:15-25, K10):
  * flags_out[i] = 1 keep / 0 remove. */

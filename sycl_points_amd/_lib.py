@@ -174,6 +174,10 @@ SIGNATURES = {
     "sp_angle_incidence_flags": (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp, _vp]),
     "sp_intensity_correct": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp]),
     "sp_intensity_gaussian": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _f, _f, _f, _f, _vp, _vp]),
+    "sp_intensity_zscore": (_i, [_vp, _vp, _sz, _sz, _sz, _f, _vp, _vp]),
+    "sp_outlier_workspace_bytes": (_sz, [_sz]),
+    "sp_outlier_statistical_flags": (_i, [_vp, _sz, _sz, _sz, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_outlier_radius_flags": (_i, [_vp, _sz, _sz, _sz, _f, _vp, _vp]),
     "sp_relative_twist_host": (None, [_vp, _vp, _vp]),
     "sp_imu_preint_create": (_i, [C.POINTER(ImuParams), C.POINTER(_vp)]),
     "sp_imu_preint_destroy": (None, [_vp]),

@@ -10,6 +10,7 @@ device memory, streams and torch.distributed only — all compute goes through l
 """
 import ctypes as C
 import enum
+import sys
 import weakref
 from dataclasses import dataclass, field
 
@@ -1132,6 +1133,111 @@ def normalize_intensity_local_mean(cloud, neighbors, sigma_azimuth, sigma_elevat
             raise SpError(2, "[intensity_local_mean_norm::normalize] mean_min must be positive")
         mean_min = 1.0  # (selects the normalisation's texts)
     _intensity_gaussian(cloud, neighbors, sigma_azimuth, sigma_elevation, sigma_range, mean_min, k_limit)
+
+
+def intensity_zscore(cloud, neighbors, sigma_min=0.01):
+    """intensity_zscore::compute (filter/intensity_zscore.hpp:40-72): cloud.intensities replaced by (I - local mean) / local sigma
+    over the neighbours of `neighbors` (a KNNResult of the cloud on itself, or its index tensor), 0 where sigma < sigma_min. The
+    reference's checks in its order (sp_intensity_zscore reports them); an empty cloud returns before them."""
+    n = cloud.size()
+    if n == 0:
+        return
+    idx = neighbors.indices if isinstance(neighbors, KNNResult) else neighbors
+    k = int(idx.shape[1]) if idx is not None and idx.dim() == 2 else 0
+    if k and (idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape[0] != n):
+        raise SpError(1, "expected a contiguous int32 (N, k) tensor of neighbour indices")
+    inten = _dev_f32(cloud.intensities) if cloud.has_intensity() else None
+    out = None if inten is None else torch.empty_like(inten)
+    check(_lib.lib().sp_intensity_zscore(_ptr(inten), _ptr(idx) if k else None, n, k, k, sigma_min, _ptr(out), _stream()))
+    cloud.intensities = out  # (the reference swaps a fresh vector in)
+
+
+class OutlierRemoval:
+    """filter::OutlierRemoval (filter/outlier_removal_filter.hpp:13-242). statistical() and radius() filter `cloud` in place:
+    the kNN search is the caller's KDTree as it is, the flags come from sp_outlier_statistical_flags / sp_outlier_radius_flags on
+    the same stream (the reference waits after each of its kernels), and every attribute goes through one
+    sp_compact_by_flags_multi, which also leaves the indices calculate_indices() returns. Kept from the reference: the SQUARED
+    neighbour distances are averaged and compared as they are, radius() compares the squared distance with `radius` itself
+    (:178-188), and too few points print its message and leave the cloud untouched."""
+
+    _ATTRS = ("covs", "normals", "rgb", "intensities", "timestamp_offsets", "points")  # the reference's order (:224-241)
+
+    def __init__(self):
+        self.neighbors = KNNResult()
+        self.flags = None
+        self.indices = None
+        self.local_mean_distance = None
+        self.statistics = None  # device tensor: global mean, variance, threshold, n
+
+    def statistical(self, cloud, tree, mean_k, stddev_mul_thresh, remove_from_tree=False):
+        n = cloud.size()
+        if n < mean_k:
+            print(f"Not enough points in the cloud [ points = {n}, mean_k = {mean_k} ]", file=sys.stderr)
+            return
+        if n == 0:
+            return
+        L = _lib.lib()
+        tree.knn_search_async(cloud, mean_k, self.neighbors)
+        dev = cloud.points.device
+        self.flags = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.local_mean_distance = torch.empty(n, dtype=torch.float32, device=dev)
+        self.statistics = torch.empty(4, dtype=torch.float32, device=dev)
+        nbytes = L.sp_outlier_workspace_bytes(n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(L.sp_outlier_statistical_flags(_ptr(self.neighbors.distances), n, mean_k, mean_k, stddev_mul_thresh, _ptr(self.flags),
+                                             _ptr(self.local_mean_distance), _ptr(self.statistics), _ptr(ws), nbytes, _stream()))
+        self._filter_by_flags(cloud)
+        if remove_from_tree:
+            tree.remove_nodes_by_flags(self.get_flags(), self.calculate_indices())
+
+    def radius(self, cloud, tree, min_k, radius, remove_from_tree=False):
+        n = cloud.size()
+        if n < min_k:
+            print(f"Not enough points in the cloud [ points = {n}, min_k = {min_k} ]", file=sys.stderr)
+            return
+        if n == 0:
+            return
+        tree.knn_search_async(cloud, min_k + 1, self.neighbors)  # (the tree holds the point itself: :162-163)
+        self.flags = torch.empty(n, dtype=torch.uint8, device=cloud.points.device)
+        check(_lib.lib().sp_outlier_radius_flags(_ptr(self.neighbors.distances), n, min_k + 1, min_k, radius, _ptr(self.flags),
+                                                 _stream()))
+        self._filter_by_flags(cloud)
+        if remove_from_tree:
+            tree.remove_nodes_by_flags(self.get_flags(), self.calculate_indices())
+
+    def get_flags(self):
+        """1 for the points of the last call that stayed, 0 for the removed ones"""
+        return self.flags
+
+    def calculate_indices(self):
+        """the new index of every point of the last call, -1 for a removed one (left by the compaction)"""
+        return self.indices
+
+    def _filter_by_flags(self, cloud):
+        L = _lib.lib()
+        n = cloud.size()
+        has = dict(points=True, covs=cloud.has_cov(), normals=cloud.has_normal(), rgb=cloud.has_rgb(),
+                   intensities=cloud.has_intensity(), timestamp_offsets=cloud.has_timestamps())
+        names = [k for k in OutlierRemoval._ATTRS if has[k]]
+        src = [getattr(cloud, k) for k in names]
+        for t in src:
+            if not (t.is_cuda and t.is_contiguous()):
+                raise SpError(1, "expected contiguous CUDA tensors")
+        dst = [torch.empty_like(t) for t in src]
+        na = len(src)
+        rows = (C.c_void_p * na)(*[t.data_ptr() for t in src])
+        rows_out = (C.c_void_p * na)(*[t.data_ptr() for t in dst])
+        row_bytes = (C.c_size_t * na)(*[t.element_size() * (t.numel() // n) for t in src])
+        dev = cloud.points.device
+        self.indices = torch.empty(n, dtype=torch.int32, device=dev)
+        n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = L.sp_compact_workspace_bytes(n)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        check(L.sp_compact_by_flags_multi(rows, row_bytes, rows_out, na, n, _ptr(self.flags), _ptr(self.indices), _ptr(n_out),
+                                          _ptr(ws), nbytes, _stream()))
+        m = int(n_out.item())
+        for k, t in zip(names, dst):
+            setattr(cloud, k, t[:m])
 
 
 @dataclass
