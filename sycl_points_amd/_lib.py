@@ -301,6 +301,11 @@ INTERNAL_SIGNATURES = {
     "sp_internal_align_searched_log": (_vp, [_vp, _vp]),
     "sp_internal_radix_sort_workspace_bytes": (_sz, [_sz]),
     "sp_internal_radix_sort_u32": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]),
+    "sp_internal_radix_sort_u32_ex": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, C.c_uint, _i, _vp, _sz, _vp, _vp]),
+    "sp_internal_radix_first_pass": (None, [_sz, C.c_uint, _vp]),
+    "sp_internal_radix_sort_u64": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]),
+    "sp_internal_exclusive_scan_workspace_bytes": (_sz, [_sz]),
+    "sp_internal_exclusive_scan_u32": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "sp_internal_atan2f_host": (None, [_vp, _vp, _sz, _vp]),
     "sp_internal_fps": (_i, [_i, _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }

@@ -489,3 +489,33 @@ extern "C" int sp_internal_radix_sort_u32(uint32_t* keys_a, uint32_t* keys_b, ui
     if (result_in_b_out) *result_in_b_out = in_b ? 1 : 0;
     return rc;
 }
+extern "C" int sp_internal_radix_sort_u32_ex(uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
+                                             unsigned bits, unsigned first_bit, int first_hist_ready, void* workspace,
+                                             size_t workspace_bytes, int* result_in_b_out, void* stream) {
+    bool in_b = false;
+    const int rc = sp::radix_sort_pairs_u32(keys_a, keys_b, vals_a, vals_b, n, bits, workspace, workspace_bytes, &in_b,
+                                            sp::as_stream(stream), first_bit, first_hist_ready != 0);
+    if (result_in_b_out) *result_in_b_out = in_b ? 1 : 0;
+    return rc;
+}
+extern "C" void sp_internal_radix_first_pass(size_t n, unsigned bits, unsigned* out4) {
+    const sp::RadixFirstPass p = sp::radix_first_pass(n, bits);
+    out4[0] = p.tiles;
+    out4[1] = p.tile_keys;
+    out4[2] = p.digit_bits;
+    out4[3] = p.mask;
+}
+extern "C" int sp_internal_radix_sort_u64(uint64_t* keys_a, uint64_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
+                                          unsigned bits, void* workspace, size_t workspace_bytes, int* result_in_b_out,
+                                          void* stream) {
+    bool in_b = false;
+    const int rc = sp::radix_sort_pairs_u64(keys_a, keys_b, vals_a, vals_b, n, bits, workspace, workspace_bytes, &in_b,
+                                            sp::as_stream(stream));
+    if (result_in_b_out) *result_in_b_out = in_b ? 1 : 0;
+    return rc;
+}
+extern "C" size_t sp_internal_exclusive_scan_workspace_bytes(size_t n) { return sp::exclusive_scan_u32_workspace_bytes(n); }
+extern "C" int sp_internal_exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* total_out_or_null,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    return sp::exclusive_scan_u32(in, out, n, total_out_or_null, workspace, workspace_bytes, sp::as_stream(stream));
+}

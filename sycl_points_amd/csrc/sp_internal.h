@@ -66,6 +66,21 @@ const uint32_t* sp_internal_align_searched_log(void* workspace, size_t* n_entrie
 size_t sp_internal_radix_sort_workspace_bytes(size_t n);
 int sp_internal_radix_sort_u32(uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
                                unsigned bits, void* workspace, size_t workspace_bytes, int* result_in_b_out, void* stream);
+/* The same sort by the key bits [first_bit, bits) only, and with the first pass's tile histograms already at the start of the
+ * workspace (first_hist_ready != 0: hist[digit * tiles + tile], laid out as sp_internal_radix_first_pass says; first_bit 0). */
+int sp_internal_radix_sort_u32_ex(uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
+                                  unsigned bits, unsigned first_bit, int first_hist_ready, void* workspace,
+                                  size_t workspace_bytes, int* result_in_b_out, void* stream);
+/* radix_first_pass(n, bits) (csrc/radix_sort.h) on the host: out4 = {tiles, tile_keys, digit_bits, mask}. */
+void sp_internal_radix_first_pass(size_t n, unsigned bits, unsigned* out4);
+/* The sort of (u64 key, u32 value) pairs on the low `bits` <= 64 key bits; workspace as for the u32 sort. */
+int sp_internal_radix_sort_u64(uint64_t* keys_a, uint64_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, size_t n,
+                               unsigned bits, void* workspace, size_t workspace_bytes, int* result_in_b_out, void* stream);
+/* The one-launch exclusive scan (csrc/radix_sort.hip, csrc/sp_lookback.h): device pointers, in == out allowed, the total
+ * below 2^30; *total_out_or_null (device) receives the total. */
+size_t sp_internal_exclusive_scan_workspace_bytes(size_t n);
+int sp_internal_exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* total_out_or_null, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 /* sp_math.h's atan2f (the one the polar keys are made of) on the host, element by element: out[i] = atan2(y[i], x[i]). */
 void sp_internal_atan2f_host(const float* y, const float* x, size_t n, float* out);
 /* sp_farthest_point_sampling in a form of the caller's choice (low byte): 0 the library's choice (what the public entry does),
