@@ -138,6 +138,9 @@ CASES = [
     dict(opt="DOGLEG", reg_type="GICP", loss="NONE", scale=10.0),
     dict(opt="DOGLEG", reg_type="POINT_TO_DISTRIBUTION", loss="NONE", scale=10.0),
     dict(opt="GN", reg_type="POINT_TO_DISTRIBUTION", loss="CAUCHY", scale=0.3),
+    # TUKEY: the only loss with a hard zero branch (r >= scale -> weight 0) and the only powf
+    dict(opt="LM", reg_type="GICP", loss="TUKEY", scale=0.5),
+    dict(opt="GN", reg_type="POINT_TO_DISTRIBUTION", loss="TUKEY", scale=0.5),
 ]
 
 
