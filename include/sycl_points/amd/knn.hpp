@@ -3,6 +3,7 @@
 //   algorithms/knn/knn.hpp        : KNNBase (the operator boundary Registration::align sits on)
 //   algorithms/knn/bruteforce.hpp : knn_search_bruteforce
 //   algorithms/knn/kdtree.hpp     : KDTree (host build with the reference's split rule, device search)
+//   algorithms/knn/octree.hpp     : Octree (device build, device search, k <= 100)
 //   + GridKNN: an MI355X-native KNNBase (device-built uniform grid), no counterpart file in the reference.
 #pragma once
 #include <atomic>
@@ -240,6 +241,67 @@ private:
     uint64_t id_ = 0;
     std::shared_ptr<PointContainerShared> built_on_;  // the cloud's point container at build(), and its generation then
     uint64_t built_generation_ = 0;
+};
+
+/// algorithms/knn/octree.hpp:27-844 over the library's device-built octree (sp_octree_*, csrc/octree.hip): the reference's
+/// constructor, build, knn_search_async, accessors and remove_nodes_by_flags. Exact kNN for k <= 100; rows are bit-identical to
+/// knn_search_bruteforce (ties to the lowest index, where the reference's heap leaves them to its traversal).
+class Octree : public KNNBase {
+public:
+    using Ptr = std::shared_ptr<Octree>;
+
+    /// octree.hpp:193-210: an empty tree, ready to be built
+    Octree(const sycl_utils::DeviceQueue& queue, float resolution, size_t max_points_per_node)
+        : queue_(queue), resolution_(resolution), max_points_per_node_(max_points_per_node) {
+        throw_on_error(sp_octree_create(nullptr, 0, resolution, max_points_per_node, queue.stream(), &tree_));
+    }
+    ~Octree() override { sp_octree_destroy(tree_); }
+    Octree(const Octree&) = delete;
+    Octree& operator=(const Octree&) = delete;
+
+    /// octree.hpp:581-596
+    static Ptr build(const sycl_utils::DeviceQueue& queue, const PointCloudShared& points, float resolution,
+                     size_t max_points_per_node = 32) {
+        auto t = std::make_shared<Octree>(queue, resolution, max_points_per_node);
+        if (!points.points) throw std::runtime_error("[Octree::build_from_cloud] Point cloud is not initialised");
+        sp_octree* built = nullptr;
+        throw_on_error(sp_octree_create(points.points_device(), points.size(), resolution, max_points_per_node, queue.stream(), &built));
+        sp_octree_destroy(t->tree_);
+        t->tree_ = built;
+        return t;
+    }
+    const sp_octree* handle() const { return tree_; }
+
+    /// octree.hpp:599-630
+    sycl_utils::events knn_search_async(const PointCloudShared& queries, const size_t k, KNNResult& result,
+                                        const std::vector<sycl_utils::event>& = {},
+                                        const TransformMatrix& transT = TransformMatrix::Identity()) const override {
+        const size_t nq = queries.size();
+        if (k > 100) throw std::runtime_error("[Octree::knn_search_async] Requested neighbor count exceeds the supported maximum");
+        detail::prepare_result(queue_, result, nq, k);
+        if (nq == 0 || k == 0) return sycl_utils::events();
+        throw_on_error(sp_octree_search(tree_, queries.points_device(), nq, k, transT.data(), 0,
+                                        result.indices->device_data_for_write(nq * k),
+                                        result.distances->device_data_for_write(nq * k), queue_.stream()));
+        return sycl_utils::events(queue_.stream());
+    }
+
+    [[nodiscard]] float resolution() const { return resolution_; }
+    [[nodiscard]] size_t max_points_per_node() const { return max_points_per_node_; }
+    [[nodiscard]] size_t size() const { return sp_octree_size(tree_); }
+
+    /// octree.hpp:276-380
+    void remove_nodes_by_flags(const shared_vector<uint8_t>& flags, const shared_vector<int32_t>& indices) {
+        if (flags.size() != indices.size())
+            throw std::runtime_error("[Octree::remove_nodes_by_flags] flags and indices must have the same size");
+        throw_on_error(sp_octree_remove_by_flags(tree_, flags.device_data(), indices.device_data(), flags.size(), queue_.stream()));
+    }
+
+private:
+    sycl_utils::DeviceQueue queue_;
+    float resolution_;
+    size_t max_points_per_node_;
+    sp_octree* tree_ = nullptr;
 };
 
 /// MI355X-native KNNBase: exact kNN on a device-built uniform grid (sp_grid_*). Bit-identical to

@@ -223,6 +223,46 @@ int sp_bvh_remove_by_flags(sp_bvh* bvh, const uint8_t* flags, const int32_t* new
  * for radius search / lazy delete) does not depend on the source cloud still being there. */
 int sp_bvh_export_points(const sp_bvh* bvh, float* points_out, void* stream);
 
+/* ------------------------------------------------------------------- device-built octree (k up to 100) */
+
+/* knn::Octree (algorithms/knn/octree.hpp:27-844) built ENTIRELY on the device (csrc/octree.hip states how), for lists of up to
+ * 100 neighbours: the hierarchy (sp_bvh_*) stops at 32, the grid and the brute-force search at 20.
+ *   sp_octree_create   Octree::build (octree.hpp:233-274, 388-475, 581-596): the box of the finite points widened by
+ *                      max(1e-5, resolution / 2) per side (:267-269); a node splits while it holds more than max_points_per_node
+ *                      points, its cell's longest edge exceeds `resolution` and its depth is below 21 (:416-418; the reference
+ *                      allows 32, which shows only in leaves of coincident points). Non-finite points go into no leaf and are never
+ *                      neighbours, as in sp_knn_bruteforce. Point i gets the id i. Allocates and synchronises; n == 0: an empty
+ *                      tree, no device work.
+ *   sp_octree_size     size() (:118): the points still kept.
+ *   sp_octree_info     SP_OCTREE_NODES, _LEAVES, _DEPTH (the deepest node), _NEXT_ID (the ids in use are below it,
+ *                      next_point_id_ :273, :368-379), _SLOTS (entries of sp_octree_export's point_ids_out).
+ *   sp_octree_search   knn_search_async (:599-630, 684-844): exact kNN, 0 <= k <= 100, queries searched at transT * q (NULL:
+ *                      identity; host or device matrix as for sp_kdtree_search); rows as KNNResult (knn/result.hpp:12-34):
+ *                      ascending by (distance, index), -1 / FLT_MAX padded, every entry written; ties to the lowest index
+ *                      (bit-identical to sp_knn_bruteforce; the reference's heap leaves the order of ties to its traversal and
+ *                      its 32-entry stack drops nodes when full: nothing is dropped here). k > 100 (:629), a null handle or null
+ *                      outputs: SP_ERR_INVALID_ARGUMENT before any device work. Enqueue only.
+ *   sp_octree_remove_by_flags  remove_nodes_by_flags (:276-380): a stored point with id p is kept iff flags[p] == 1 and
+ *                      new_indices[p] >= 0, and is then relabelled new_indices[p]; the others can no longer be found (no
+ *                      rebuild; the boxes stay valid supersets). n_flags must equal SP_OCTREE_NEXT_ID (:285-289) and every new
+ *                      id of a kept point be below it (:329-332), else SP_ERR_RUNTIME with the reference's text. Afterwards
+ *                      SP_OCTREE_NEXT_ID = max(largest new id + 1, points kept) (:368-379); nothing kept: the empty tree with
+ *                      next id 0 (:363-366). Synchronises (one 8-byte read-back).
+ *   sp_octree_export   for tests and bindings: nodes_out receives 64 bytes per node (:65-80) — box min xyz, box max xyz (the
+ *                      tight box of the points below, floats), is_leaf, depth, then the eight child indices (-1: none; always
+ *                      above the node's own) or start, count and six zeros; point_ids_out the ids in leaf order (-1: removed).
+ *                      Either may be NULL. Device pointers; enqueue only. */
+typedef struct sp_octree sp_octree;
+enum { SP_OCTREE_NODES = 0, SP_OCTREE_LEAVES = 1, SP_OCTREE_DEPTH = 2, SP_OCTREE_NEXT_ID = 3, SP_OCTREE_SLOTS = 4 };
+int sp_octree_create(const float* points, size_t n, float resolution, size_t max_points_per_node, void* stream, sp_octree** out);
+void sp_octree_destroy(sp_octree* octree);
+size_t sp_octree_size(const sp_octree* octree);
+int sp_octree_info(const sp_octree* octree, int what, uint64_t* out);
+int sp_octree_search(const sp_octree* octree, const float* queries, size_t nq, size_t k, const float* transT, int transT_on_device,
+                     int32_t* idx_out, float* d2_out, void* stream);
+int sp_octree_remove_by_flags(sp_octree* octree, const uint8_t* flags, const int32_t* new_indices, size_t n_flags, void* stream);
+int sp_octree_export(const sp_octree* octree, void* nodes_out, int32_t* point_ids_out, void* stream);
+
 /* ------------------------------------------------------------------- accelerated KDTree (which structure answers) */
 
 /* KDTree (knn/kdtree.hpp:142-766) with the structure chosen per search: the one object behind the facade's KDTree and

@@ -150,6 +150,13 @@ SIGNATURES = {
     "sp_bvh_radius_search": (_i, [_vp, _vp, _sz, _sz, _f, _vp, _i, _vp, _vp, _vp]),
     "sp_bvh_remove_by_flags": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "sp_bvh_export_points": (_i, [_vp, _vp, _vp]),
+    "sp_octree_create": (_i, [_vp, _sz, _f, _sz, _vp, C.POINTER(_vp)]),
+    "sp_octree_destroy": (None, [_vp]),
+    "sp_octree_size": (_sz, [_vp]),
+    "sp_octree_info": (_i, [_vp, _i, C.POINTER(C.c_uint64)]),
+    "sp_octree_search": (_i, [_vp, _vp, _sz, _sz, _vp, _i, _vp, _vp, _vp]),
+    "sp_octree_remove_by_flags": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "sp_octree_export": (_i, [_vp, _vp, _vp, _vp]),
     "sp_knn_tree_create": (_i, [_vp, _sz, _sz, _vp, C.POINTER(_vp)]),
     "sp_knn_tree_destroy": (None, [_vp]),
     "sp_knn_tree_backend": (_i, [_vp, _sz, _sz, _vp, _i, _i, _vp, C.POINTER(_i)]),

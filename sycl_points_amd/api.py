@@ -343,6 +343,69 @@ class BVH(KNNBase):
         check(_lib.lib().sp_bvh_remove_by_flags(self._h, _ptr(flags), _ptr(indices), flags.shape[0], _stream()))
 
 
+class Octree(KNNBase):
+    """algorithms/knn/octree.hpp:27-844 on a device-built octree (csrc/octree.hip, sp_octree_*): exact kNN for k <= 100, rows
+    bit-identical to knn_search_bruteforce (ties to the lowest index), lazy removal."""
+
+    _INFO = {"nodes": 0, "leaves": 1, "depth": 2, "next_id": 3, "slots": 4}  # SP_OCTREE_*
+
+    def __init__(self, handle, device, resolution, max_points_per_node):
+        self._h = handle
+        self.device = device
+        self.resolution = resolution
+        self.max_points_per_node = max_points_per_node
+
+    @staticmethod
+    def build(points, resolution, max_points_per_node=32):
+        p = _dev_f32(_points_of(points), 4)
+        h = C.c_void_p()
+        check(_lib.lib().sp_octree_create(_ptr(p), p.shape[0], resolution, max_points_per_node, _stream(), C.byref(h)))
+        return Octree(h, p.device, resolution, max_points_per_node)
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().sp_octree_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def size(self):
+        return int(_lib.lib().sp_octree_size(self._h))
+
+    def info(self, what):
+        """sp_octree_info: 'nodes' | 'leaves' | 'depth' | 'next_id' | 'slots'."""
+        v = C.c_uint64()
+        check(_lib.lib().sp_octree_info(self._h, Octree._INFO[what], C.byref(v)))
+        return int(v.value)
+
+    def knn_search_async(self, queries, k, result, transT=None):
+        q = _dev_f32(_points_of(queries), 4)
+        if k > 100:  # octree.hpp:629
+            raise SpError(2, "[Octree::knn_search_async] Requested neighbor count exceeds the supported maximum")
+        result.resize(q.shape[0], k, q.device)
+        if q.shape[0] == 0 or k == 0:  # octree.hpp:603-611
+            return
+        tp, on_dev, keep = _trans_arg(transT)
+        check(_lib.lib().sp_octree_search(self._h, _ptr(q), q.shape[0], k, tp, on_dev, _ptr(result.indices),
+                                          _ptr(result.distances), _stream()))
+
+    def remove_nodes_by_flags(self, flags, indices):
+        """octree.hpp:276-380: flags 1 = keep, a kept point p is relabelled indices[p]."""
+        if flags.shape[0] != indices.shape[0]:
+            raise SpError(2, "[Octree::remove_nodes_by_flags] flags and indices must have the same size")
+        check(_lib.lib().sp_octree_remove_by_flags(self._h, _ptr(flags), _ptr(indices), flags.shape[0], _stream()))
+
+    def export(self):
+        """(nodes, ids) as numpy arrays: nodes is (n_nodes, 16) int32 — words 0-5 the float bits of the box (min xyz, max xyz),
+        6 is_leaf, 7 depth, 8-15 the child indices (-1: none) or start, count and zeros; ids the stored ids in leaf order."""
+        nodes = torch.empty((self.info("nodes"), 16), dtype=torch.int32, device=self.device)
+        ids = torch.empty((self.info("slots"),), dtype=torch.int32, device=self.device)
+        check(_lib.lib().sp_octree_export(self._h, _ptr(nodes), _ptr(ids), _stream()))
+        torch.cuda.current_stream().synchronize()
+        return nodes.cpu().numpy(), ids.cpu().numpy()
+
+
 class GridKNN(KNNBase):
     """MI355X-native KNNBase: exact kNN on a device-built uniform grid (csrc/grid.hip); bit-identical to
     knn_search_bruteforce. `points_per_cell` tunes the cell size (about 2 for k = 1, about 6-8 for k = 20)."""
