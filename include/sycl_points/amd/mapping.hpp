@@ -1,8 +1,8 @@
 // sycl_points facade for MI355X — algorithms/mapping/voxel_hash_map.hpp:22-250 (VoxelHashMap) over the sp_vhm_* entry
 // points. Same public surface as the reference: constructor (queue, voxel_size), the five setters / getters, clear,
 // add_point_cloud(cloud, sensor_pose), downsampling(result, center, distance), compute_overlap_ratio, remove_old_data.
-// algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 (OccupancyGridMap) over the sp_ogm_* entry points: the reference's public
-// signatures without extract_visible_points, which the reference marks experimental and no pipeline calls.
+// algorithms/mapping/occupancy_grid_map.hpp:27-472 (OccupancyGridMap) over the sp_ogm_* entry points: the reference's public
+// signatures.
 // The tables live in HBM inside the library objects; clouds go in and come out through their device mirrors.
 #pragma once
 #include "core.hpp"
@@ -13,22 +13,22 @@ namespace mapping {
 
 namespace detail {
 
-/// The averaged export of either map (sp_vhm_downsampling, sp_ogm_extract_occupied_points: one shape): `result`'s device arrays sized
-/// for the map's voxels, written by the entry point, cut to the rows that came out; an attribute the map does not hold is cleared.
+/// The averaged export of either map (sp_vhm_downsampling, sp_ogm_extract_occupied_points, sp_ogm_extract_visible_points: one shape
+/// after their own leading arguments, which `call` binds): `result`'s device arrays sized for the map's voxels, written by the entry
+/// point, cut to the rows that came out; an attribute the map does not hold is cleared.
+/// call(points, covs, rgb, intensities, capacity, &n) -> the entry point's status.
 static_assert(+SP_VHM_INFO_VOXEL_NUM == +SP_OGM_INFO_VOXEL_NUM && +SP_VHM_INFO_HAS_COV == +SP_OGM_INFO_HAS_COV &&
               +SP_VHM_INFO_HAS_RGB == +SP_OGM_INFO_HAS_RGB && +SP_VHM_INFO_HAS_INTENSITY == +SP_OGM_INFO_HAS_INTENSITY);
-template <class Handle>
-void mean_rows(int (*entry_point)(Handle*, const float*, float, float*, float*, float*, float*, uint64_t*, size_t, size_t*, void*),
-               size_t (*info)(const Handle*, int), Handle* h, const float (&xyz)[3], const float distance, PointCloudShared& result,
-               void* stream) {
+template <class Handle, class Call>
+void mean_rows(Call&& call, size_t (*info)(const Handle*, int), const Handle* h, PointCloudShared& result) {
     const size_t cap = info(h, SP_VHM_INFO_VOXEL_NUM);
     if (cap == 0) { result.clear(); return; }
     const bool has_cov = info(h, SP_VHM_INFO_HAS_COV), has_rgb = info(h, SP_VHM_INFO_HAS_RGB), has_int = info(h, SP_VHM_INFO_HAS_INTENSITY);
     size_t n = 0;
-    throw_on_error(entry_point(h, xyz, distance, reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
-                               has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
-                               has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
-                               has_int ? result.intensities->device_data_for_write(cap) : nullptr, nullptr, cap, &n, stream));
+    throw_on_error(call(reinterpret_cast<float*>(result.points->device_data_for_write(cap)),
+                        has_cov ? reinterpret_cast<float*>(result.covs->device_data_for_write(cap)) : nullptr,
+                        has_rgb ? reinterpret_cast<float*>(result.rgb->device_data_for_write(cap)) : nullptr,
+                        has_int ? result.intensities->device_data_for_write(cap) : nullptr, cap, &n));
     result.points->set_device_size(n);
     if (has_cov) result.covs->set_device_size(n); else result.covs->clear();
     if (has_rgb) result.rgb->set_device_size(n); else result.rgb->clear();
@@ -87,7 +87,9 @@ public:
     /// voxel_hash_map.hpp:146-190 — voxel means whose centroid lies in the box center +- distance.
     void downsampling(PointCloudShared& result, const Eigen::Vector3f& center, const float distance = 100.0f) {
         const float c[3] = {center.x(), center.y(), center.z()};
-        detail::mean_rows(sp_vhm_downsampling, sp_vhm_info, h_, c, distance, result, queue_.stream());
+        detail::mean_rows([&](float* p, float* cv, float* rgb, float* in, size_t cap, size_t* n) {
+            return sp_vhm_downsampling(h_, c, distance, p, cv, rgb, in, nullptr, cap, n, queue_.stream());
+        }, sp_vhm_info, h_, result);
     }
 
     /// voxel_hash_map.hpp:196-246
@@ -158,7 +160,20 @@ public:
                                  const float max_distance = 100.0f) const {
         const Eigen::Vector3f t = sensor_pose.translation();
         const float c[3] = {t.x(), t.y(), t.z()};
-        detail::mean_rows(sp_ogm_extract_occupied_points, sp_ogm_info, h_, c, max_distance, result, queue_.stream());
+        detail::mean_rows([&](float* p, float* cv, float* rgb, float* in, size_t cap, size_t* n) {
+            return sp_ogm_extract_occupied_points(h_, c, max_distance, p, cv, rgb, in, nullptr, cap, n, queue_.stream());
+        }, sp_ogm_info, h_, result);
+    }
+
+    /// occupancy_grid_map.hpp:183-411 — of those, the voxels within max_distance (L2) inside the frustum of the two fields of view
+    /// (radians, around the sensor's x axis) that no other occupied voxel hides; in table-slot order. On an empty map every
+    /// attribute of `result` is resized to 0 (the reference resizes points and covariances only).
+    void extract_visible_points(PointCloudShared& result, const Eigen::Isometry3f& sensor_pose, float max_distance,
+                                float horizontal_fov, float vertical_fov) const {
+        detail::mean_rows([&](float* p, float* cv, float* rgb, float* in, size_t cap, size_t* n) {
+            return sp_ogm_extract_visible_points(h_, sensor_pose.matrix().data(), max_distance, horizontal_fov, vertical_fov, p, cv,
+                                                 rgb, in, nullptr, cap, n, queue_.stream());
+        }, sp_ogm_info, h_, result);
     }
 
     /// occupancy_grid_map.hpp:417-472

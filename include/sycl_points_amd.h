@@ -1116,7 +1116,7 @@ int sp_vhm_overlap_ratio(const sp_voxel_hash_map* map, const float* points, size
                          float* ratio_out_host, void* stream);
 int sp_vhm_remove_old_data(sp_voxel_hash_map* map, void* stream);
 
-/* ---------------------------------------------------------------- OccupancyGridMap (mapping/occupancy_grid_map.hpp:27-190, 417)
+/* ---------------------------------------------------------------- OccupancyGridMap (mapping/occupancy_grid_map.hpp:27-472)
  * The other submap of Submap::build_submap: the VoxelHashMap table (same key, same double hashing, same capacity ladder; 128
  * probes; removed slots keep a `deleted` key) whose voxels also carry a log-odds occupancy. Per voxel: sums of the map-frame hit
  * points, of log(R C R^T), of rgb and of intensity, hit_count, miss_count, log_odds, the frame of the last update.
@@ -1137,6 +1137,16 @@ int sp_vhm_remove_old_data(sp_voxel_hash_map* map, void* stream);
  *                        threshold and a centroid within max_distance (L-infinity) of sensor_xyz -> mean point (w = 1), exp of
  *                        the mean log-covariance, mean rgb / intensity, in table-slot order. Attribute outputs are written only
  *                        when the map holds that attribute; out arrays must hold sp_ogm_info(SP_OGM_INFO_VOXEL_NUM) entries.
+ *   sp_ogm_extract_visible_points  extract_visible_points (:183-411): the occupied voxels whose centroid lies within max_distance
+ *                        (L2) of the sensor and inside the frustum of horizontal_fov x vertical_fov around the sensor's x axis
+ *                        (:197-198 clamps them to [1e-6, pi - 1e-6] and [1e-6, 2 pi - 1e-6]; at the horizontal limit the frustum
+ *                        is mirrored behind the sensor, :248, 284), and that no other occupied voxel hides: the ray walk of the
+ *                        carving runs from the sensor to the centroid and stops at the first occupied cell whose centroid is
+ *                        nearer by more than 1e-6 in the squared distance (:313-361); a voxel within voxel_size of the sensor is
+ *                        never hidden. Rows as for sp_ogm_extract_occupied_points, in table-slot order. Reads the map only. The
+ *                        cosines of the frustum test are forward / sqrt(norm_sq), correctly rounded (the reference uses rsqrt); a
+ *                        sensor at a non-finite position or outside the 21-bit cell range gives 0 rows; NaN max_distance (+inf is
+ *                        allowed), a non-finite field of view or other pose entry is SP_ERR_INVALID_ARGUMENT.
  *   sp_ogm_overlap_ratio compute_overlap_ratio (:417-472)
  *   sp_ogm_voxel_probability  voxel_probability (:85-93): 0.5 where the map has no voxel
  *   sp_ogm_export        every live slot, in slot order, for tests and debugging: key, hit_count, miss_count, log_odds, the frame
@@ -1161,6 +1171,10 @@ int sp_ogm_add_point_cloud(sp_occupancy_grid_map* map, const float* points, cons
 int sp_ogm_extract_occupied_points(sp_occupancy_grid_map* map, const float* sensor_xyz_host3, float max_distance,
                                    float* points_out, float* covs_out, float* rgb_out, float* intensities_out,
                                    uint64_t* keys_out_opt, size_t out_capacity, size_t* n_out_host, void* stream);
+int sp_ogm_extract_visible_points(sp_occupancy_grid_map* map, const float* sensor_pose_host16 /* column-major, map frame */,
+                                  float max_distance, float horizontal_fov, float vertical_fov,
+                                  float* points_out, float* covs_out, float* rgb_out, float* intensities_out,
+                                  uint64_t* keys_out_opt, size_t out_capacity, size_t* n_out_host, void* stream);
 int sp_ogm_overlap_ratio(const sp_occupancy_grid_map* map, const float* points, size_t n, const float* sensor_pose_host16,
                          float* ratio_out_host, void* stream);
 int sp_ogm_voxel_probability(const sp_occupancy_grid_map* map, const float* xyz_host3, float* probability_out_host, void* stream);

@@ -292,6 +292,7 @@ SIGNATURES = {
     "sp_ogm_clear": (_i, [_vp, _vp]),
     "sp_ogm_add_point_cloud": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "sp_ogm_extract_occupied_points": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sp_ogm_extract_visible_points": (_i, [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "sp_ogm_overlap_ratio": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_f), _vp]),
     "sp_ogm_voxel_probability": (_i, [_vp, _vp, C.POINTER(_f), _vp]),
     "sp_ogm_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),

@@ -1514,8 +1514,9 @@ class _HashedVoxelMap:
                                         _stream()))
         return float(r.value)
 
-    def _mean_rows(self, entry_point, xyz3, distance):
-        """the voxel means `entry_point` keeps around xyz3, as a PointCloudShared, and their keys in the same order"""
+    def _mean_rows(self, entry_point, where, *limits):
+        """the voxel means `entry_point` keeps around `where` (a position, or a pose as 16 floats) within `limits` (floats), as a
+        PointCloudShared, and their keys in the same order"""
         cap = self.info("voxel_num")
         dev = self.device
         rows = max(cap, 1)
@@ -1524,10 +1525,10 @@ class _HashedVoxelMap:
         rgb = torch.empty((rows, 4), dtype=torch.float32, device=dev) if self.info("has_rgb") else None
         inten = torch.empty(rows, dtype=torch.float32, device=dev) if self.info("has_intensity") else None
         keys = torch.empty(rows, dtype=torch.int64, device=dev)
-        c = np.ascontiguousarray(xyz3, np.float32).copy()
+        c = np.ascontiguousarray(where, np.float32).copy()
         n_out = C.c_size_t(0)
-        check(self._fn(entry_point)(self._h, c.ctypes.data_as(C.c_void_p), float(distance), _ptr(pts), _ptr(covs), _ptr(rgb),
-                                    _ptr(inten), _ptr(keys), cap, C.byref(n_out), _stream()))
+        check(self._fn(entry_point)(self._h, c.ctypes.data_as(C.c_void_p), *[float(v) for v in limits], _ptr(pts), _ptr(covs),
+                                    _ptr(rgb), _ptr(inten), _ptr(keys), cap, C.byref(n_out), _stream()))
         n = n_out.value
         out = PointCloudShared(pts[:n], covs=None if covs is None else covs[:n], rgb=None if rgb is None else rgb[:n],
                                intensities=None if inten is None else inten[:n], device=dev)
@@ -1566,7 +1567,8 @@ class OccupancyGridMap(_HashedVoxelMap):
     """algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 over the sp_ogm_* entry points: the log-odds submap in HBM, with
     free-space carving along the rays from the sensor. add_point_cloud takes a PointCloudShared in the sensor frame and the sensor
     pose (4x4, map frame); extract_occupied_points returns a PointCloudShared of the occupied voxels' means (plus `.keys`, the voxel
-    keys in output order: rows are in table-slot order, align them by key). extract_visible_points is not provided."""
+    keys in output order: rows are in table-slot order, align them by key); extract_visible_points returns, in the same form, those
+    of them inside the sensor's frustum that no other occupied voxel hides."""
     _PREFIX = "sp_ogm"
     _PARAM = {"voxel_size": 0, "log_odds_hit": 1, "log_odds_miss": 2, "log_odds_min": 3, "log_odds_max": 4,
               "occupancy_threshold": 5, "free_space_updates_enabled": 6, "voxel_pruning_enabled": 7, "stale_frame_threshold": 8,
@@ -1593,6 +1595,12 @@ class OccupancyGridMap(_HashedVoxelMap):
     def extract_occupied_points(self, sensor_pose=None, max_distance=100.0):
         T = np.asarray(identity() if sensor_pose is None else sensor_pose, np.float32).reshape(4, 4)
         out, keys = self._mean_rows("extract_occupied_points", T[:3, 3], max_distance)
+        out.keys = keys
+        return out
+
+    def extract_visible_points(self, sensor_pose, max_distance, horizontal_fov, vertical_fov):
+        """occupancy_grid_map.hpp:183-411: the fields of view in radians, around the sensor's x axis"""
+        out, keys = self._mean_rows("extract_visible_points", _T16(sensor_pose), max_distance, horizontal_fov, vertical_fov)
         out.keys = keys
         return out
 

@@ -1,10 +1,14 @@
-// OccupancyGridMap for gfx950 — the log-odds submap of Submap::build_submap (replaces mapping/occupancy_grid_map.hpp:27-190, 417-472,
-// 482-1687 but extract_visible_points).
+// OccupancyGridMap for gfx950 — the log-odds submap of Submap::build_submap (replaces mapping/occupancy_grid_map.hpp:27-472,
+// 482-1687).
 //
 // The table is sp_voxel_table.h's, as VoxelHashMap's, with 128 probes, a `deleted` key for pruned slots and a 32-byte core {sum xyz,
 // log_odds, hit_count, miss_count, and the part of either count already applied to log_odds}; the host state, the compaction
 // scratch and the overlap kernel are there too.
 // add_point_cloud is the reference's five steps: [rehash] -> hits, one lane per point -> carving, one lane per ray -> apply -> prune.
+// extract_visible_points (:183-411) is two passes with a compaction between them and one after: candidate flags, one lane per slot
+// (occupied, within max_distance, inside the frustum) -> scan -> the candidates' slots as a dense list -> the occlusion walk, one lane
+// per candidate, which clears the flag of a candidate it finds occluded -> scan -> rows. The walk reads the table and writes nothing
+// to it; it is the carving kernel's counted walk with another visitor (counted_walk below).
 // Where this differs from the reference, on purpose:
 //   * the ray walk is a counted loop of exactly |dix| + |diy| + |diz| steps in which an axis that has reached the target's cell no
 //     longer competes; the reference's `while (true)` (:880-899) ends only by landing on the target cell;
@@ -12,10 +16,15 @@
 //     outside that range (the reference casts NaN to int64 / walks millions of rejected cells);
 //   * pending log-odds are two integer counts per voxel, turned into hits * log_hit + misses * log_miss by the apply kernel, so the
 //     log-odds do not depend on the order in which lanes arrive (the reference adds floats with relaxed atomics: order unspecified);
-//   * a pruned slot's covariance sums are cleared with the rest (the reference leaves them to whoever claims the slot next).
+//   * a pruned slot's covariance sums are cleared with the rest (the reference leaves them to whoever claims the slot next);
+//   * extract_visible_points: the two cosines of the frustum test are forward / sqrtf(norm_sq), both correctly rounded, where the
+//     reference multiplies by sycl::rsqrt (implementation-defined); rows come out in table-slot order (the reference hands them out
+//     through an atomic counter); a sensor at a non-finite position or outside the 21-bit cell range sees nothing; other
+//     non-finite arguments are refused.
 // The walk's arithmetic is IEEE multiply / subtract / add / floor / one division per axis, compiled uncontracted (-ffp-contract=off,
 // csrc/Makefile) with hipcc's correctly rounded division: the cells are those of tests/cpp/occupancy_grid_restate.cpp bit for bit.
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 
@@ -98,20 +107,83 @@ struct Ray {
     int tx, ty, tz;
     bool cast;
 };
-__device__ __forceinline__ Ray make_ray(const Rigid& T, const float4 p, float ox, float oy, float oz, float inv) {
+// the ray to a map-frame point: cast when the point has a cell (finite, inside the 21-bit range)
+__device__ __forceinline__ Ray ray_to(float wx, float wy, float wz, float inv) {
     Ray r;
-    transform_point(T, p.x, p.y, p.z, r.wx, r.wy, r.wz);
+    r.wx = wx; r.wy = wy; r.wz = wz;
     r.tx = r.ty = r.tz = 0;
-    r.cast = false;
-    if (voxel_key3(r.wx, r.wy, r.wz, inv) == kInvalidKey) return r;  // non-finite or outside the 21-bit range: skipped whole
-    const float dx = r.wx - ox, dy = r.wy - oy, dz = r.wz - oz;
-    const float dist_sq = dx * dx + dy * dy + dz * dz;
-    if (dist_sq <= FLT_EPSILON) return r;  // :1306, 1400
-    r.tx = (int)floorf(r.wx * inv);
-    r.ty = (int)floorf(r.wy * inv);
-    r.tz = (int)floorf(r.wz * inv);
-    r.cast = true;
+    r.cast = voxel_key3(wx, wy, wz, inv) != kInvalidKey;
+    if (!r.cast) return r;
+    r.tx = (int)floorf(wx * inv);
+    r.ty = (int)floorf(wy * inv);
+    r.tz = (int)floorf(wz * inv);
     return r;
+}
+__device__ __forceinline__ Ray make_ray(const Rigid& T, const float4 p, float ox, float oy, float oz, float inv) {
+    float wx, wy, wz;
+    transform_point(T, p.x, p.y, p.z, wx, wy, wz);
+    Ray r = ray_to(wx, wy, wz, inv);  // non-finite or outside the 21-bit range: skipped whole
+    if (!r.cast) return r;
+    const float dx = wx - ox, dy = wy - oy, dz = wz - oz;
+    const float dist_sq = dx * dx + dy * dy + dz * dz;
+    if (dist_sq <= FLT_EPSILON) r.cast = false;  // :1306, 1400
+    return r;
+}
+
+// Where every ray of a call starts: the sensor position in cell units, its floor and its cell (inside the 21-bit range: the host
+// checked).
+struct WalkOrigin {
+    float sox, soy, soz, fox, foy, foz;
+    int oix, oiy, oiz;
+};
+__device__ __forceinline__ WalkOrigin walk_origin(float ox, float oy, float oz, float inv) {
+    WalkOrigin o;
+    o.sox = ox * inv; o.soy = oy * inv; o.soz = oz * inv;
+    o.fox = floorf(o.sox); o.foy = floorf(o.soy); o.foz = floorf(o.soz);
+    o.oix = (int)o.fox; o.oiy = (int)o.foy; o.oiz = (int)o.foz;
+    return o;
+}
+__device__ __forceinline__ unsigned walk_steps(const WalkOrigin& o, const Ray& r) {
+    return (unsigned)(abs(r.tx - o.oix) + abs(r.ty - o.oiy) + abs(r.tz - o.oiz));
+}
+
+// The walk of traverse_ray_exclusive_impl (:823-900) as a counted loop: exactly steps = |dix| + |diy| + |diz| steps, each along an
+// axis that has not reached the target's cell yet — the smallest t_max among those, ties to x then y, as the reference orders its
+// comparisons. Wherever the reference's loop ends this visits its cells in its order. visit(key) is called for every cell stepped
+// into but the last (the target's own cell is excluded) and ends the walk by returning false.
+template <class Visit>
+__device__ __forceinline__ void counted_walk(const WalkOrigin& o, const Ray& r, float inv, unsigned steps, Visit visit) {
+    const float inf = INFINITY;
+    int ix = o.oix, iy = o.oiy, iz = o.oiz;
+    const float dir_x = r.wx * inv - o.sox, dir_y = r.wy * inv - o.soy, dir_z = r.wz * inv - o.soz;
+    const float ax = fabsf(dir_x), ay = fabsf(dir_y), az = fabsf(dir_z);
+    const int step_x = (dir_x > 0.0f) ? 1 : ((dir_x < 0.0f) ? -1 : 0);
+    const int step_y = (dir_y > 0.0f) ? 1 : ((dir_y < 0.0f) ? -1 : 0);
+    const int step_z = (dir_z > 0.0f) ? 1 : ((dir_z < 0.0f) ? -1 : 0);
+    const float frac_x = o.sox - o.fox, frac_y = o.soy - o.foy, frac_z = o.soz - o.foz;
+    const float inv_x = (ax > FLT_EPSILON) ? (1.0f / ax) : inf;
+    const float inv_y = (ay > FLT_EPSILON) ? (1.0f / ay) : inf;
+    const float inv_z = (az > FLT_EPSILON) ? (1.0f / az) : inf;
+    float t_max_x = (step_x != 0) ? ((step_x > 0 ? (1.0f - frac_x) : frac_x) * inv_x) : inf;
+    float t_max_y = (step_y != 0) ? ((step_y > 0 ? (1.0f - frac_y) : frac_y) * inv_y) : inf;
+    float t_max_z = (step_z != 0) ? ((step_z > 0 ? (1.0f - frac_z) : frac_z) * inv_z) : inf;
+    const float t_delta_x = (step_x != 0) ? inv_x : inf;
+    const float t_delta_y = (step_y != 0) ? inv_y : inf;
+    const float t_delta_z = (step_z != 0) ? inv_z : inf;
+    // An axis whose cells differ has a non-zero direction of the right sign (floor is monotone), so step_* leads to the target.
+    for (unsigned s = 1; s <= steps; ++s) {
+        const bool ux = ix != r.tx, uy = iy != r.ty, uz = iz != r.tz;  // axes still short of the target: at least one
+        int axis;
+        if (ux && (!uy || t_max_x <= t_max_y) && (!uz || t_max_x <= t_max_z)) axis = 0;
+        else if (uy && (!uz || t_max_y <= t_max_z)) axis = 1;
+        else if (uz) axis = 2;
+        else axis = uy ? 1 : 0;  // only reached through a NaN t_max (0 * inf): still an axis that is short
+        if (axis == 0) { ix += step_x; t_max_x += t_delta_x; }
+        else if (axis == 1) { iy += step_y; t_max_y += t_delta_y; }
+        else { iz += step_z; t_max_z += t_delta_z; }
+        if (s == steps) break;  // the target's cell itself is excluded
+        if (!visit(cell_key(ix, iy, iz))) break;  // between two cells inside the range the key is always valid
+    }
 }
 
 // The origin-voxel hit flag (:1258-1280) and the visit estimate (:1283-1335) in one pass: out[0..1] = the estimate (64 bits),
@@ -147,55 +219,23 @@ __device__ __forceinline__ void post_miss(const OgmTable& t, uint64_t key, uint3
     stamp(t, s, frame);
 }
 
-// update_free_space's walk (:1385-1448) over traverse_ray_exclusive_impl (:823-900), one lane per ray. The loop is counted: exactly
-// |dix| + |diy| + |diz| steps, each along an axis that has not reached the target's cell yet — the smallest t_max among those, ties
-// to x then y, as the reference orders its comparisons. Wherever the reference's loop ends this visits its cells in its order.
+// update_free_space's walk (:1385-1448), one lane per ray: counted_walk with a visitor that posts a miss and never stops.
 __global__ __launch_bounds__(kBlock) void ogm_walk_kernel(OgmTable t, const float4* __restrict__ pts, unsigned n, Mat4Arg pose,
                                                           float inv, float ox, float oy, float oz, bool skip_origin_miss,
                                                           uint32_t frame, unsigned* __restrict__ voxel_num) {
     const Rigid T = load_rigid_colmajor(pose.m);
-    const float sox = ox * inv, soy = oy * inv, soz = oz * inv;
-    const float fox = floorf(sox), foy = floorf(soy), foz = floorf(soz);
-    const int oix = (int)fox, oiy = (int)foy, oiz = (int)foz;  // inside the 21-bit range: the host checked
-    const float inf = INFINITY;
+    const WalkOrigin o = walk_origin(ox, oy, oz, inv);
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const float4 p = pts[i];
         const Ray r = make_ray(T, p, ox, oy, oz, inv);
         if (!r.cast) continue;
-        int ix = oix, iy = oiy, iz = oiz;
-        const unsigned steps = (unsigned)(abs(r.tx - ix) + abs(r.ty - iy) + abs(r.tz - iz));
+        const unsigned steps = walk_steps(o, r);
         if (steps == 0) continue;  // the hit lies in the sensor's own cell
-        if (!skip_origin_miss) post_miss(t, cell_key(ix, iy, iz), frame, voxel_num);  // :1427-1433
-        const float dir_x = r.wx * inv - sox, dir_y = r.wy * inv - soy, dir_z = r.wz * inv - soz;
-        const float ax = fabsf(dir_x), ay = fabsf(dir_y), az = fabsf(dir_z);
-        const int step_x = (dir_x > 0.0f) ? 1 : ((dir_x < 0.0f) ? -1 : 0);
-        const int step_y = (dir_y > 0.0f) ? 1 : ((dir_y < 0.0f) ? -1 : 0);
-        const int step_z = (dir_z > 0.0f) ? 1 : ((dir_z < 0.0f) ? -1 : 0);
-        const float frac_x = sox - fox, frac_y = soy - foy, frac_z = soz - foz;
-        const float inv_x = (ax > FLT_EPSILON) ? (1.0f / ax) : inf;
-        const float inv_y = (ay > FLT_EPSILON) ? (1.0f / ay) : inf;
-        const float inv_z = (az > FLT_EPSILON) ? (1.0f / az) : inf;
-        float t_max_x = (step_x != 0) ? ((step_x > 0 ? (1.0f - frac_x) : frac_x) * inv_x) : inf;
-        float t_max_y = (step_y != 0) ? ((step_y > 0 ? (1.0f - frac_y) : frac_y) * inv_y) : inf;
-        float t_max_z = (step_z != 0) ? ((step_z > 0 ? (1.0f - frac_z) : frac_z) * inv_z) : inf;
-        const float t_delta_x = (step_x != 0) ? inv_x : inf;
-        const float t_delta_y = (step_y != 0) ? inv_y : inf;
-        const float t_delta_z = (step_z != 0) ? inv_z : inf;
-        // An axis whose cells differ has a non-zero direction of the right sign (floor is monotone), so step_* leads to the target.
-        for (unsigned s = 1; s <= steps; ++s) {
-            const bool ux = ix != r.tx, uy = iy != r.ty, uz = iz != r.tz;  // axes still short of the target: at least one
-            int axis;
-            if (ux && (!uy || t_max_x <= t_max_y) && (!uz || t_max_x <= t_max_z)) axis = 0;
-            else if (uy && (!uz || t_max_y <= t_max_z)) axis = 1;
-            else if (uz) axis = 2;
-            else axis = uy ? 1 : 0;  // only reached through a NaN t_max (0 * inf): still an axis that is short
-            if (axis == 0) { ix += step_x; t_max_x += t_delta_x; }
-            else if (axis == 1) { iy += step_y; t_max_y += t_delta_y; }
-            else { iz += step_z; t_max_z += t_delta_z; }
-            if (s == steps) break;  // the hit cell itself is excluded
-            const uint64_t key = cell_key(ix, iy, iz);  // between two cells inside the range: always valid
+        if (!skip_origin_miss) post_miss(t, cell_key(o.oix, o.oiy, o.oiz), frame, voxel_num);  // :1427-1433
+        counted_walk(o, r, inv, steps, [&](uint64_t key) {
             if (key != kInvalidKey) post_miss(t, key, frame, voxel_num);
-        }
+            return true;
+        });
     }
 }
 
@@ -252,6 +292,12 @@ __global__ __launch_bounds__(kBlock) void ogm_rehash_kernel(OgmTable old_t, OgmT
     }
 }
 
+// compute_overlap_ratio (:417-472) and the occluders of extract_visible_points (:332): a voxel counts when it was hit and is occupied
+struct Occupied {
+    float threshold;
+    __device__ bool operator()(const OgmCore& c) const { return c.hit_count > 0u && !(c.log_odds < threshold); }
+};
+
 // flags for the two compactions: every live slot (export), or the occupied voxels near the sensor (:1568-1589).
 // Each map's flag kernel tests its own condition: not shared.
 __global__ __launch_bounds__(kBlock) void ogm_flag_kernel(OgmTable t, bool occupied_only, float threshold, float sx, float sy,
@@ -279,6 +325,90 @@ __global__ __launch_bounds__(kBlock) void ogm_extract_kernel(OgmTable t, const u
     if (o >= out_capacity) return;
     const OgmCore c = t.core[i];
     write_mean_row(t, i, o, c.hit_count, c.sx, c.sy, c.sz, out);
+}
+
+// extract_visible_points, first pass (:250-311): flags[slot] = 1 for a candidate — an occupied voxel whose centroid lies within
+// max_distance (L2) of the sensor and inside the frustum. local = R^T d is eigen_utils::multiply<3, 3> (one fma chain per row). The
+// cosines are forward / sqrtf(norm_sq), not forward * rsqrt(norm_sq) as in the reference (:291, 305): division and square root are
+// correctly rounded, sycl::rsqrt is implementation-defined.
+struct Frustum {
+    float sx, sy, sz;  // the sensor position
+    float max_dist_sq, cos_limit_horizontal, cos_limit_vertical;
+    bool include_backward;
+};
+__device__ __forceinline__ float clamp_unit(float c) { return c < -1.0f ? -1.0f : (c > 1.0f ? 1.0f : c); }
+
+__global__ __launch_bounds__(kBlock) void ogm_visible_flag_kernel(OgmTable t, float threshold, Mat4Arg pose, Frustum f,
+                                                                  unsigned* __restrict__ flags) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= t.capacity) return;
+    bool keep = live(t.key[i]);
+    if (keep) {
+        const OgmCore c = t.core[i];
+        keep = c.hit_count != 0u && !(c.log_odds < threshold);
+        if (keep) {
+            const Rigid T = load_rigid_colmajor(pose.m);
+            const float inv = 1.0f / (float)c.hit_count;
+            const float dx = c.sx * inv - f.sx, dy = c.sy * inv - f.sy, dz = c.sz * inv - f.sz;
+            const float dist_sq = dx * dx + dy * dy + dz * dz;
+            const float lx = chain3(T.R[0][0], dx, T.R[1][0], dy, T.R[2][0], dz);
+            const float ly = chain3(T.R[0][1], dx, T.R[1][1], dy, T.R[2][1], dz);
+            const float lz = chain3(T.R[0][2], dx, T.R[1][2], dy, T.R[2][2], dz);
+            const float forward = f.include_backward ? fabsf(lx) : lx;  // :284: the limits apply behind the sensor as in front
+            const float h_sq = forward * forward + ly * ly, v_sq = forward * forward + lz * lz;
+            const float cos_h = h_sq > 0.0f ? clamp_unit(forward / sqrtf(h_sq)) : 1.0f;
+            const float cos_v = v_sq > 0.0f ? clamp_unit(forward / sqrtf(v_sq)) : 1.0f;
+            keep = dist_sq <= f.max_dist_sq && (f.include_backward || !(lx <= 0.0f)) && !(cos_h < f.cos_limit_horizontal) &&
+                   !(cos_v < f.cos_limit_vertical);
+        }
+    }
+    flags[i] = keep ? 1u : 0u;
+}
+
+// the flagged slots as a dense list in slot order: list[pos[slot]] = slot
+__global__ __launch_bounds__(kBlock) void ogm_candidate_list_kernel(const unsigned* __restrict__ flags,
+                                                                    const unsigned* __restrict__ pos, unsigned long long capacity,
+                                                                    unsigned* __restrict__ list) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i < capacity && flags[i]) list[pos[i]] = (unsigned)i;
+}
+
+// extract_visible_points, second pass (:313-361), one lane per candidate: the counted walk from the sensor to the candidate's
+// centroid, stopped at the first occluder — another occupied voxel whose centroid is nearer to the sensor by more than 1e-6 in the
+// squared distance (:341). An occluded candidate's flag is cleared. *count is the number of candidates (the scan's total, device
+// memory); the host knows only its bound, voxel_num, and sizes the grid from that. Reads the table, writes nothing to it, no atomics.
+__global__ __launch_bounds__(kBlock) void ogm_visible_walk_kernel(OgmTable t, const unsigned* __restrict__ list,
+                                                                  const unsigned* __restrict__ count, float threshold, float ox,
+                                                                  float oy, float oz, float inv, float voxel_size,
+                                                                  unsigned* __restrict__ flags) {
+    const unsigned n = *count;
+    const WalkOrigin o = walk_origin(ox, oy, oz, inv);
+    const Occupied occupied{threshold};
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const unsigned slot = list[i];
+        const uint64_t own_key = t.key[slot];
+        const OgmCore c = t.core[slot];
+        const float inv_count = 1.0f / (float)c.hit_count;
+        const float cx = c.sx * inv_count, cy = c.sy * inv_count, cz = c.sz * inv_count;
+        const float dx = cx - ox, dy = cy - oy, dz = cz - oz;
+        const float dist_sq = dx * dx + dy * dy + dz * dz;
+        if (sqrtf(dist_sq) <= voxel_size) continue;  // :317: too near to be hidden
+        const Ray r = ray_to(cx, cy, cz, inv);
+        if (!r.cast) continue;  // a centroid without a cell (its sums overflowed): nothing to walk to
+        bool occluded = false;
+        counted_walk(o, r, inv, walk_steps(o, r), [&](uint64_t key) {
+            if (key == kInvalidKey || key == own_key) return true;
+            const unsigned long long s = find_slot<kOgmMaxProbe>(t.key, t.capacity, key);
+            if (s == kNoSlot) return true;
+            const OgmCore occ = t.core[s];
+            if (!occupied(occ)) return true;
+            const float inv_occ = 1.0f / (float)occ.hit_count;
+            const float ex = occ.sx * inv_occ - ox, ey = occ.sy * inv_occ - oy, ez = occ.sz * inv_occ - oz;
+            occluded = ex * ex + ey * ey + ez * ez + 1e-6f < dist_sq;
+            return !occluded;
+        });
+        if (occluded) flags[slot] = 0u;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void ogm_export_kernel(OgmTable t, const unsigned* __restrict__ flags,
@@ -311,12 +441,6 @@ __global__ __launch_bounds__(kBlock) void ogm_export_kernel(OgmTable t, const un
     }
     if (inten) inten[o] = t.intensity[i];
 }
-
-// compute_overlap_ratio (:417-472): a voxel counts when it was hit and is occupied
-struct Occupied {
-    float threshold;
-    __device__ bool operator()(const OgmCore& c) const { return c.hit_count > 0u && !(c.log_odds < threshold); }
-};
 
 // find_voxel (:591-609) for one key: out[0] = 1 and out[1] = the log-odds' bits when the map holds the voxel
 __global__ void ogm_lookup_kernel(OgmTable t, uint64_t key, unsigned* __restrict__ out) {
@@ -522,6 +646,61 @@ extern "C" int sp_ogm_extract_occupied_points(sp_occupancy_grid_map* m, const fl
     int rc = flag_and_scan(m, true, sensor_xyz_host3, max_distance, st);
     if (rc != SP_OK) return rc;
     ogm_extract_kernel<<<div_up((size_t)m->t.capacity, kBlock), kBlock, 0, st>>>(
+        m->t, m->flags, m->pos, (unsigned)out_capacity, m->mean_rows(points_out, covs_out, rgb_out, intensities_out, keys_out_opt));
+    return m->read_total(st, n_out_host);
+}
+
+// extract_visible_points (:183-411). Output rows are in table-slot order, as for extract_occupied_points.
+extern "C" int sp_ogm_extract_visible_points(sp_occupancy_grid_map* m, const float* sensor_pose_host16, float max_distance,
+                                             float horizontal_fov, float vertical_fov, float* points_out, float* covs_out,
+                                             float* rgb_out, float* intensities_out, uint64_t* keys_out_opt, size_t out_capacity,
+                                             size_t* n_out_host, void* stream) {
+    using namespace sp;
+    if (!m || !sensor_pose_host16 || !n_out_host) return SP_ERR_INVALID_ARGUMENT;
+    *n_out_host = 0;
+    bool finite = !std::isnan(max_distance) && std::isfinite(horizontal_fov) && std::isfinite(vertical_fov);  // +inf: no bound
+    for (int i = 0; i < 16; ++i)  // the sensor position (12..14) is judged by its cell, below
+        if (i < 12 || i == 15) finite = finite && std::isfinite(sensor_pose_host16[i]);
+    if (!finite) {  // the reference would compare against NaN limits; refused here, before any HIP call
+        sp_set_error("[OccupancyGridMap::extract_visible_points] sensor_pose, max_distance and the fields of view must be finite");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
+    if (m->voxel_num == 0) return SP_OK;
+    if (!points_out || out_capacity < m->voxel_num) {
+        sp_set_error("[OccupancyGridMap::extract_visible_points] output arrays must hold sp_ogm_info(SP_OGM_INFO_VOXEL_NUM) entries");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
+    const float ox = sensor_pose_host16[12], oy = sensor_pose_host16[13], oz = sensor_pose_host16[14];
+    const float inv = m->voxel_size_inv, lim = (float)kCellOffset;
+    const float fx = std::floor(ox * inv), fy = std::floor(oy * inv), fz = std::floor(oz * inv);
+    // a sensor at a non-finite position or outside the 21-bit cell range sees nothing, as a frame from it carves nothing (the
+    // reference would walk millions of rejected cells)
+    if (!(fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim)) return SP_OK;
+    constexpr float kFovTolerance = 1e-6f;  // :475-477; kPi is the same float
+    horizontal_fov = std::min(std::max(horizontal_fov, kFovTolerance), kPi - kFovTolerance);  // :197-198
+    vertical_fov = std::min(std::max(vertical_fov, kFovTolerance), 2.0f * kPi - kFovTolerance);
+    Frustum f;
+    f.sx = ox; f.sy = oy; f.sz = oz;
+    f.max_dist_sq = max_distance * max_distance;
+    f.cos_limit_horizontal = std::cos(horizontal_fov * 0.5f);  // :245-248, on the host
+    f.cos_limit_vertical = std::cos(vertical_fov * 0.5f);
+    f.include_backward = horizontal_fov >= (kPi - kFovTolerance);
+    hipStream_t st = as_stream(stream);
+    int rc = m->ensure_scratch();
+    if (rc != SP_OK) return rc;
+    const unsigned cap_blocks = div_up((size_t)m->t.capacity, kBlock);
+    ogm_visible_flag_kernel<<<cap_blocks, kBlock, 0, st>>>(m->t, m->occupancy_threshold_log_odds, pose_arg(sensor_pose_host16), f,
+                                                          m->flags);
+    if ((rc = m->scan_flags(st)) != SP_OK) return rc;
+    // Candidates are compacted before the walk: the table is at most 0.7 full and a frustum keeps a few per cent of it, so with one
+    // lane per slot most of every wave would idle for as long as its longest ray.
+    ogm_candidate_list_kernel<<<cap_blocks, kBlock, 0, st>>>(m->flags, m->pos, m->t.capacity, m->list);
+    ogm_visible_walk_kernel<<<stream_grid(m->voxel_num), kBlock, 0, st>>>(m->t, m->list, m->pos + m->t.capacity,
+                                                                         m->occupancy_threshold_log_odds, ox, oy, oz, inv,
+                                                                         m->voxel_size, m->flags);
+    if ((rc = launch_status()) != SP_OK) return rc;
+    if ((rc = m->scan_flags(st)) != SP_OK) return rc;
+    ogm_extract_kernel<<<cap_blocks, kBlock, 0, st>>>(
         m->t, m->flags, m->pos, (unsigned)out_capacity, m->mean_rows(points_out, covs_out, rgb_out, intensities_out, keys_out_opt));
     return m->read_total(st, n_out_host);
 }

@@ -6,7 +6,7 @@
 //     sums 16 B | intensity sum | stamp of the last update), open addressing; its allocation, the read-only probe, the attribute
 //     atomics, the averaged output row and the overlap kernel;
 //   * the host state around it (VoxelMapState): settings and has_* flags, the 4-word device counter, growing into a larger table,
-//     the flags -> exclusive scan compaction scratch, create / clear / destroy.
+//     the flags -> exclusive scan compaction scratch (and the list of flagged slots), create / clear / destroy.
 // What stays in the two .hip files differs on purpose: how a slot is claimed, how a table is rehashed, which slots an export keeps.
 // The kernels here are compiled into both translation units (unnamed namespace, voxel_table_* names).
 #pragma once
@@ -273,6 +273,7 @@ struct VoxelMapState {
     VoxelTable<Core> t{};
     unsigned* counter = nullptr;  // device, 4 words: the voxel count / hit count / result of the running call in the first
     unsigned *flags = nullptr, *pos = nullptr;  // compaction scratch, sized to the capacity + 1
+    unsigned* list = nullptr;                   // the flagged slots as a dense list (OccupancyGridMap's candidates), sized with them
     size_t scratch_cap = 0;
     void* scan_tmp = nullptr;
     size_t scan_tmp_bytes = 0;
@@ -328,11 +329,12 @@ struct VoxelMapState {
     int ensure_scratch() {
         const size_t cap = (size_t)t.capacity;
         if (scratch_cap >= cap) return SP_OK;
-        (void)hipFree(flags); (void)hipFree(pos); (void)hipFree(scan_tmp);
-        flags = pos = nullptr; scan_tmp = nullptr; scratch_cap = 0;
+        (void)hipFree(flags); (void)hipFree(pos); (void)hipFree(list); (void)hipFree(scan_tmp);
+        flags = pos = list = nullptr; scan_tmp = nullptr; scratch_cap = 0;
         const size_t tmp = exclusive_scan_u32_workspace_bytes(cap + 1);
         hipError_t e = hipMalloc(&flags, (cap + 1) * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc(&pos, (cap + 1) * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMalloc(&list, (cap + 1) * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc(&scan_tmp, tmp ? tmp : 16);
         if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); return SP_ERR_HIP; }
         scan_tmp_bytes = tmp;
@@ -396,8 +398,8 @@ struct VoxelMapState {
     }
     void release() {
         free_table(t);
-        (void)hipFree(counter); (void)hipFree(flags); (void)hipFree(pos); (void)hipFree(scan_tmp);
-        counter = flags = pos = nullptr; scan_tmp = nullptr; scratch_cap = 0;
+        (void)hipFree(counter); (void)hipFree(flags); (void)hipFree(pos); (void)hipFree(list); (void)hipFree(scan_tmp);
+        counter = flags = pos = list = nullptr; scan_tmp = nullptr; scratch_cap = 0;
     }
 };
 
