@@ -103,6 +103,29 @@ struct Isometry3f {
         for (int i = 0; i < 3; ++i) r.m(i, 3) = -(r.m(i, 0) * m(0, 3) + r.m(i, 1) * m(1, 3) + r.m(i, 2) * m(2, 3));
         return r;
     }
+    Matrix3f rotation() const { return linear(); }  // (an isometry: the linear part is the rotation)
+};
+// AngleAxis<float> subset: what the odometry pipeline's signatures carry (pipeline/motion_predictor.hpp:60-63)
+struct AngleAxisf {
+    AngleAxisf() = default;
+    AngleAxisf(float angle, const Vector3f& axis) : angle_(angle), axis_(axis) {}
+    static AngleAxisf Identity() { return AngleAxisf(); }
+    float angle() const { return angle_; }
+    float& angle() { return angle_; }
+    const Vector3f& axis() const { return axis_; }
+    Vector3f& axis() { return axis_; }
+    Matrix3f toRotationMatrix() const {
+        const float twist[6] = {axis_[0] * angle_, axis_[1] * angle_, axis_[2] * angle_, 0.0f, 0.0f, 0.0f};
+        float T[16];
+        sp_se3_exp_host(twist, T);
+        Matrix3f r;
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) r(i, j) = T[j * 4 + i];
+        return r;
+    }
+
+private:
+    float angle_ = 0.0f;
+    Vector3f axis_ = Vector3f(1.0f, 0.0f, 0.0f);
 };
 }  // namespace Eigen
 #define EIGEN_MAKE_ALIGNED_OPERATOR_NEW
@@ -755,8 +778,9 @@ public:
         dev_size_ = n; size_override_ = true; dev_dirty_ = true; host_dirty_ = false;
         generation_ = next_generation();
     }
-    /// Read-write device pointer (in-place kernels).
-    T* device_data_rw() { sync_device(); dev_dirty_ = true; dev_size_ = host_.size(); size_override_ = true; generation_ = next_generation(); return dev_; }
+    /// Read-write device pointer (in-place kernels). The size is the container's, whichever side holds it: a vector a kernel
+    /// wrote (a filter's output) has no host copy to take it from.
+    T* device_data_rw() { const size_t n = size(); sync_device(); dev_dirty_ = true; dev_size_ = n; size_override_ = true; generation_ = next_generation(); return dev_; }
     /// After a kernel produced fewer rows than reserved (compaction, downsampling).
     void set_device_size(size_t n) { dev_size_ = n; size_override_ = true; dev_dirty_ = true; generation_ = next_generation(); }
     /// Changes whenever the contents may have changed (any non-const access counts): a structure built on the container can

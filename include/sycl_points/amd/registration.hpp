@@ -141,6 +141,10 @@ struct RegistrationOptimizationParams {
 };
 struct RegistrationParams : public RegistrationFactorParams, public RegistrationOptimizationParams {
     using Criteria = RegistrationConvergenceCriteria;
+    RegistrationParams() = default;
+    /// registration_params.hpp:104-107: from the two halves (what Parameters::make_registration_pipeline_params passes)
+    explicit RegistrationParams(const RegistrationFactorParams& factor, const RegistrationOptimizationParams& optimization = {})
+        : RegistrationFactorParams(factor), RegistrationOptimizationParams(optimization) {}
     size_t max_iterations = 20;
     Criteria criteria;
     DegenerateRegularizationParams degenerate_reg;  // registration_params.hpp:111-112

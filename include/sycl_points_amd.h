@@ -1010,6 +1010,79 @@ int sp_map_prior_update_host(const sp_map_prior_params* params, const float* H_r
 float sp_map_prior_apply_host(const sp_map_prior_state* state, const float* T_est16, float* H36_rowmajor, float* b6,
                               float* error);
 
+/* ---- host numerics of the per-frame odometry loop (pipeline/lidar_odometry.hpp and what it calls): 3x3 / 4x4 arithmetic the
+ * reference writes with Eigen::SelfAdjointEigenSolver<Matrix3f>, AngleAxisf, Quaternionf and FromTwoVectors. HOST memory only,
+ * no device is touched. Poses column-major 4x4, rotations column-major 3x3, H row-major as in sp_linearized. */
+/* MotionPredictionMode (pipeline/motion_predictor.hpp:17-21) */
+enum { SP_MOTION_LIDAR_CV = 0, SP_MOTION_GYRO_LIDAR_CV = 1, SP_MOTION_IMU_SE3 = 2 };
+typedef struct sp_motion_axis_params { /* AdaptiveMotionPredictor::Params::AdaptiveAxis, adaptive_motion_predictor.hpp:22-27 */
+    float factor_min;          /* 0.2: applied when the block is well constrained */
+    float factor_max;          /* 1.0: applied when it is degenerate */
+    float min_eigenvalue_low;  /* 1.0 (rotation: 5.0) */
+    float min_eigenvalue_high; /* 10.0 */
+} sp_motion_axis_params;
+typedef struct sp_motion_predict_params { /* MotionPredictor::Params, motion_predictor.hpp:54-56 */
+    sp_motion_axis_params rotation, translation;
+    float velocity_ema_alpha; /* 1.0 = the raw velocity, 0.0 = frozen */
+    int mode;                 /* SP_MOTION_* */
+} sp_motion_predict_params;
+/* The moving averages of AdaptiveMotionPredictor (:140-141), owned by the caller; zero-initialised = no value yet. */
+typedef struct sp_motion_predict_state {
+    int has_linear, has_angular;
+    float linear[3];  /* m/s, previous LiDAR body frame */
+    float angular[3]; /* rotation vector, rad/s */
+} sp_motion_predict_state;
+/* MotionPredictor::predict (motion_predictor.hpp:60-76) over AdaptiveMotionPredictor::predict (adaptive_motion_predictor.hpp:
+ * 54-133). With mode IMU_SE3 and imu_se3_pose16 given, T_pred = that pose and nothing else happens (the averages are not
+ * touched). Otherwise: both factors start at factor_max; with registrated != 0 and inlier > 0 each becomes
+ * max * (1 - score) + min * score, score = clamp((lambda_min / inlier - low) / max(high - low, 1e-6), 0, 1), lambda_min the
+ * smallest eigenvalue of H_raw's rotation (0..2) / translation (3..5) block. The velocities pass through
+ * s <- alpha * v + (1 - alpha) * s (the first call stores v); an averaged angular speed that is not > 1e-6 rad/s is no rotation.
+ * T_pred: t = t_odom + R_odom (v dt f_t), R = normalized(quat(R_odom) * quat(axis, |w| dt f_r)). With mode GYRO_LIDAR_CV and
+ * gyro_delta_rotation9 given, the rotation of odom^-1 * T_pred is replaced by it. H_raw36 may be NULL when registrated == 0;
+ * the two candidates may be NULL; factors2_out (rotation, translation) may be NULL. */
+int sp_motion_predict_host(const sp_motion_predict_params* params, sp_motion_predict_state* state,
+                           const float* linear_velocity3, const float* angular_velocity_rotvec3, const float* odom16, float dt,
+                           const float* H_raw36_rowmajor, uint32_t inlier, int registrated, const float* gyro_delta_rotation9,
+                           const float* imu_se3_pose16, float* T_pred16_out, float* factors2_out);
+/* lidar_odometry.hpp:282-286: delta = prev^-1 * cur; linear3 = delta.t / dt; angle_axis4 = (AngleAxisf(delta.R).angle / dt,
+ * axis xyz) - angle >= 0; the identity gives angle 0 about x. */
+int sp_velocity_from_poses_host(const float* T_prev16, const float* T_cur16, float dt, float* linear3_out, float* angle_axis4_out);
+/* Submap::is_keyframe (pipeline/submapping.hpp:144-161): *is_keyframe_out = distance >= distance_threshold || angle (degrees,
+ * of AngleAxisf) >= angle_threshold_degrees || delta_time >= time_threshold_seconds, where delta_time is DBL_MAX unless
+ * last_keyframe_time > 0.0. metrics3_out (may be NULL): distance, angle in degrees, delta_time. */
+int sp_keyframe_decision_host(const float* T_last_keyframe16, const float* T_current16, double last_keyframe_time,
+                              double timestamp, float distance_threshold, float angle_threshold_degrees,
+                              float time_threshold_seconds, int* is_keyframe_out, double* metrics3_out);
+typedef struct sp_initial_alignment_params { /* imu::InitialAlignmentParams, imu_initial_alignment.hpp:18-46 (what estimate reads) */
+    float required_duration_sec; /* 1.0 */
+    float max_gyro_std;          /* 0.01 rad/s */
+    float max_accel_std;         /* 0.2 m/s^2 */
+    float max_accel_norm_error;  /* 0.5 m/s^2 */
+    int estimate_gyro_bias;      /* 1 */
+} sp_initial_alignment_params;
+typedef struct sp_initial_alignment_result { /* imu::InitialAlignmentResult, :54-65 */
+    int success;
+    int window_size;      /* samples the statistics were taken over (0 on the returns before the window is chosen) */
+    float R_world_imu[9]; /* column-major */
+    float gyro_bias[3], accel_mean[3], gyro_std[3], accel_std[3];
+    float accel_norm, roll_rad, pitch_rad;
+    char error_message[96]; /* the reference's text of the early return taken; empty on success */
+} sp_initial_alignment_result;
+/* imu::estimate_initial_alignment (imu_initial_alignment.hpp:85-204). stamps: n absolute seconds in buffer order; gyro_accel: n
+ * rows of gyro xyz, accel xyz; bias6 = (gyro_bias, accel_bias). The window is every sample with stamp >= last - required, plus
+ * the latest earlier one when the first of them lies more than 1e-6 s inside; means and variances in double; the three
+ * stationarity tests unless bypass_stationarity != 0; R_world_imu the minimum rotation taking the bias-corrected mean specific
+ * force onto -gravity (Quaternionf::FromTwoVectors; for opposite vectors the reference takes an axis from an SVD, here the cross
+ * product with the coordinate axis least aligned with the force), roll = atan2(R21, R22), pitch = asin(-clamp(R20)). An early
+ * return of the reference is SP_OK with success = 0 and its message. Null pointers (stamps / gyro_accel with n > 0, gravity3,
+ * params, bias6, result_out) -> SP_ERR_INVALID_ARGUMENT. */
+int sp_initial_alignment_host(const double* stamps_host, const float* gyro_accel_host, size_t n, const float* gravity3,
+                              const sp_initial_alignment_params* params, const float* bias6, int bypass_stationarity,
+                              sp_initial_alignment_result* result_out);
+/* imu::detail::yaw_from_rotation (:211-218): atan2(R10, R00), 0 when R00^2 + R10^2 < 1e-12. */
+float sp_yaw_from_rotation_host(const float* R9_colmajor);
+
 /* ----------------------------------------------------------------------------------------- multi-GPU */
 
 /* One process per GPU; the source cloud is sharded over the ranks, the target (points, covariances, grid, prepared rows)

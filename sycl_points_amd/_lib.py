@@ -95,11 +95,37 @@ class ImuState(C.Structure):  # sp_imu_state
                 ("J_p_bg", C.c_float * 9), ("J_p_ba", C.c_float * 9), ("covariance", C.c_float * 225)]
 
 
+class MotionAxisParams(C.Structure):  # sp_motion_axis_params
+    _fields_ = [("factor_min", C.c_float), ("factor_max", C.c_float), ("min_eigenvalue_low", C.c_float),
+                ("min_eigenvalue_high", C.c_float)]
+
+
+class MotionPredictParams(C.Structure):  # sp_motion_predict_params
+    _fields_ = [("rotation", MotionAxisParams), ("translation", MotionAxisParams), ("velocity_ema_alpha", C.c_float), ("mode", C.c_int)]
+
+
+class MotionPredictState(C.Structure):  # sp_motion_predict_state
+    _fields_ = [("has_linear", C.c_int), ("has_angular", C.c_int), ("linear", C.c_float * 3), ("angular", C.c_float * 3)]
+
+
+class InitialAlignmentParams(C.Structure):  # sp_initial_alignment_params
+    _fields_ = [("required_duration_sec", C.c_float), ("max_gyro_std", C.c_float), ("max_accel_std", C.c_float),
+                ("max_accel_norm_error", C.c_float), ("estimate_gyro_bias", C.c_int)]
+
+
+class InitialAlignmentResult(C.Structure):  # sp_initial_alignment_result
+    _fields_ = [("success", C.c_int), ("window_size", C.c_int), ("R_world_imu", C.c_float * 9), ("gyro_bias", C.c_float * 3),
+                ("accel_mean", C.c_float * 3), ("gyro_std", C.c_float * 3), ("accel_std", C.c_float * 3), ("accel_norm", C.c_float),
+                ("roll_rad", C.c_float), ("pitch_rad", C.c_float), ("error_message", C.c_char * 96)]
+
+
+MOTION_MODE = {"LIDAR_CV": 0, "GYRO_LIDAR_CV": 1, "IMU_SE3": 2}  # SP_MOTION_*
 # deskew::IMUDeskewStatus (SP_IMU_DESKEW_*)
 IMU_DESKEW_STATUS = ("success", "insufficient_imu_coverage", "no_timestamps", "invalid_scan_duration", "empty_cloud")
 OPT_WANT_DONE, OPT_WANT_LINEARIZE, OPT_WANT_TRIAL = 0, 1, 2
 assert C.sizeof(Linearized) == 192
 assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
+assert C.sizeof(MotionPredictParams) == 40 and C.sizeof(MotionPredictState) == 32 and C.sizeof(InitialAlignmentResult) == 200
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
 _vp, _sz, _f, _i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
@@ -273,6 +299,12 @@ SIGNATURES = {
     "sp_degenerate_regularize_host": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "sp_map_prior_update_host": (_i, [_vp, _vp, _f, C.c_uint32, _vp, _vp, _vp]),
     "sp_map_prior_apply_host": (_f, [_vp, _vp, _vp, _vp, _vp]),
+    "sp_motion_predict_host": (_i, [C.POINTER(MotionPredictParams), C.POINTER(MotionPredictState), _vp, _vp, _vp, _f, _vp, C.c_uint32, _i,
+                                    _vp, _vp, _vp, _vp]),
+    "sp_velocity_from_poses_host": (_i, [_vp, _vp, _f, _vp, _vp]),
+    "sp_keyframe_decision_host": (_i, [_vp, _vp, C.c_double, C.c_double, _f, _f, _f, C.POINTER(_i), _vp]),
+    "sp_initial_alignment_host": (_i, [_vp, _vp, _sz, _vp, C.POINTER(InitialAlignmentParams), _vp, _i, C.POINTER(InitialAlignmentResult)]),
+    "sp_yaw_from_rotation_host": (_f, [_vp]),
     "sp_vhm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
     "sp_vhm_destroy": (None, [_vp]),
     "sp_vhm_set": (_i, [_vp, _i, _f]),

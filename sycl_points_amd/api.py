@@ -2285,3 +2285,122 @@ class Registration:
     @staticmethod
     def T_from_device(T_dev):
         return T_dev.cpu().numpy().reshape(4, 4).T.copy()
+
+
+# ------------------------------------------------------------------ host numerics of the odometry loop
+# Thin wrappers of csrc/odometry_host.hip (the C++ facade's pipeline classes call the same entry points). Poses are 4x4 and
+# rotations 3x3 row-major numpy arrays; no device is touched.
+@dataclass
+class AdaptiveAxisParams:
+    """AdaptiveMotionPredictor::Params::AdaptiveAxis (pipeline/adaptive_motion_predictor.hpp:22-27)"""
+    factor_min: float = 0.2
+    factor_max: float = 1.0
+    min_eigenvalue_low: float = 1.0
+    min_eigenvalue_high: float = 10.0
+
+
+@dataclass
+class MotionPredictionParams:
+    """MotionPredictor::Params (pipeline/motion_predictor.hpp:54-56, adaptive_motion_predictor.hpp:21-42)"""
+    rotation: AdaptiveAxisParams = field(default_factory=lambda: AdaptiveAxisParams(min_eigenvalue_low=5.0))
+    translation: AdaptiveAxisParams = field(default_factory=AdaptiveAxisParams)
+    velocity_ema_alpha: float = 1.0
+    mode: str = "GYRO_LIDAR_CV"
+
+    def _c(self):
+        ax = lambda a: _lib.MotionAxisParams(a.factor_min, a.factor_max, a.min_eigenvalue_low, a.min_eigenvalue_high)  # noqa: E731
+        return _lib.MotionPredictParams(ax(self.rotation), ax(self.translation), self.velocity_ema_alpha,
+                                        _lib.MOTION_MODE[self.mode.upper()])
+
+
+class MotionPredictor:
+    """MotionPredictor over AdaptiveMotionPredictor (sp_motion_predict_host); owns the velocity averages. The angular velocity is
+    a rotation vector (axis * rad/s)."""
+
+    def __init__(self, params=None):
+        self.params = params or MotionPredictionParams()
+        self.state = _lib.MotionPredictState()
+        self.last_factors = None  # (rotation, translation) of the latest predict
+
+    def predict(self, linear_velocity, angular_velocity, odom, dt, H_raw=None, inlier=0, registrated=False,
+                gyro_delta_rotation_lidar=None, imu_se3_pose=None):
+        T, f = np.zeros(16, np.float32), np.zeros(2, np.float32)
+        H = None if H_raw is None else _f32(H_raw, 36)
+        g = None if gyro_delta_rotation_lidar is None else _f32(np.asarray(gyro_delta_rotation_lidar, np.float32).T, 9)
+        se3 = None if imu_se3_pose is None else _f32(_T16(imu_se3_pose), 16)
+        check(_lib.lib().sp_motion_predict_host(C.byref(self.params._c()), C.byref(self.state), _hp(_f32(linear_velocity, 3)),
+                                                _hp(_f32(angular_velocity, 3)), _hp(_f32(_T16(odom), 16)), float(dt), _hp(H),
+                                                int(inlier), int(bool(registrated)), _hp(g), _hp(se3), _hp(T), _hp(f)))
+        self.last_factors = (float(f[0]), float(f[1]))
+        return T.reshape(4, 4).T.copy()
+
+
+def velocity_from_poses(prev_pose, cur_pose, dt):
+    """(linear velocity [3], angular speed, axis [3]) of prev^-1 * cur over dt (sp_velocity_from_poses_host,
+    pipeline/lidar_odometry.hpp:282-286)"""
+    lin, aa = np.zeros(3, np.float32), np.zeros(4, np.float32)
+    check(_lib.lib().sp_velocity_from_poses_host(_hp(_f32(_T16(prev_pose), 16)), _hp(_f32(_T16(cur_pose), 16)), float(dt), _hp(lin), _hp(aa)))
+    return lin, float(aa[0]), aa[1:].copy()
+
+
+def keyframe_decision(last_keyframe_pose, current_pose, last_keyframe_time, timestamp, distance_threshold=2.0,
+                      angle_threshold_degrees=20.0, time_threshold_seconds=1.0):
+    """Submap::is_keyframe (sp_keyframe_decision_host, pipeline/submapping.hpp:144-161): (is_keyframe, distance, angle in degrees,
+    delta_time)"""
+    flag, m = C.c_int(0), np.zeros(3, np.float64)
+    check(_lib.lib().sp_keyframe_decision_host(_hp(_f32(_T16(last_keyframe_pose), 16)), _hp(_f32(_T16(current_pose), 16)),
+                                               float(last_keyframe_time), float(timestamp), float(distance_threshold),
+                                               float(angle_threshold_degrees), float(time_threshold_seconds), C.byref(flag), _hp(m)))
+    return bool(flag.value), float(m[0]), float(m[1]), float(m[2])
+
+
+@dataclass
+class InitialAlignmentParams:
+    """imu::InitialAlignmentParams (algorithms/imu/imu_initial_alignment.hpp:18-46)"""
+    enable: bool = True
+    required_duration_sec: float = 1.0
+    max_gyro_std: float = 0.01
+    max_accel_std: float = 0.2
+    max_accel_norm_error: float = 0.5
+    estimate_gyro_bias: bool = True
+    max_wait_sec: float = 5.0
+
+
+@dataclass
+class InitialAlignmentResult:
+    """imu::InitialAlignmentResult (imu_initial_alignment.hpp:54-65)"""
+    success: bool
+    R_world_imu: np.ndarray
+    gyro_bias: np.ndarray
+    accel_mean: np.ndarray
+    gyro_std: np.ndarray
+    accel_std: np.ndarray
+    accel_norm: float
+    roll_rad: float
+    pitch_rad: float
+    error_message: str
+    window_size: int
+
+
+def estimate_initial_alignment(stamps, gyro, accel, gravity_world=(0.0, 0.0, -9.80665), params=None, current_bias=None,
+                               bypass_stationarity=False):
+    """imu::estimate_initial_alignment (sp_initial_alignment_host, imu_initial_alignment.hpp:85-204) on a buffer of n samples:
+    stamps [n] in seconds, gyro and accel [n, 3]; current_bias is (gyro_bias, accel_bias)."""
+    p = params or InitialAlignmentParams()
+    t = np.ascontiguousarray(np.asarray(stamps, np.float64).reshape(-1))
+    n = t.size
+    ga = np.ascontiguousarray(np.concatenate([np.asarray(gyro, np.float32).reshape(n, 3), np.asarray(accel, np.float32).reshape(n, 3)], 1))
+    cp = _lib.InitialAlignmentParams(p.required_duration_sec, p.max_gyro_std, p.max_accel_std, p.max_accel_norm_error,
+                                     int(bool(p.estimate_gyro_bias)))
+    r = _lib.InitialAlignmentResult()
+    check(_lib.lib().sp_initial_alignment_host(_hp(t) if n else None, _hp(ga) if n else None, n, _hp(_f32(gravity_world, 3)), C.byref(cp),
+                                               _hp(_bias6(current_bias)), int(bool(bypass_stationarity)), C.byref(r)))
+    v3 = lambda f: np.array(f, np.float32)  # noqa: E731
+    return InitialAlignmentResult(bool(r.success), np.array(r.R_world_imu, np.float32).reshape(3, 3).T.copy(), v3(r.gyro_bias),
+                                  v3(r.accel_mean), v3(r.gyro_std), v3(r.accel_std), float(r.accel_norm), float(r.roll_rad),
+                                  float(r.pitch_rad), r.error_message.decode(), int(r.window_size))
+
+
+def yaw_from_rotation(R):
+    """imu::detail::yaw_from_rotation (sp_yaw_from_rotation_host, imu_initial_alignment.hpp:211-218)"""
+    return float(_lib.lib().sp_yaw_from_rotation_host(_hp(_f32(np.asarray(R, np.float32).T, 9))))

@@ -373,14 +373,6 @@ int invalid(const char* msg) {
     return SP_ERR_INVALID_ARGUMENT;
 }
 
-// quat_mult (imu_deskew.hpp:43-50)
-inline void quat_mult(const float a[4], const float b[4], float r[4]) {
-    r[0] = fmaf(a[3], b[0], fmaf(+a[0], b[3], fmaf(+a[1], b[2], -a[2] * b[1])));
-    r[1] = fmaf(a[3], b[1], fmaf(-a[0], b[2], fmaf(+a[1], b[3], +a[2] * b[0])));
-    r[2] = fmaf(a[3], b[2], fmaf(+a[0], b[1], fmaf(-a[1], b[0], +a[2] * b[3])));
-    r[3] = fmaf(a[3], b[3], fmaf(-a[0], b[0], fmaf(-a[1], b[1], -a[2] * b[2])));
-}
-
 }  // namespace
 }  // namespace sp
 

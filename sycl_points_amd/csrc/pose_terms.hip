@@ -13,55 +13,6 @@ void sp_set_error(const char* msg);
 namespace sp {
 namespace {
 
-// Symmetric 3x3 eigen-pairs by cyclic Jacobi rotations (stands in for Eigen::SelfAdjointEigenSolver<Matrix3f>,
-// degenerate_regularization.hpp:71-78): ascending eigenvalues, unit eigenvectors in the columns of V.
-void eigen_sym3(const float A_in[3][3], float lam[3], float V[3][3]) {
-    float A[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            A[i][j] = 0.5f * (A_in[i][j] + A_in[j][i]);
-            V[i][j] = (i == j) ? 1.0f : 0.0f;
-        }
-    for (int sweep = 0; sweep < 32; ++sweep) {
-        const float off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const float dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (!(off > 1e-18f * dg)) break;
-        static const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2};
-        for (int e = 0; e < 3; ++e) {
-            const int p = P[e], q = Q[e];
-            if (A[p][q] == 0.0f) continue;
-            const float tau = (A[q][q] - A[p][p]) / (2.0f * A[p][q]);
-            const float t = copysignf(1.0f, tau) / (fabsf(tau) + sqrtf(fmaf(tau, tau, 1.0f)));
-            const float c = 1.0f / sqrtf(fmaf(t, t, 1.0f)), s = t * c;
-            for (int k = 0; k < 3; ++k) {
-                const float x = A[k][p], y = A[k][q];
-                A[k][p] = c * x - s * y;
-                A[k][q] = s * x + c * y;
-            }
-            for (int k = 0; k < 3; ++k) {
-                const float x = A[p][k], y = A[q][k];
-                A[p][k] = c * x - s * y;
-                A[q][k] = s * x + c * y;
-            }
-            for (int k = 0; k < 3; ++k) {
-                const float x = V[k][p], y = V[k][q];
-                V[k][p] = c * x - s * y;
-                V[k][q] = s * x + c * y;
-            }
-        }
-    }
-    int idx[3] = {0, 1, 2};
-    for (int i = 0; i < 2; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (A[idx[j]][idx[j]] < A[idx[i]][idx[i]]) { const int t = idx[i]; idx[i] = idx[j]; idx[j] = t; }
-    float Vs[3][3];
-    for (int c = 0; c < 3; ++c) {
-        lam[c] = A[idx[c]][idx[c]];
-        for (int r = 0; r < 3; ++r) Vs[r][c] = V[r][idx[c]];
-    }
-    std::memcpy(V, Vs, sizeof(Vs));
-}
-
 void add_weak_directions(const float* H, int o, float inlier, float threshold, float lambda, float* P) {
     if (!(threshold > 0.0f)) return;
     float blk[3][3], lam[3], V[3][3];
