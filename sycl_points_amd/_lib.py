@@ -348,6 +348,8 @@ INTERNAL_SIGNATURES = {
     "sp_internal_exclusive_scan_u32": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "sp_internal_atan2f_host": (None, [_vp, _vp, _sz, _vp]),
     "sp_internal_fps": (_i, [_i, _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_internal_eigen3": (_i, [_vp, _sz, _vp, _vp, _vp]),
+    "sp_internal_inverse3": (_i, [_vp, _sz, _vp, _vp]),
 }
 VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOXEL_BOX_SHARD_STRIDE
 COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA

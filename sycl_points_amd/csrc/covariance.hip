@@ -9,6 +9,7 @@
 #include "sp_common.h"
 #include "sp_math.h"
 #include "sp_cov_normal.h"
+#include "sp_internal.h"
 
 void sp_set_error(const char* msg);
 
@@ -190,6 +191,26 @@ __global__ __launch_bounds__(kBlock) void cov_normalize_kernel(const float4* __r
     store_cov(out + 4 * (size_t)i, normalize_cov(load_cov(covs + 4 * (size_t)i)));
 }
 
+// ---- sp_internal.h: symmetric_eigen3 and inverse on their own, one lane per row, for their tests
+__global__ __launch_bounds__(kBlock) void eigen3_kernel(const float4* __restrict__ covs, unsigned n,
+                                                        float* __restrict__ vals, float4* __restrict__ vecs) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float ev[3];
+    Mat3 V;
+    symmetric_eigen3(load_cov(covs + 4 * (size_t)i), ev, V);
+    vals[3 * (size_t)i + 0] = ev[0];
+    vals[3 * (size_t)i + 1] = ev[1];
+    vals[3 * (size_t)i + 2] = ev[2];
+    store_cov(vecs + 4 * (size_t)i, V);
+}
+__global__ __launch_bounds__(kBlock) void inverse3_kernel(const float4* __restrict__ mats, unsigned n,
+                                                          float4* __restrict__ out) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    store_cov(out + 4 * (size_t)i, inverse(load_cov(mats + 4 * (size_t)i)));
+}
+
 }  // namespace
 }  // namespace sp
 
@@ -269,5 +290,20 @@ extern "C" int sp_cov_normalize(const float* covs, size_t n, float* covs_out, vo
     cov_normalize_kernel<<<div_up(n, kBlock), kBlock, 0, as_stream(stream)>>>(reinterpret_cast<const float4*>(covs),
                                                                               (unsigned)n,
                                                                               reinterpret_cast<float4*>(covs_out));
+    return launch_status();
+}
+
+extern "C" int sp_internal_eigen3(const float* covs, size_t n, float* vals_out, float* vecs_out, void* stream) {
+    using namespace sp;
+    if (n == 0) return SP_OK;
+    eigen3_kernel<<<div_up(n, kBlock), kBlock, 0, as_stream(stream)>>>(reinterpret_cast<const float4*>(covs), (unsigned)n, vals_out,
+                                                                       reinterpret_cast<float4*>(vecs_out));
+    return launch_status();
+}
+extern "C" int sp_internal_inverse3(const float* mats, size_t n, float* out, void* stream) {
+    using namespace sp;
+    if (n == 0) return SP_OK;
+    inverse3_kernel<<<div_up(n, kBlock), kBlock, 0, as_stream(stream)>>>(reinterpret_cast<const float4*>(mats), (unsigned)n,
+                                                                         reinterpret_cast<float4*>(out));
     return launch_status();
 }

@@ -89,6 +89,11 @@ void sp_internal_atan2f_host(const float* y, const float* x, size_t n, float* ou
  * form 3's points per lane (1, 2, 4, 8); 0 the library's choice. Same order, flags and distances in every form. */
 int sp_internal_fps(int form, const float* points, size_t n, size_t sampling_num, uint32_t first_index, uint32_t* order_out,
                     uint8_t* flags_out_opt, float* min_d2_out_opt, void* workspace, size_t workspace_bytes, void* stream);
+/* sp_math.h's symmetric_eigen3 and inverse on the device and nothing else, one lane per row, for their tests. covs / mats / vecs_out /
+ * out: n rows of 16 floats, the stored covariance layout (a column-major 4x4 whose 3x3 block counts); vals_out: n rows of 3 floats,
+ * ascending; column k of a vecs_out row is the eigenvector of eigenvalue k. All device pointers, rows 16-byte aligned. */
+int sp_internal_eigen3(const float* covs, size_t n, float* vals_out, float* vecs_out, void* stream);
+int sp_internal_inverse3(const float* mats, size_t n, float* out, void* stream);
 
 #ifdef __cplusplus
 }
