@@ -510,7 +510,7 @@ struct CommonParameters {
             float sigma_range = 0.05f;
             float mean_min = 1e-3f;
         };
-        struct EnhancedReflectivity {  // consumed by the reference's ROS node only; `enable` still switches intensity_correction off
+        struct EnhancedReflectivity {  // consumed by the caller that owns the messages (ros2::EnhancedReflectivityCorrector); `enable` switches intensity_correction off
             bool enable = false;
             float clip_max = 5.0f;
             float ring_mean_ema_alpha = 0.5f;

@@ -1255,6 +1255,83 @@ int sp_ogm_export(sp_occupancy_grid_map* map, uint64_t* keys_out, uint32_t* hit_
                   float* log_odds_out, uint32_t* last_updated_out, float* sum_xyz_out, float* cov_sums_out, float* rgb_sums_out,
                   float* intensity_sums_out, size_t out_capacity, size_t* n_out_host, void* stream);
 
+/* ------------------------------------------------------- sensor_msgs/PointCloud2 ingestion (ros2/convert.hpp, ros2/enhanced_reflectivity.hpp)
+ * A PointCloud2 is a byte buffer of n records of point_step bytes plus a list of named, typed fields. The reference unpacks the
+ * coordinates, rgb and intensity in a kernel (convert.hpp:192-248) and leaves the time stamps (:144-190), the whole reflectivity
+ * correction (enhanced_reflectivity.hpp:45-140) and the packing of toROS2msg (convert.hpp:376-426) as host loops over USM-shared
+ * memory. Here all of it runs on the device. Field type codes are sensor_msgs/PointField's. */
+enum { SP_PC2_INT8 = 1, SP_PC2_UINT8 = 2, SP_PC2_INT16 = 3, SP_PC2_UINT16 = 4, SP_PC2_INT32 = 5, SP_PC2_UINT32 = 6,
+       SP_PC2_FLOAT32 = 7, SP_PC2_FLOAT64 = 8 };
+#define SP_PC2_BLOCK_POINTS 256   /* records per workgroup of every kernel of this section */
+#define SP_PC2_MAX_POINT_STEP 240 /* a workgroup's records are staged in LDS: 256 * 240 bytes and the sums' arrays fit 64 KiB */
+#define SP_ER_MAX_RINGS 256       /* EnhancedReflectivityCorrector::MAX_RINGS */
+#define SP_ER_STATE_BYTES (3 * 4 * SP_ER_MAX_RINGS) /* float ref_mean[256], float amb_mean[256], uint32 initialised[256] */
+/* Where the fields of a record are: byte offsets inside the record, -1 = absent. */
+typedef struct sp_pc2_layout {
+    uint32_t point_step;
+    int32_t x_offset, y_offset, z_offset, rgb_offset, intensity_offset, timestamp_offset;
+    uint8_t xyz_type;       /* FLOAT32 / FLOAT64, the same for x, y and z */
+    uint8_t rgb_type;       /* FLOAT32 / UINT32: four bytes either way */
+    uint8_t intensity_type; /* FLOAT32 / UINT16 */
+    uint8_t timestamp_type; /* FLOAT32 (s) / FLOAT64 (s, absolute when > 1e8) / UINT32 (ns) */
+    double start_time_ms;   /* the header stamp (sec * 1000.0 + nanosec * 1e-6): FLOAT64 time stamps are taken relative to it */
+} sp_pc2_layout;
+/* fromROS2msg's field resolution (convert.hpp:38-136) over num_fields (name, offset, datatype) triples. Names: x, y, z; rgb / rgba;
+ * intensity; reflectivity; t / time / timestamp / offset_time (a later field of the same role replaces an earlier one). With
+ * convert_intensity and use_reflectivity_as_intensity a UINT16 reflectivity takes over the intensity (:112-121). An optional field
+ * that is switched off or has a type the reference does not convert is dropped (offset -1, type 0). A missing x, y or z, a
+ * coordinate type other than FLOAT32 / FLOAT64, or three types that are not equal -> SP_ERR_RUNTIME (the reference returns false).
+ * A kept field whose offset + size exceeds point_step -> SP_ERR_INVALID_ARGUMENT (the reference would read past the record), as
+ * are a null pointer and point_step == 0. start_time_ms is set to 0: the caller fills it in. Host only. */
+int sp_pc2_resolve_fields_host(const char* const* names, const uint32_t* offsets, const uint8_t* datatypes, size_t num_fields,
+                               uint32_t point_step, int convert_rgb, int convert_intensity, int use_reflectivity_as_intensity,
+                               sp_pc2_layout* layout_out);
+/* The conversion kernel of fromROS2msg (convert.hpp:192-248) and its host loop over the time stamps (:144-190) as one pass:
+ *   points_out[i] = {float(x), float(y), float(z), 1} (FLOAT64 rounds to nearest);  rgb_out[i] = four bytes, each / 255.0f;
+ *   intensities_out[i] = the float, or float(uint16);  timestamps_out[i] = float(offset_ms) with offset_ms, a double, from
+ *     UINT32   float(u) * 1e-6f (a float, widened)
+ *     FLOAT32  double(raw) * 1e3 if raw is finite and > 0, else 0
+ *     FLOAT64  0 unless raw is finite and >= 0; raw > 1e8 ? raw * 1e3 - start_time_ms : raw * 1e3; a negative result becomes 0
+ *   *max_offset_ms_dev = the largest offset_ms BEFORE the cast to float (what the reference adds to start_time_ms, :186-189).
+ * Each workgroup pulls its SP_PC2_BLOCK_POINTS consecutive records into LDS with aligned 16-byte loads and picks the (unaligned)
+ * fields from there; no load touches a byte at or beyond data_dev + data_bytes rounded up to 16. An attribute whose offset is -1
+ * is not written and its pointer is ignored; max_offset_ms_dev is written, and workspace (sp_pc2_unpack_workspace_bytes(n) bytes
+ * of device memory, 16-byte aligned: one value per workgroup, reduced by a second small launch) used, only with a time stamp field.
+ * layout == NULL -> SP_ERR_INVALID_ARGUMENT; then n == 0 -> SP_OK, nothing enqueued. A null or not 16-byte aligned data_dev, a
+ * null output of a present attribute, a null or not aligned workspace with a time stamp field, point_step == 0 or > SP_PC2_MAX_POINT_STEP, n * point_step > data_bytes, n >= 2^32, a type
+ * outside the lists above, a field running past point_step, a start_time_ms that is not finite -> SP_ERR_INVALID_ARGUMENT
+ * before any HIP call. Enqueue only. */
+size_t sp_pc2_unpack_workspace_bytes(size_t n);
+int sp_pc2_unpack(const void* data_dev, size_t data_bytes, size_t n, const sp_pc2_layout* layout, float* points_out,
+                  float* rgb_out, float* intensities_out, float* timestamps_out, double* max_offset_ms_dev, void* workspace,
+                  void* stream);
+/* toROS2msg's packing loop (convert.hpp:394-426): record i = the 16 bytes of points[i], then, each only where its array is given,
+ * four bytes uint8(clamp(c, 0, 1) * 255.0f) of rgb[i] (truncating; clamp = fminf(fmaxf(c, 0), 1), so NaN gives 0), the float
+ * intensities[i], the double (start_time_ms + double(timestamps[i])) * 1e-3. data_out_dev: n * sp_pc2_pack_point_step(...) bytes,
+ * 16-byte aligned. A null points or data_out_dev, a data_out_dev that is not aligned, n >= 2^32 -> SP_ERR_INVALID_ARGUMENT before
+ * any HIP call. n == 0: SP_OK, nothing enqueued. Enqueue only. */
+uint32_t sp_pc2_pack_point_step(int has_rgb, int has_intensity, int has_timestamp);
+int sp_pc2_pack(const float* points, const float* rgb, const float* intensities, const float* timestamps, size_t n,
+                double start_time_ms, void* data_out_dev, void* stream);
+/* EnhancedReflectivityCorrector::apply (enhanced_reflectivity.hpp:45-140) as three launches and no read-back. Per point:
+ * range_sq = x * x + y * y + z * z, ref = intensity * range_sq, amb = float(ambient) / range_sq, both 0 where range_sq < 1e-6f;
+ * ring and ambient (UINT16) are read from the message's records (data_dev, 16-byte aligned, n * point_step bytes; loads reach
+ * to the next 16-byte boundary at most).
+ *   1. per ring < 256: sums of ref and amb and the count over the points with range_sq >= 1e-6f (:70-102)
+ *   2. per ring with a count: mean = sum / float(count); state = mean on the first observation, else
+ *      ema_alpha * mean + (1 - ema_alpha) * state (:107-123). state_dev: SP_ER_STATE_BYTES, zeroed by the caller once.
+ *   3. intensity = clamp((ref / ref_mean if ref_mean > 0) + (amb / amb_mean if amb_mean > 0), 0, clip_max); 0 for a ring >= 256
+ * The sums are deterministic: workgroup b sums its fixed span of consecutive points in index order, launch 2 adds the spans in
+ * a fixed order (four slices of consecutive spans, each in span order, then the slices in order). No float atomics; the same bits from every call on the same input and state. workspace:
+ * sp_enhanced_reflectivity_workspace_bytes(n) bytes of device memory, 16-byte aligned.
+ * n == 0: SP_OK, nothing enqueued (no ring has points: the state stays). A null pointer, a data_dev that is not aligned,
+ * point_step == 0 or > SP_PC2_MAX_POINT_STEP, a ring or ambient field running past point_step, n >= 2^32 ->
+ * SP_ERR_INVALID_ARGUMENT before any HIP call. Enqueue only. */
+size_t sp_enhanced_reflectivity_workspace_bytes(size_t n);
+int sp_enhanced_reflectivity(const float* points, float* intensities_inout, size_t n, const void* data_dev, uint32_t point_step,
+                             int32_t ring_offset, int ring_is_u8, int32_t ambient_offset, void* state_dev, float ema_alpha,
+                             float clip_max, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

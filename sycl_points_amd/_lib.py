@@ -119,11 +119,21 @@ class InitialAlignmentResult(C.Structure):  # sp_initial_alignment_result
                 ("roll_rad", C.c_float), ("pitch_rad", C.c_float), ("error_message", C.c_char * 96)]
 
 
+class Pc2Layout(C.Structure):  # sp_pc2_layout
+    _fields_ = [("point_step", C.c_uint32), ("x_offset", C.c_int32), ("y_offset", C.c_int32), ("z_offset", C.c_int32),
+                ("rgb_offset", C.c_int32), ("intensity_offset", C.c_int32), ("timestamp_offset", C.c_int32), ("xyz_type", C.c_uint8),
+                ("rgb_type", C.c_uint8), ("intensity_type", C.c_uint8), ("timestamp_type", C.c_uint8), ("start_time_ms", C.c_double)]
+
+
+# sensor_msgs/PointField datatypes (SP_PC2_*)
+PC2_TYPE = {"INT8": 1, "UINT8": 2, "INT16": 3, "UINT16": 4, "INT32": 5, "UINT32": 6, "FLOAT32": 7, "FLOAT64": 8}
+PC2_BLOCK_POINTS, PC2_MAX_POINT_STEP, ER_MAX_RINGS = 256, 240, 256  # SP_PC2_BLOCK_POINTS, SP_PC2_MAX_POINT_STEP, SP_ER_MAX_RINGS
+ER_STATE_BYTES = 3 * 4 * ER_MAX_RINGS  # SP_ER_STATE_BYTES
 MOTION_MODE = {"LIDAR_CV": 0, "GYRO_LIDAR_CV": 1, "IMU_SE3": 2}  # SP_MOTION_*
 # deskew::IMUDeskewStatus (SP_IMU_DESKEW_*)
 IMU_DESKEW_STATUS = ("success", "insufficient_imu_coverage", "no_timestamps", "invalid_scan_duration", "empty_cloud")
 OPT_WANT_DONE, OPT_WANT_LINEARIZE, OPT_WANT_TRIAL = 0, 1, 2
-assert C.sizeof(Linearized) == 192
+assert C.sizeof(Linearized) == 192 and C.sizeof(Pc2Layout) == 40
 assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
 assert C.sizeof(MotionPredictParams) == 40 and C.sizeof(MotionPredictState) == 32 and C.sizeof(InitialAlignmentResult) == 200
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
@@ -328,6 +338,14 @@ SIGNATURES = {
     "sp_ogm_overlap_ratio": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_f), _vp]),
     "sp_ogm_voxel_probability": (_i, [_vp, _vp, C.POINTER(_f), _vp]),
     "sp_ogm_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sp_pc2_resolve_fields_host": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _sz, C.c_uint32, _i, _i, _i,
+                                        C.POINTER(Pc2Layout)]),
+    "sp_pc2_unpack_workspace_bytes": (_sz, [_sz]),
+    "sp_pc2_unpack": (_i, [_vp, _sz, _sz, C.POINTER(Pc2Layout), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sp_pc2_pack_point_step": (C.c_uint32, [_i, _i, _i]),
+    "sp_pc2_pack": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_double, _vp, _vp]),
+    "sp_enhanced_reflectivity_workspace_bytes": (_sz, [_sz]),
+    "sp_enhanced_reflectivity": (_i, [_vp, _vp, _sz, _vp, C.c_uint32, C.c_int32, _i, C.c_int32, _vp, _f, _f, _vp, _vp]),
 }
 
 

@@ -2404,3 +2404,156 @@ def estimate_initial_alignment(stamps, gyro, accel, gravity_world=(0.0, 0.0, -9.
 def yaw_from_rotation(R):
     """imu::detail::yaw_from_rotation (sp_yaw_from_rotation_host, imu_initial_alignment.hpp:211-218)"""
     return float(_lib.lib().sp_yaw_from_rotation_host(_hp(_f32(np.asarray(R, np.float32).T, 9))))
+
+
+# ------------------------------------------------------------------ sensor_msgs/PointCloud2 (ros2/convert.hpp, ros2/enhanced_reflectivity.hpp)
+def _pc2_type(t):
+    return _lib.PC2_TYPE[t] if isinstance(t, str) else int(t)
+
+
+def _pc2_bytes(data, device="cuda"):
+    """the message's bytes as a uint8 CUDA tensor: a device tensor as it is, anything else (bytes, numpy) uploaded"""
+    if isinstance(data, torch.Tensor):
+        if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
+            raise SpError(1, "expected a contiguous uint8 CUDA tensor")
+        return data.reshape(-1)
+    return torch.from_numpy(np.frombuffer(bytes(data), np.uint8).copy() if isinstance(data, (bytes, bytearray, memoryview))
+                            else np.ascontiguousarray(data).view(np.uint8).reshape(-1)).to(device)
+
+
+def resolve_pointcloud2_fields(fields, point_step, convert_rgb=True, convert_intensity=True, use_reflectivity_as_intensity=True):
+    """fromROS2msg's field resolution (sp_pc2_resolve_fields_host, ros2/convert.hpp:38-136). fields: (name, offset, datatype)
+    triples, the datatype a sensor_msgs/PointField code or its name ("FLOAT32"). Returns the _lib.Pc2Layout; SpError code 2 where
+    the reference returns false, code 1 for a field that runs past point_step."""
+    fields = list(fields)
+    nf = len(fields)
+    names = (C.c_char_p * max(nf, 1))(*[str(f[0]).encode() for f in fields])
+    offsets = (C.c_uint32 * max(nf, 1))(*[int(f[1]) for f in fields])
+    types = (C.c_uint8 * max(nf, 1))(*[_pc2_type(f[2]) for f in fields])
+    layout = _lib.Pc2Layout()
+    check(_lib.lib().sp_pc2_resolve_fields_host(names, offsets, types, nf, int(point_step), int(bool(convert_rgb)),
+                                                int(bool(convert_intensity)), int(bool(use_reflectivity_as_intensity)), C.byref(layout)))
+    return layout
+
+
+def from_pointcloud2(data, fields, point_step, stamp=(0, 0), num_points=None, convert_rgb=True, convert_intensity=True,
+                     use_reflectivity_as_intensity=True, is_bigendian=False):
+    """ros2::fromROS2msg (ros2/convert.hpp:34-320) on a message given by its parts: `data` the records (a uint8 CUDA tensor is used
+    where it is; bytes or numpy are uploaded), `fields` (name, offset, datatype) triples, `stamp` the header's (sec, nanosec),
+    num_points = width * height (default: all whole records of data). One sp_pc2_unpack fills points, rgb, intensities and
+    timestamp_offsets; start_time_ms is the stamp and end_time_ms = start_time_ms + the largest offset (one 8-byte read-back).
+    None where the reference returns false (no or unsupported x / y / z) and for a big-endian message, which the reference
+    misreads. An empty message gives an empty cloud."""
+    if is_bigendian:
+        print("Not supported big-endian point cloud", file=sys.stderr)
+        return None
+    try:
+        layout = resolve_pointcloud2_fields(fields, point_step, convert_rgb, convert_intensity, use_reflectivity_as_intensity)
+    except SpError as e:
+        if e.code != _lib.SP_ERR_RUNTIME:
+            raise
+        print(_lib.lib().sp_last_error().decode(), file=sys.stderr)
+        return None
+    buf = _pc2_bytes(data)
+    n = int(buf.numel()) // int(point_step) if num_points is None else int(num_points)
+    dev = buf.device
+    cloud = PointCloudShared(device=dev)
+    cloud.start_time_ms = cloud.end_time_ms = 0.0
+    if n == 0:
+        return cloud
+    layout.start_time_ms = float(stamp[0]) * 1000.0 + float(stamp[1]) * 1e-6
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    cloud.points = new(n, 4)
+    if layout.rgb_offset >= 0:
+        cloud.rgb = new(n, 4)
+    if layout.intensity_offset >= 0:
+        cloud.intensities = new(n)
+    max_ms = ws = None
+    L = _lib.lib()
+    if layout.timestamp_offset >= 0:
+        cloud.timestamp_offsets = new(n)
+        max_ms = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(max(L.sp_pc2_unpack_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+    check(L.sp_pc2_unpack(_ptr(buf), int(buf.numel()), n, C.byref(layout), _ptr(cloud.points), _ptr(cloud.rgb),
+                          _ptr(cloud.intensities), _ptr(cloud.timestamp_offsets), _ptr(max_ms), _ptr(ws), _stream()))
+    if max_ms is not None:
+        cloud.start_time_ms = layout.start_time_ms
+        cloud.end_time_ms = cloud.start_time_ms + float(max_ms.item())
+    return cloud
+
+
+def to_pointcloud2(cloud):
+    """ros2::toROS2msg (ros2/convert.hpp:331-429) without the message type: (data, fields, point_step) with data a uint8 CUDA
+    tensor of cloud.size() records packed by sp_pc2_pack and fields (name, offset, datatype, count) tuples. The `timestamp`
+    field is declared where its data is (the reference declares it 4 bytes further), so from_pointcloud2 reads it back."""
+    n = cloud.size()
+    has_rgb, has_int, has_ts = cloud.has_rgb(), cloud.has_intensity(), cloud.has_timestamps()
+    T = _lib.PC2_TYPE
+    fields = [("x", 0, T["FLOAT32"], 1), ("y", 4, T["FLOAT32"], 1), ("z", 8, T["FLOAT32"], 1)]
+    offset = 16
+    for name, present, dtype, size in (("rgb", has_rgb, "UINT32", 4), ("intensity", has_int, "FLOAT32", 4),
+                                       ("timestamp", has_ts, "FLOAT64", 8)):
+        if present:
+            fields.append((name, offset, T[dtype], 1))
+            offset += size
+    step = int(_lib.lib().sp_pc2_pack_point_step(int(has_rgb), int(has_int), int(has_ts)))
+    assert step == offset
+    data = torch.empty(n * step, dtype=torch.uint8, device=cloud.points.device)
+    if n:
+        check(_lib.lib().sp_pc2_pack(_ptr(_dev_f32(cloud.points, 4)), _ptr(_dev_f32(cloud.rgb, 4)) if has_rgb else None,
+                                     _ptr(_dev_f32(cloud.intensities)) if has_int else None,
+                                     _ptr(_dev_f32(cloud.timestamp_offsets)) if has_ts else None, n,
+                                     float(getattr(cloud, "start_time_ms", 0.0)), _ptr(data), _stream()))
+    return data, fields, step
+
+
+class EnhancedReflectivityCorrector:
+    """ros2::EnhancedReflectivityCorrector (ros2/enhanced_reflectivity.hpp:32-194): range and ambient compensation of an Ouster
+    scan's intensity, normalised per ring by means that are kept across scans (EMA). The means live on the device
+    (`state`: 256 ref means, 256 amb means, 256 initialised flags) and sp_enhanced_reflectivity never reads anything back."""
+
+    MAX_RINGS = _lib.ER_MAX_RINGS
+
+    def __init__(self, ema_alpha=0.5):
+        self.ema_alpha = float(ema_alpha)
+        self.state = None
+        self._fields = None  # (ring_offset, ring_is_u8, ambient_offset), parsed once (:145-175)
+
+    def set_ema_alpha(self, alpha):
+        self.ema_alpha = float(alpha)
+
+    def _parse_fields(self, fields):
+        if self._fields is not None:
+            return True
+        ambient = ring = None
+        for f in fields:
+            if f[0] == "ambient":
+                ambient = (int(f[1]), _pc2_type(f[2]))
+            elif f[0] == "ring":
+                ring = (int(f[1]), _pc2_type(f[2]))
+        T = _lib.PC2_TYPE
+        if ambient is None or ring is None or ambient[1] != T["UINT16"] or ring[1] not in (T["UINT8"], T["UINT16"]):
+            return False
+        self._fields = (ring[0], ring[1] == T["UINT8"], ambient[0])
+        return True
+
+    def apply(self, cloud, data, fields, point_step, clip_max=5.0):
+        """apply(cloud, msg, clip_max) (:45-140) with the message given by its parts; `data` as for from_pointcloud2 (hand it the
+        tensor from_pointcloud2 was given and nothing is uploaded). False, the cloud untouched, without intensities or without an
+        `ambient` (UINT16) and a `ring` (UINT8 / UINT16) field."""
+        if not cloud.has_intensity() or not self._parse_fields(fields):
+            return False
+        n = cloud.size()
+        buf = _pc2_bytes(data, cloud.points.device)
+        if n * int(point_step) > buf.numel():
+            raise SpError(1, "[EnhancedReflectivityCorrector] the message holds fewer records than the cloud has points")
+        dev = cloud.points.device
+        if self.state is None:
+            self.state = torch.zeros(_lib.ER_STATE_BYTES // 4, dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        ws = torch.empty(max(L.sp_enhanced_reflectivity_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+        ring_offset, ring_is_u8, ambient_offset = self._fields
+        check(L.sp_enhanced_reflectivity(_ptr(_dev_f32(cloud.points, 4)), _ptr(_dev_f32(cloud.intensities)), n, _ptr(buf),
+                                         int(point_step), ring_offset, int(ring_is_u8), ambient_offset, _ptr(self.state),
+                                         self.ema_alpha, float(clip_max), _ptr(ws), _stream()))
+        return True
