@@ -1083,6 +1083,114 @@ int sp_initial_alignment_host(const double* stamps_host, const float* gyro_accel
 /* imu::detail::yaw_from_rotation (:211-218): atan2(R10, R00), 0 when R00^2 + R10^2 < 1e-12. */
 float sp_yaw_from_rotation_host(const float* R9_colmajor);
 
+/* ---- tightly coupled LiDAR-inertial alignment in 15 DoF (algorithms/imu/imu_factor.hpp = A, algorithms/lio/lio_registration.hpp
+ * = B, algorithms/registration/dogleg_step.hpp). HOST memory only, no device is touched, no stream. The per-point work of LIO is
+ * sp_gicp_linearize / sp_gicp_error; these are the 15x15 algebra and the control flow around them.
+ * Every 15x15 matrix is COLUMN-major (as sp_imu_preint_reset takes its covariance); the 6x6 of sp_linearized stays row-major.
+ * A state is 21 floats: position 3, rotation 9 (column-major), velocity 3, accelerometer bias 3, gyroscope bias 3. The
+ * error-state order is [dp, dphi, dv, db_a, db_g] (indices 0, 3, 6, 9, 12; imu::State::kIdx*). LDL^T is Eigen's (diagonal pivoting,
+ * left-looking, failure on a zero pivot under a non-zero column; "positive" = vectorD().minCoeff() > 0), the algorithm of
+ * sp_ldlt6_solve_host for any size. A null argument not named optional -> SP_ERR_INVALID_ARGUMENT. */
+/* compute_manifold_residual (A:71-85): r = x_op (-) x_pred, the rotation part so3_log(quat(R_pred^T R_op)). */
+int sp_imu_manifold_residual_host(const float* x_pred21, const float* x_op21, float* r15_out);
+/* compute_imu_hessian_gradient (A:116-141): H = P^-1, b = P^-1 r through one LDL^T of P. *valid_out = 0 with H = 0 and b = 0 when
+ * the factorisation fails or its smallest D is <= 0. */
+int sp_imu_hessian_gradient_host(const float* x_pred21, const float* x_op21, const float* P225, float* H225_out, float* b15_out,
+                                 int* valid_out);
+/* compute_imu_gradient (A:154-157): b = H r. */
+int sp_imu_gradient_host(const float* x_pred21, const float* x_op21, const float* H225, float* b15_out);
+typedef struct sp_lio_linearized { /* LIOLinearizedResult (lio_linearized_result.hpp) */
+    float H[225]; /* column-major */
+    float b[15];
+    float error_icp, error_imu;
+    uint32_t inlier;
+    uint32_t pad;
+} sp_lio_linearized; /* 976 bytes */
+/* add_icp_factor (B:94-113): the ICP system ([d_omega, d_t], body frame) is added into the rotation / position blocks, the
+ * translation blocks rotated into the world frame with R_world_lidar; error_icp += weight * error, inlier += inlier. */
+int sp_lio_add_icp_factor_host(sp_lio_linearized* result, const sp_linearized* icp, const float* R_world_lidar9, float weight);
+typedef struct sp_lio_directional_params { /* DirectionalIcpWeightingParams (lio_registration_params.hpp:28-38) */
+    int enable;                            /* 1 */
+    float trans_min_eigenvalue_per_inlier; /* 10 */
+    float rot_min_eigenvalue_per_inlier;   /* 10 */
+    float trans_weak_direction_scale;      /* 0.2 */
+    float rot_weak_direction_scale;        /* 0.2 */
+} sp_lio_directional_params;
+/* apply_directional_icp_weighting (B:144-202) on a factor that holds the ICP contribution only: nothing when disabled or
+ * inlier == 0; the pose blocks symmetrised; per 3x3 diagonal block a filter sum_i sqrt(clamp(scale_i)) q_i q_i^T with scale_i = 0
+ * for an eigenvalue <= 0, else max(weak_scale, lambda_i / (min_per_inlier * inlier)) when that threshold is > 0, else 1; the pose
+ * system becomes F H F and F F b. */
+int sp_lio_directional_weighting_host(sp_lio_linearized* icp_factor, const sp_lio_directional_params* params);
+/* solve_ldlt (B:224-238): H delta = -b; P_post225_opt (may be NULL) = H^-1. *ok_out = 0 with delta = 0 (and P_post = 0) when the
+ * factorisation fails or is not positive. */
+int sp_lio_solve_ldlt_host(const float* H225, const float* b15, float* delta15_out, float* P_post225_opt, int* ok_out);
+/* retract (B:260-273): p + dp, R * quat_to_rot(so3_exp(dphi)), v + dv, b_a + db_a, b_g + db_g. */
+int sp_lio_retract_host(const float* x21, const float* delta15, float* x_out21);
+/* imu_to_lidar_jacobian (B:308-323): identity but J[phi, phi] = R_lidar_imu and J[p, phi] = -R_world_lidar R_lidar_imu
+ * skew(t_lidar_in_imu), T_imu_to_lidar column-major 4x4. */
+int sp_lio_imu_to_lidar_jacobian_host(const float* T_imu_to_lidar16, const float* R_world_lidar9, float* J225_out);
+/* transform_covariance_imu_to_lidar (lidar_to_imu == 0: J P J^T) and transform_covariance_lidar_to_imu (lidar_to_imu != 0:
+ * J^-1 P J^-T with the analytic inverse) (B:340-381). P_out225 must not be P225. */
+int sp_lio_transform_covariance_host(const float* P225, const float* T_imu_to_lidar16, const float* R_world_lidar9, int lidar_to_imu,
+                                     float* P_out225);
+/* compute_dogleg_step<N> (dogleg_step.hpp:33-102) for n = 6 or 15 (any other n -> SP_ERR_INVALID_ARGUMENT): H n x n column-major
+ * (it is symmetric), g[n]. For n = 6 the arithmetic is that of sp_dogleg_step_host, whose signature stays as it is. */
+int sp_dogleg_step_n_host(int n, const float* H, const float* g, float trust_region_radius, float* p_out, float* step_norm_out,
+                          float* predicted_reduction_out);
+typedef struct sp_lio_params { /* LIORegistrationParams (lio_registration_params.hpp:41-49) */
+    sp_opt_params opt; /* optimization + criteria; max_iterations = total_iterations, summed over all robust levels */
+    int robust_auto_scale; /* LIORobustScheduleParams: 0 */
+    float robust_init_scale, robust_min_scale;                   /* 10, 0.5 */
+    float rotation_robust_init_scale, rotation_robust_min_scale; /* 10, 0.5 */
+    int robust_auto_scaling_iter;                                /* 4 */
+    float invalid_regularization_factor;                         /* 1e4 */
+    sp_lio_directional_params directional;
+} sp_lio_params;
+typedef struct sp_lio_factor_facts { /* what the loop reads of RegistrationFactorParams */
+    int residual_dim;    /* 1 for POINT_TO_PLANE / GENZ, 3 otherwise (B:412-415) */
+    int robust_is_none;  /* robust.type == NONE: no auto scaling (B:444-445) */
+    float robust_default_scale, rotation_robust_default_scale; /* the scales of the single level without auto scaling */
+} sp_lio_factor_facts;
+typedef struct sp_lio_request {
+    int want;             /* SP_OPT_WANT_* */
+    int level, iteration; /* robust level and its solver iteration */
+    float robust_scale, rotation_robust_scale; /* of the level in force */
+    float state[21];      /* LINEARIZE: the operating state; TRIAL: the state to evaluate; DONE: the final state */
+    float T[16];          /* its pose, column-major */
+    float T_lin[16];      /* pose of the latest linearisation */
+    float damping;        /* lambda (GN, LM) / trust-region radius (dog-leg) in force */
+    float icp_weight;     /* the chi-square weight of the latest linearisation (1 before the first) */
+} sp_lio_request;
+typedef struct sp_lio_result { /* LIORegistrationResult */
+    float state[21];
+    float posterior_covariance[225];
+    uint32_t iterations; /* every outer iteration, rejected ones too */
+    uint32_t inlier;     /* of the last ICP linearisation, unweighted */
+    float error;
+    uint32_t converged;  /* always 1 (B:643) */
+} sp_lio_result;
+/* LIORegistration::align (B:396-648) as a state machine in the shape of sp_opt_stepper_*: the caller linearises
+ * (Registration::compute_linearized_result at T with initial_pose = the predicted pose and the request's two scales) and
+ * evaluates trials (compute_error_frozen at T) and the stepper does everything else: the IMU prior from ONE factorisation at
+ * (x_pred, x_pred), from the second iteration on its gradient only; icp_weight = 1 / max(1, 2 error / (dim inlier - 6));
+ * directional weighting of the ICP-only factor; invalid_regularization_factor * I on velocity and biases when the prior is
+ * invalid; GN (a failed solve ends the level), LM (a TRIAL at the operating state first, then up to max_inner trials; none
+ * accepted ends the level), dog-leg (a TRIAL at the operating state first; step on the undamped H, the bias freeze before the
+ * predicted reduction; predicted <= 0 or rho < eta1 shrinks the radius, counts the iteration and linearises again at the same
+ * state); update_bias == 0 zeroes both bias segments of every candidate; convergence leaves the current level only; the robust
+ * schedule of B:443-476 with its three messages on stderr; the posterior of B:663-685. total_iterations 0: done at once, state =
+ * predicted, posterior = previous, iterations 0, inlier 0, error FLT_MAX. An answer of the kind that was not asked for is
+ * SP_ERR_INVALID_ARGUMENT and changes nothing. */
+typedef struct sp_lio_stepper sp_lio_stepper;
+int sp_lio_stepper_create(const sp_lio_params* params, const sp_lio_factor_facts* facts, const float* predicted_state21,
+                          const float* predicted_covariance225, const float* previous_posterior_covariance225, int update_bias,
+                          sp_lio_stepper** out);
+void sp_lio_stepper_destroy(sp_lio_stepper* stepper);
+int sp_lio_stepper_next(const sp_lio_stepper* stepper, sp_lio_request* out);
+int sp_lio_stepper_linearized(sp_lio_stepper* stepper, const sp_linearized* lin_host);
+int sp_lio_stepper_trial(sp_lio_stepper* stepper, float error, uint32_t inlier);
+int sp_lio_stepper_result(const sp_lio_stepper* stepper, sp_lio_result* out);
+
 /* ----------------------------------------------------------------------------------------- multi-GPU */
 
 /* One process per GPU; the source cloud is sharded over the ranks, the target (points, covariances, grid, prepared rows)

@@ -119,6 +119,39 @@ class InitialAlignmentResult(C.Structure):  # sp_initial_alignment_result
                 ("roll_rad", C.c_float), ("pitch_rad", C.c_float), ("error_message", C.c_char * 96)]
 
 
+class LioLinearized(C.Structure):  # sp_lio_linearized
+    _fields_ = [("H", C.c_float * 225), ("b", C.c_float * 15), ("error_icp", C.c_float), ("error_imu", C.c_float),
+                ("inlier", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LioDirectionalParams(C.Structure):  # sp_lio_directional_params
+    _fields_ = [("enable", C.c_int), ("trans_min_eigenvalue_per_inlier", C.c_float), ("rot_min_eigenvalue_per_inlier", C.c_float),
+                ("trans_weak_direction_scale", C.c_float), ("rot_weak_direction_scale", C.c_float)]
+
+
+class LioParams(C.Structure):  # sp_lio_params
+    _fields_ = [("opt", OptParams), ("robust_auto_scale", C.c_int), ("robust_init_scale", C.c_float), ("robust_min_scale", C.c_float),
+                ("rotation_robust_init_scale", C.c_float), ("rotation_robust_min_scale", C.c_float),
+                ("robust_auto_scaling_iter", C.c_int), ("invalid_regularization_factor", C.c_float),
+                ("directional", LioDirectionalParams)]
+
+
+class LioFactorFacts(C.Structure):  # sp_lio_factor_facts
+    _fields_ = [("residual_dim", C.c_int), ("robust_is_none", C.c_int), ("robust_default_scale", C.c_float),
+                ("rotation_robust_default_scale", C.c_float)]
+
+
+class LioRequest(C.Structure):  # sp_lio_request
+    _fields_ = [("want", C.c_int), ("level", C.c_int), ("iteration", C.c_int), ("robust_scale", C.c_float),
+                ("rotation_robust_scale", C.c_float), ("state", C.c_float * 21), ("T", C.c_float * 16), ("T_lin", C.c_float * 16),
+                ("damping", C.c_float), ("icp_weight", C.c_float)]
+
+
+class LioResult(C.Structure):  # sp_lio_result
+    _fields_ = [("state", C.c_float * 21), ("posterior_covariance", C.c_float * 225), ("iterations", C.c_uint32),
+                ("inlier", C.c_uint32), ("error", C.c_float), ("converged", C.c_uint32)]
+
+
 class Pc2Layout(C.Structure):  # sp_pc2_layout
     _fields_ = [("point_step", C.c_uint32), ("x_offset", C.c_int32), ("y_offset", C.c_int32), ("z_offset", C.c_int32),
                 ("rgb_offset", C.c_int32), ("intensity_offset", C.c_int32), ("timestamp_offset", C.c_int32), ("xyz_type", C.c_uint8),
@@ -136,6 +169,8 @@ OPT_WANT_DONE, OPT_WANT_LINEARIZE, OPT_WANT_TRIAL = 0, 1, 2
 assert C.sizeof(Linearized) == 192 and C.sizeof(Pc2Layout) == 40
 assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
 assert C.sizeof(MotionPredictParams) == 40 and C.sizeof(MotionPredictState) == 32 and C.sizeof(InitialAlignmentResult) == 200
+assert C.sizeof(LioLinearized) == 976 and C.sizeof(LioParams) == 68 + 7 * 4 + 20 and C.sizeof(LioRequest) == 4 * 60
+assert C.sizeof(LioResult) == 4 * 250 and C.sizeof(LioFactorFacts) == 16
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
 _vp, _sz, _f, _i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
@@ -315,6 +350,22 @@ SIGNATURES = {
     "sp_keyframe_decision_host": (_i, [_vp, _vp, C.c_double, C.c_double, _f, _f, _f, C.POINTER(_i), _vp]),
     "sp_initial_alignment_host": (_i, [_vp, _vp, _sz, _vp, C.POINTER(InitialAlignmentParams), _vp, _i, C.POINTER(InitialAlignmentResult)]),
     "sp_yaw_from_rotation_host": (_f, [_vp]),
+    "sp_imu_manifold_residual_host": (_i, [_vp, _vp, _vp]),
+    "sp_imu_hessian_gradient_host": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    "sp_imu_gradient_host": (_i, [_vp, _vp, _vp, _vp]),
+    "sp_lio_add_icp_factor_host": (_i, [C.POINTER(LioLinearized), C.POINTER(Linearized), _vp, _f]),
+    "sp_lio_directional_weighting_host": (_i, [C.POINTER(LioLinearized), C.POINTER(LioDirectionalParams)]),
+    "sp_lio_solve_ldlt_host": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    "sp_lio_retract_host": (_i, [_vp, _vp, _vp]),
+    "sp_lio_imu_to_lidar_jacobian_host": (_i, [_vp, _vp, _vp]),
+    "sp_lio_transform_covariance_host": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "sp_dogleg_step_n_host": (_i, [_i, _vp, _vp, _f, _vp, C.POINTER(_f), C.POINTER(_f)]),
+    "sp_lio_stepper_create": (_i, [C.POINTER(LioParams), C.POINTER(LioFactorFacts), _vp, _vp, _vp, _i, C.POINTER(_vp)]),
+    "sp_lio_stepper_destroy": (None, [_vp]),
+    "sp_lio_stepper_next": (_i, [_vp, C.POINTER(LioRequest)]),
+    "sp_lio_stepper_linearized": (_i, [_vp, C.POINTER(Linearized)]),
+    "sp_lio_stepper_trial": (_i, [_vp, _f, C.c_uint32]),
+    "sp_lio_stepper_result": (_i, [_vp, C.POINTER(LioResult)]),
     "sp_vhm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
     "sp_vhm_destroy": (None, [_vp]),
     "sp_vhm_set": (_i, [_vp, _i, _f]),

@@ -1736,6 +1736,15 @@ class RegistrationParams:
     map_prior_trans_base_sigma: float = 1e-2
 
 
+def _opt_params(p):
+    """sp_opt_params of a RegistrationParams"""
+    return _lib.OptParams({"GN": 0, "LM": 1, "DOGLEG": 2}[p.optimization_method], p.max_iterations, p.criteria_rotation,
+                          p.criteria_translation, p.gn_lambda, p.lm_max_inner_iterations, p.lm_lambda_factor,
+                          p.lm_init_lambda, p.lm_max_lambda, p.lm_min_lambda, p.dogleg_initial_trust_region_radius,
+                          p.dogleg_min_trust_region_radius, p.dogleg_max_trust_region_radius, p.dogleg_eta1, p.dogleg_eta2,
+                          p.dogleg_gamma_decrease, p.dogleg_gamma_increase)
+
+
 @dataclass
 class RegistrationResult:
     """result.hpp:12-28"""
@@ -1951,12 +1960,7 @@ class Registration:
 
     def opt_params(self):
         """sp_opt_params of these RegistrationParams."""
-        p = self.params
-        return _lib.OptParams({"GN": 0, "LM": 1, "DOGLEG": 2}[p.optimization_method], p.max_iterations, p.criteria_rotation,
-                              p.criteria_translation, p.gn_lambda, p.lm_max_inner_iterations, p.lm_lambda_factor,
-                              p.lm_init_lambda, p.lm_max_lambda, p.lm_min_lambda, p.dogleg_initial_trust_region_radius,
-                              p.dogleg_min_trust_region_radius, p.dogleg_max_trust_region_radius, p.dogleg_eta1, p.dogleg_eta2,
-                              p.dogleg_gamma_decrease, p.dogleg_gamma_increase)
+        return _opt_params(self.params)
 
     def align_optimize(self, source, prepared_target, initial_guess=None, robust_scales=None, sort_by_cell=True, prepare=True,
                        enqueue_only=False):
@@ -2404,6 +2408,281 @@ def estimate_initial_alignment(stamps, gyro, accel, gravity_world=(0.0, 0.0, -9.
 def yaw_from_rotation(R):
     """imu::detail::yaw_from_rotation (sp_yaw_from_rotation_host, imu_initial_alignment.hpp:211-218)"""
     return float(_lib.lib().sp_yaw_from_rotation_host(_hp(_f32(np.asarray(R, np.float32).T, 9))))
+
+
+# ------------------------------------------------------------------ LiDAR-inertial alignment (imu/imu_factor.hpp, lio/*.hpp)
+@dataclass
+class IMUState:
+    """imu::State (imu_factor.hpp:43-60). Error-state order [dp, dphi, dv, db_a, db_g]."""
+    position: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    rotation: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))
+    velocity: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    accel_bias: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    gyro_bias: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    kIdxPos, kIdxRot, kIdxVel, kIdxAccBias, kIdxGyrBias, kDOF = 0, 3, 6, 9, 12, 15
+
+    def pack(self):
+        """The 21 floats of the C ABI: p3, R9 column-major, v3, b_a3, b_g3."""
+        return np.concatenate([_f32(self.position, 3), _f32(np.asarray(self.rotation, np.float32).T, 9), _f32(self.velocity, 3),
+                               _f32(self.accel_bias, 3), _f32(self.gyro_bias, 3)])
+
+    @staticmethod
+    def unpack(s):
+        s = np.array(s, np.float32)
+        return IMUState(s[0:3].copy(), s[3:12].reshape(3, 3).T.copy(), s[12:15].copy(), s[15:18].copy(), s[18:21].copy())
+
+    def pose(self):
+        T = identity()
+        T[:3, :3], T[:3, 3] = self.rotation, self.position
+        return T
+
+
+@dataclass
+class LIORobustScheduleParams:
+    """lio_registration_params.hpp:11-18"""
+    auto_scale: bool = False
+    init_scale: float = 10.0
+    min_scale: float = 0.5
+    rotation_init_scale: float = 10.0
+    rotation_min_scale: float = 0.5
+    auto_scaling_iter: int = 4
+
+
+@dataclass
+class DirectionalIcpWeightingParams:
+    """lio_registration_params.hpp:28-38"""
+    enable: bool = True
+    trans_min_eigenvalue_per_inlier: float = 10.0
+    rot_min_eigenvalue_per_inlier: float = 10.0
+    trans_weak_direction_scale: float = 0.2
+    rot_weak_direction_scale: float = 0.2
+
+    def c_struct(self):
+        return _lib.LioDirectionalParams(int(self.enable), self.trans_min_eigenvalue_per_inlier, self.rot_min_eigenvalue_per_inlier,
+                                         self.trans_weak_direction_scale, self.rot_weak_direction_scale)
+
+
+@dataclass
+class RegistrationConvergenceCriteria:
+    """registration_params.hpp:41-44"""
+    translation: float = 1e-3
+    rotation: float = 1e-3
+
+
+@dataclass
+class LIORegistrationParams:
+    """lio_registration_params.hpp:41-49. `optimization` stands for RegistrationOptimizationParams: of the RegistrationParams only
+    optimization_method and the gn / lm / dogleg fields are read."""
+    total_iterations: int = 10
+    criteria: RegistrationConvergenceCriteria = field(default_factory=RegistrationConvergenceCriteria)
+    optimization: RegistrationParams = field(default_factory=RegistrationParams)
+    robust: LIORobustScheduleParams = field(default_factory=LIORobustScheduleParams)
+    invalid_regularization_factor: float = 1e4
+    directional_icp_weighting: DirectionalIcpWeightingParams = field(default_factory=DirectionalIcpWeightingParams)
+
+    def c_struct(self):
+        o = _opt_params(self.optimization)
+        o.max_iterations = int(self.total_iterations)
+        o.crit_rotation, o.crit_translation = self.criteria.rotation, self.criteria.translation
+        r = self.robust
+        return _lib.LioParams(o, int(r.auto_scale), r.init_scale, r.min_scale, r.rotation_init_scale, r.rotation_min_scale,
+                              int(r.auto_scaling_iter), self.invalid_regularization_factor, self.directional_icp_weighting.c_struct())
+
+
+@dataclass
+class LIOLinearizedResult:
+    """lio_linearized_result.hpp"""
+    H: np.ndarray = field(default_factory=lambda: np.zeros((15, 15), np.float32))
+    b: np.ndarray = field(default_factory=lambda: np.zeros(15, np.float32))
+    error_icp: float = 0.0
+    error_imu: float = 0.0
+    inlier: int = 0
+
+    def _c(self):
+        c = _lib.LioLinearized()
+        C.memmove(c.H, _cm15(self.H).ctypes.data, 900)
+        C.memmove(c.b, _f32(self.b, 15).ctypes.data, 60)
+        c.error_icp, c.error_imu, c.inlier = self.error_icp, self.error_imu, int(self.inlier)
+        return c
+
+    def _take(self, c):
+        self.H = np.array(c.H, np.float32).reshape(15, 15).T.copy()
+        self.b = np.array(c.b, np.float32)
+        self.error_icp, self.error_imu, self.inlier = float(c.error_icp), float(c.error_imu), int(c.inlier)
+
+
+@dataclass
+class LIORegistrationResult:
+    """lio_registration_result.hpp: the state, the posterior covariance and the RegistrationResult fields align() fills."""
+    state: IMUState = field(default_factory=IMUState)
+    posterior_covariance: np.ndarray = field(default_factory=lambda: np.zeros((15, 15), np.float32))
+    registration_result: RegistrationResult = field(default_factory=RegistrationResult)
+
+
+def _cm15(M):
+    """15x15 row-major numpy -> 225 floats column-major"""
+    return _f32(np.asarray(M, np.float32).reshape(15, 15).T, 225)
+
+
+def _lin6(icp):
+    """a compute_linearized_result dict (or a Linearized) -> sp_linearized"""
+    if isinstance(icp, Linearized):
+        return icp
+    c = Linearized()
+    C.memmove(c.H, _f32(icp["H"], 36).ctypes.data, 144)
+    C.memmove(c.b, _f32(icp["b"], 6).ctypes.data, 24)
+    c.error, c.inlier = float(icp["error"]), int(icp["inlier"])
+    return c
+
+
+def compute_manifold_residual(x_pred, x_op):
+    """imu::compute_manifold_residual (imu_factor.hpp:71-85)"""
+    r = np.zeros(15, np.float32)
+    check(_lib.lib().sp_imu_manifold_residual_host(_hp(x_pred.pack()), _hp(x_op.pack()), _hp(r)))
+    return r
+
+
+def compute_imu_hessian_gradient(x_pred, x_op, P_pred):
+    """imu::compute_imu_hessian_gradient (imu_factor.hpp:116-141) -> (valid, H_imu, b_imu)"""
+    H, b, ok = np.zeros(225, np.float32), np.zeros(15, np.float32), C.c_int(0)
+    check(_lib.lib().sp_imu_hessian_gradient_host(_hp(x_pred.pack()), _hp(x_op.pack()), _hp(_cm15(P_pred)), _hp(H), _hp(b),
+                                                  C.byref(ok)))
+    return bool(ok.value), H.reshape(15, 15).T.copy(), b
+
+
+def compute_imu_gradient(x_pred, x_op, H_imu):
+    """imu::compute_imu_gradient (imu_factor.hpp:154-157)"""
+    b = np.zeros(15, np.float32)
+    check(_lib.lib().sp_imu_gradient_host(_hp(x_pred.pack()), _hp(x_op.pack()), _hp(_cm15(H_imu)), _hp(b)))
+    return b
+
+
+def add_icp_factor(result, icp, R_world_lidar, weight=1.0):
+    """lio::add_icp_factor (lio_registration.hpp:94-113); `icp` as Registration.compute_linearized_result returns it"""
+    c = result._c()
+    check(_lib.lib().sp_lio_add_icp_factor_host(C.byref(c), C.byref(_lin6(icp)), _hp(_f32(np.asarray(R_world_lidar, np.float32).T, 9)),
+                                                C.c_float(weight)))
+    result._take(c)
+
+
+def add_imu_factor(result, H_imu, b_imu, error=0.0):
+    """lio::add_imu_factor (lio_registration.hpp:129-134)"""
+    result.H = (result.H + np.asarray(H_imu, np.float32)).astype(np.float32)
+    result.b = (result.b + np.asarray(b_imu, np.float32)).astype(np.float32)
+    result.error_imu = float(error)
+
+
+def apply_directional_icp_weighting(icp_factor, params):
+    """lio::apply_directional_icp_weighting (lio_registration.hpp:144-202)"""
+    c, p = icp_factor._c(), params.c_struct()
+    check(_lib.lib().sp_lio_directional_weighting_host(C.byref(c), C.byref(p)))
+    icp_factor._take(c)
+
+
+def solve_ldlt(H, b, want_posterior=False):
+    """lio::solve_ldlt (lio_registration.hpp:224-238) -> (ok, delta[, P_post])"""
+    d, P, ok = np.zeros(15, np.float32), np.zeros(225, np.float32), C.c_int(0)
+    check(_lib.lib().sp_lio_solve_ldlt_host(_hp(_cm15(H)), _hp(_f32(b, 15)), _hp(d), _hp(P) if want_posterior else None,
+                                            C.byref(ok)))
+    return (bool(ok.value), d, P.reshape(15, 15).T.copy()) if want_posterior else (bool(ok.value), d)
+
+
+def retract(state, delta):
+    """lio::retract (lio_registration.hpp:260-273)"""
+    out = np.zeros(21, np.float32)
+    check(_lib.lib().sp_lio_retract_host(_hp(state.pack()), _hp(_f32(delta, 15)), _hp(out)))
+    return IMUState.unpack(out)
+
+
+def imu_to_lidar_jacobian(T_imu_to_lidar, R_world_lidar):
+    """lio::imu_to_lidar_jacobian (lio_registration.hpp:308-323)"""
+    J = np.zeros(225, np.float32)
+    check(_lib.lib().sp_lio_imu_to_lidar_jacobian_host(_hp(_T16(T_imu_to_lidar).reshape(-1)),
+                                                       _hp(_f32(np.asarray(R_world_lidar, np.float32).T, 9)), _hp(J)))
+    return J.reshape(15, 15).T.copy()
+
+
+def _transform_covariance(P, T_imu_to_lidar, R_world_lidar, lidar_to_imu):
+    out = np.zeros(225, np.float32)
+    check(_lib.lib().sp_lio_transform_covariance_host(_hp(_cm15(P)), _hp(_T16(T_imu_to_lidar).reshape(-1)),
+                                                      _hp(_f32(np.asarray(R_world_lidar, np.float32).T, 9)), int(lidar_to_imu), _hp(out)))
+    return out.reshape(15, 15).T.copy()
+
+
+def transform_covariance_imu_to_lidar(P_imu, T_imu_to_lidar, R_world_lidar):
+    """lio::transform_covariance_imu_to_lidar (lio_registration.hpp:340-345)"""
+    return _transform_covariance(P_imu, T_imu_to_lidar, R_world_lidar, 0)
+
+
+def transform_covariance_lidar_to_imu(P_lidar, T_imu_to_lidar, R_world_lidar):
+    """lio::transform_covariance_lidar_to_imu (lio_registration.hpp:366-381)"""
+    return _transform_covariance(P_lidar, T_imu_to_lidar, R_world_lidar, 1)
+
+
+def compute_dogleg_step(H, g, trust_region_radius):
+    """registration::compute_dogleg_step<N> (dogleg_step.hpp:33-102), N = 6 or 15 -> (p, step_norm, predicted_reduction)"""
+    g = np.ascontiguousarray(np.asarray(g, np.float32).reshape(-1))
+    n = g.size
+    Hc = np.ascontiguousarray(np.asarray(H, np.float32).reshape(n, n).T).reshape(-1)
+    p, norm, pred = np.zeros(n, np.float32), C.c_float(0), C.c_float(0)
+    check(_lib.lib().sp_dogleg_step_n_host(n, _hp(Hc), _hp(g), C.c_float(trust_region_radius), _hp(p), C.byref(norm), C.byref(pred)))
+    return p, float(norm.value), float(pred.value)
+
+
+def lio_factor_facts(params):
+    """sp_lio_factor_facts of a RegistrationParams: what LIORegistration::align reads of the factor (lio_registration.hpp:412-415,
+    444-445, 465-468)"""
+    return _lib.LioFactorFacts(1 if params.reg_type in ("POINT_TO_PLANE", "GENZ") else 3, int(params.robust_type == "NONE"),
+                               params.robust_default_scale, params.rotation_constraint_robust_default_scale)
+
+
+class LIORegistration:
+    """lio::LIORegistration (lio_registration.hpp:384-690): the library's stepper (sp_lio_stepper_*) decides, this class serves
+    its requests from its own Registration: compute_linearized_result for LINEARIZE, compute_error_frozen for TRIAL."""
+
+    def __init__(self, factor_params=None, params=None):
+        self.factor_params = factor_params or RegistrationParams()
+        self.params = params or LIORegistrationParams()
+        self._registration = Registration(self.factor_params)
+
+    def registration_backend(self):
+        return self._registration
+
+    def align(self, source, target, target_knn, predicted_state, predicted_covariance, previous_posterior_covariance,
+              update_bias=True, dt=0.1, previous_pose=None):
+        """lio_registration.hpp:396-648. `dt` and `previous_pose` are the reference's ExecutionOptions fields; no factor of this
+        library reads them."""
+        L = _lib.lib()
+        reg = self._registration
+        reg._validate(source, target)
+        prm, facts = self.params.c_struct(), lio_factor_facts(self.factor_params)
+        initial_pose = predicted_state.pose()
+        h, req, res = C.c_void_p(), _lib.LioRequest(), _lib.LioResult()
+        check(L.sp_lio_stepper_create(C.byref(prm), C.byref(facts), _hp(predicted_state.pack()), _hp(_cm15(predicted_covariance)),
+                                      _hp(_cm15(previous_posterior_covariance)), int(bool(update_bias)), C.byref(h)))
+        try:
+            while True:
+                check(L.sp_lio_stepper_next(h, C.byref(req)))
+                if req.want == _lib.OPT_WANT_DONE:
+                    break
+                pose = np.array(req.T, np.float32).reshape(4, 4).T.copy()
+                if req.want == _lib.OPT_WANT_LINEARIZE:
+                    lin = reg.compute_linearized_result(source, target, target_knn, pose, req.robust_scale, req.rotation_robust_scale,
+                                                        initial_pose=initial_pose)
+                    check(L.sp_lio_stepper_linearized(h, C.byref(_lin6(lin))))
+                else:
+                    error, inlier = reg.compute_error_frozen(source, target, pose, req.robust_scale, req.rotation_robust_scale)
+                    check(L.sp_lio_stepper_trial(h, C.c_float(error), inlier))
+            check(L.sp_lio_stepper_result(h, C.byref(res)))
+        finally:
+            L.sp_lio_stepper_destroy(h)
+        out = LIORegistrationResult()
+        out.state = IMUState.unpack(res.state)
+        out.posterior_covariance = np.array(res.posterior_covariance, np.float32).reshape(15, 15).T.copy()
+        rr = out.registration_result
+        rr.T, rr.converged, rr.iterations = out.state.pose(), bool(res.converged), int(res.iterations)
+        rr.inlier, rr.error = int(res.inlier), float(res.error)
+        return out
 
 
 # ------------------------------------------------------------------ sensor_msgs/PointCloud2 (ros2/convert.hpp, ros2/enhanced_reflectivity.hpp)
