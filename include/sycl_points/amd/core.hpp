@@ -913,6 +913,7 @@ struct PointCloudCPU {
 /// points/point_cloud.hpp:73-476 — six attribute containers + the queue; deep copy constructor, shallow assignment.
 struct PointCloudShared {
     using Ptr = std::shared_ptr<PointCloudShared>;
+    using ConstPtr = std::shared_ptr<const PointCloudShared>;
     sycl_utils::DeviceQueue queue;
     std::shared_ptr<PointContainerShared> points;
     std::shared_ptr<CovarianceContainerShared> covs;

@@ -10,9 +10,12 @@
 //   pipeline/pointcloud_processing.hpp            : pipeline::pointcloud_processing::ProcessingContext, PCProcessor
 //   pipeline/submapping.hpp                       : pipeline::submapping::Submap
 //   pipeline/lidar_odometry.hpp                   : pipeline::lidar_odometry::LiDAROdometryPipeline
-// Callers only: every per-point stage is a class of the other amd/*.hpp files, i.e. a kernel of the C library; the 3x3 / 4x4
-// arithmetic between them is the library's host code (csrc/odometry_host.hip), shared with the Python wrappers. No kernel is
-// launched from this file directly and no point data crosses to the host in it.
+//   pipeline/lidar_inertial_odometry_params.hpp   : pipeline::lidar_inertial_odometry::Parameters
+//   pipeline/lidar_inertial_odometry.hpp          : pipeline::lidar_inertial_odometry::LidarInertialOdometryPipeline
+//   (what the two loops hold word for word lives once, in pipeline::odometry::PipelineCommon)
+// Callers only: every per-point stage is a class of the other amd/*.hpp files, i.e. a kernel of the C library; the 3x3 / 4x4 /
+// 15x15 arithmetic between them is the library's host code (csrc/odometry_host.hip, csrc/lio_host.hip), shared with the Python
+// wrappers. No kernel is launched from this file directly and no point data crosses to the host in it.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -34,6 +37,7 @@
 #include <vector>
 
 #include "imu.hpp"
+#include "lio.hpp"
 #include "mapping.hpp"
 #include "registration.hpp"
 
@@ -945,12 +949,125 @@ private:
 
 }  // namespace submapping
 
+// ------------------------------------------------------------------------------------------------ what the two loops share
+namespace odometry {
+
+/// What pipeline/lidar_odometry.hpp and pipeline/lidar_inertial_odometry.hpp each hold, word for word: the IMU buffer with its mutex
+/// and rules, the timing maps, a stage's exception as an error result, the three conditions of the scan covariances and the
+/// constructor's widening of the IMU buffer. The two differ in the stderr prefix and in the name of stage 3 only.
+class PipelineCommon {
+public:
+    const auto& get_error_message() const { return error_message_; }
+    const auto& get_current_processing_time() const { return current_processing_time_; }
+    const auto& get_total_processing_times() const { return total_processing_times_; }
+
+    /// lidar_odometry.hpp:85-106, lidar_inertial_odometry.hpp:112-121 — no-op with the IMU disabled; non-finite samples and stamps
+    /// that do not increase are dropped; the buffer is cut to buffer_duration_sec. May be called while process() runs.
+    void add_imu_measurement(const imu::IMUMeasurement& meas) {
+        if (!imu_enabled_) return;
+        std::lock_guard<std::mutex> lock(imu_mutex_);
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(meas.accel[k]) || !std::isfinite(meas.gyro[k])) return;
+        if (!imu_buffer_.empty() && meas.timestamp <= imu_buffer_.back().timestamp) return;
+        const double latest_timestamp = meas.timestamp;
+        imu_buffer_.push_back(meas);
+        while (latest_timestamp - imu_buffer_.front().timestamp > imu_buffer_duration_sec_) imu_buffer_.pop_front();
+    }
+
+    /// lidar_odometry.hpp:110-113, lidar_inertial_odometry.hpp:123-126 — a snapshot
+    std::deque<imu::IMUMeasurement> get_imu_buffer() const {
+        std::lock_guard<std::mutex> lock(imu_mutex_);
+        return imu_buffer_;
+    }
+
+protected:
+    PipelineCommon(const char* log_prefix, const char* registration_stage)
+        : log_prefix_(log_prefix), registration_stage_(registration_stage) {}
+
+    /// lidar_odometry.hpp:41-52, lidar_inertial_odometry.hpp:73-80 — the IMU buffer must outlast the alignment window (the trimming
+    /// keeps span <= buffer_duration_sec); the rules add_imu_measurement applies are those of the widened parameters
+    void adopt_imu_params(CommonParameters::IMU& imu) {
+        if (imu.enable && imu.initial_alignment.enable) {
+            const double need = static_cast<double>(imu.initial_alignment.required_duration_sec) + 0.2;
+            if (imu.buffer_duration_sec < need) imu.buffer_duration_sec = need;
+        }
+        imu_enabled_ = imu.enable;
+        imu_buffer_duration_sec_ = imu.buffer_duration_sec;
+    }
+
+    enum class ProcessName { preprocessing = 0, compute_covariances, registration, build_submap };
+    const char* process_name(ProcessName n) const {  // lidar_odometry.hpp:357-362, lidar_inertial_odometry.hpp:339-344
+        switch (n) {
+            case ProcessName::preprocessing: return "1. preprocessing";
+            case ProcessName::compute_covariances: return "2. compute covariances";
+            case ProcessName::registration: return registration_stage_;
+            case ProcessName::build_submap: return "4. build submap";
+        }
+        return "";
+    }
+    void clear_current_processing_time() {
+        current_processing_time_.clear();
+        for (ProcessName n : {ProcessName::preprocessing, ProcessName::compute_covariances, ProcessName::registration, ProcessName::build_submap})
+            current_processing_time_[process_name(n)] = 0.0;
+    }
+    void clear_total_processing_times() {
+        total_processing_times_.clear();
+        for (ProcessName n : {ProcessName::preprocessing, ProcessName::compute_covariances, ProcessName::registration, ProcessName::build_submap})
+            total_processing_times_[process_name(n)] = {};
+    }
+    void add_delta_time(ProcessName name, double dt) {
+        total_processing_times_[process_name(name)].push_back(dt);
+        current_processing_time_[process_name(name)] = dt;
+    }
+    /// a stage's exception becomes ResultType::error with "<stage>: <what>" (lidar_odometry.hpp:145-151 and its siblings)
+    template <class F>
+    bool run_stage(const char* stage, F&& f) {
+        try {
+            f();
+            return true;
+        } catch (const std::exception& e) {
+            error_message_ = std::string(stage) + ": " + e.what();
+            std::cerr << log_prefix_ << " " << error_message_ << std::endl;
+            return false;
+        }
+    }
+
+    /// lidar_odometry.hpp:508-522, lidar_inertial_odometry.hpp:646-660 — only when the factor, the incidence filter or an intensity
+    /// filter needs them
+    static void compute_covariances(const CommonParameters& params, const pointcloud_processing::PCProcessor& pc_processor,
+                                    PointCloudShared& preprocessed_pc, pointcloud_processing::ProcessingContext& processing_ctx) {
+        namespace reg = algorithms::registration;
+        const bool needs_covs = params.registration.factor.reg_type == reg::RegType::GICP ||
+                                params.registration.factor.rotation_constraint.enable ||
+                                params.scan.preprocess.angle_incidence_filter.enable;
+        const bool needs_gaussian = params.scan.intensity_gaussian.enable && preprocessed_pc.has_intensity();
+        const bool needs_local_mean_norm = params.scan.intensity_local_mean_norm.enable && preprocessed_pc.has_intensity();
+        if (!needs_covs && !needs_gaussian && !needs_local_mean_norm) return;
+        processing_ctx = pc_processor.prepare_context(preprocessed_pc);
+        pc_processor.compute_covariances(preprocessed_pc, processing_ctx);
+    }
+
+    std::deque<imu::IMUMeasurement> imu_buffer_;
+    mutable std::mutex imu_mutex_;  // guards imu_buffer_ (written by the IMU callback, read by the LiDAR callback)
+    std::string error_message_;
+    std::map<std::string, double> current_processing_time_;
+    std::map<std::string, std::vector<double>> total_processing_times_;
+
+private:
+    const char* log_prefix_;
+    const char* registration_stage_;
+    bool imu_enabled_ = false;
+    double imu_buffer_duration_sec_ = 0.0;
+};
+
+}  // namespace odometry
+
 // ------------------------------------------------------------------------------------------------ the odometry loop
 namespace lidar_odometry {
 using LidarOdometryParams = lidar_odometry::Parameters;
 
 /// pipeline/lidar_odometry.hpp:27-622 — what the reference's ROS 2 node calls once per scan
-class LiDAROdometryPipeline {
+class LiDAROdometryPipeline : public odometry::PipelineCommon {
 public:
     using Ptr = std::shared_ptr<LiDAROdometryPipeline>;
     using ConstPtr = std::shared_ptr<const LiDAROdometryPipeline>;
@@ -965,19 +1082,13 @@ public:
     };
 
     /// :41-52 — the IMU buffer must outlast the alignment window (the trimming keeps span <= buffer_duration_sec)
-    LiDAROdometryPipeline(const LidarOdometryParams& params) {
+    LiDAROdometryPipeline(const LidarOdometryParams& params) : PipelineCommon("[LiDAR Odometry]", "3. registration") {
         params_ = params;
-        if (params_.imu.enable && params_.imu.initial_alignment.enable) {
-            const double need = static_cast<double>(params_.imu.initial_alignment.required_duration_sec) + 0.2;
-            if (params_.imu.buffer_duration_sec < need) params_.imu.buffer_duration_sec = need;
-        }
+        adopt_imu_params(params_.imu);
         initialize();
     }
 
     auto get_device_queue() const { return queue_ptr_; }
-    const auto& get_error_message() const { return error_message_; }
-    const auto& get_current_processing_time() const { return current_processing_time_; }
-    const auto& get_total_processing_times() const { return total_processing_times_; }
     /// current / previous LiDAR pose in the (gravity-aligned) odom frame
     const auto& get_odom() const { return odom_; }
     const auto& get_prev_odom() const { return prev_odom_; }
@@ -992,25 +1103,6 @@ public:
     const auto& get_registration_result() const { return *reg_result_; }
     /// MI355X extension: the parameters as the constructor adjusted them (buffer_duration_sec, velocity_update.enable)
     const LidarOdometryParams& get_params() const { return params_; }
-
-    /// :85-106 — no-op with the IMU disabled; non-finite samples and stamps that do not increase are dropped; the buffer is cut
-    /// to buffer_duration_sec. May be called while process() runs.
-    void add_imu_measurement(const imu::IMUMeasurement& meas) {
-        if (!params_.imu.enable) return;
-        std::lock_guard<std::mutex> lock(imu_mutex_);
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(meas.accel[k]) || !std::isfinite(meas.gyro[k])) return;
-        if (!imu_buffer_.empty() && meas.timestamp <= imu_buffer_.back().timestamp) return;
-        const double latest_timestamp = meas.timestamp;
-        imu_buffer_.push_back(meas);
-        while (latest_timestamp - imu_buffer_.front().timestamp > params_.imu.buffer_duration_sec) imu_buffer_.pop_front();
-    }
-
-    /// :110-113 — a snapshot
-    std::deque<imu::IMUMeasurement> get_imu_buffer() const {
-        std::lock_guard<std::mutex> lock(imu_mutex_);
-        return imu_buffer_;
-    }
 
     /// :115-298
     ResultType process(const PointCloudShared::Ptr scan, double timestamp) {
@@ -1132,42 +1224,6 @@ public:
     }
 
 private:
-    enum class ProcessName { preprocessing = 0, compute_covariances, registration, build_submap };
-    static const char* process_name(ProcessName n) {  // :357-362
-        switch (n) {
-            case ProcessName::preprocessing: return "1. preprocessing";
-            case ProcessName::compute_covariances: return "2. compute covariances";
-            case ProcessName::registration: return "3. registration";
-            case ProcessName::build_submap: return "4. build submap";
-        }
-        return "";
-    }
-    void clear_current_processing_time() {
-        current_processing_time_.clear();
-        for (ProcessName n : {ProcessName::preprocessing, ProcessName::compute_covariances, ProcessName::registration, ProcessName::build_submap})
-            current_processing_time_[process_name(n)] = 0.0;
-    }
-    void clear_total_processing_times() {
-        total_processing_times_.clear();
-        for (ProcessName n : {ProcessName::preprocessing, ProcessName::compute_covariances, ProcessName::registration, ProcessName::build_submap})
-            total_processing_times_[process_name(n)] = {};
-    }
-    void add_delta_time(ProcessName name, double dt) {
-        total_processing_times_[process_name(name)].push_back(dt);
-        current_processing_time_[process_name(name)] = dt;
-    }
-    /// a stage's exception becomes ResultType::error with "<stage>: <what>" (:145-151 and its siblings)
-    template <class F>
-    bool run_stage(const char* stage, F&& f) {
-        try {
-            f();
-            return true;
-        } catch (const std::exception& e) {
-            error_message_ = std::string(stage) + ": " + e.what();
-            std::cerr << "[LiDAR Odometry] " << error_message_ << std::endl;
-            return false;
-        }
-    }
     bool is_imu_deskew_enabled() const { return params_.imu.enable && params_.imu.deskew.enable; }
 
     /// :387-474
@@ -1231,18 +1287,8 @@ private:
         pc_processor_->prefilter(*scan, *preprocessed_pc_);
     }
 
-    /// :508-522 — only when the factor, the incidence filter or an intensity filter needs them
-    void compute_covariances() {
-        namespace reg = algorithms::registration;
-        const bool needs_covs = params_.registration.factor.reg_type == reg::RegType::GICP ||
-                                params_.registration.factor.rotation_constraint.enable ||
-                                params_.scan.preprocess.angle_incidence_filter.enable;
-        const bool needs_gaussian = params_.scan.intensity_gaussian.enable && preprocessed_pc_->has_intensity();
-        const bool needs_local_mean_norm = params_.scan.intensity_local_mean_norm.enable && preprocessed_pc_->has_intensity();
-        if (!needs_covs && !needs_gaussian && !needs_local_mean_norm) return;
-        processing_ctx_ = pc_processor_->prepare_context(*preprocessed_pc_);
-        pc_processor_->compute_covariances(*preprocessed_pc_, processing_ctx_);
-    }
+    /// :508-522
+    void compute_covariances() { PipelineCommon::compute_covariances(params_, *pc_processor_, *preprocessed_pc_, processing_ctx_); }
 
     /// :526-542 — odom * (T_imu_to_lidar * T_imu_rel * T_imu_to_lidar^-1)
     Eigen::Isometry3f imu_motion_prediction() {
@@ -1325,18 +1371,410 @@ private:
     imu::IMUVelocityCorrector imu_velocity_corrector_;
     imu::IMUBias imu_bias_;  // params_.imu.bias, then what the initial alignment found
     imu::InitialAlignmentEstimator::Ptr alignment_estimator_ = nullptr;
-    std::deque<imu::IMUMeasurement> imu_buffer_;
-    mutable std::mutex imu_mutex_;            // guards imu_buffer_ (written by the IMU callback, read by the LiDAR callback)
     double last_imu_reset_timestamp_ = -1.0;  // LiDAR stamp of the last preintegration reset
     Eigen::Matrix3f imu_R_world_at_reset_ = Eigen::Matrix3f::Identity();
     Eigen::Vector3f imu_v_world_at_reset_ = Eigen::Vector3f::Zero();
     std::vector<imu::IMUMeasurement> imu_batch_;
     bool imu_window_complete_ = false;
-    std::string error_message_;
-    std::map<std::string, double> current_processing_time_;
-    std::map<std::string, std::vector<double>> total_processing_times_;
 };
 
 }  // namespace lidar_odometry
+
+// ------------------------------------------------------------------------------------------------ the LiDAR-inertial loop
+namespace lidar_inertial_odometry {
+
+/// pipeline/lidar_inertial_odometry_params.hpp:15-57 — the IMU is mandatory: the pipeline forces imu.enable
+struct Parameters : public odometry::CommonParameters {
+    struct LIO {
+        algorithms::lio::LIORegistrationParams registration;
+
+        struct PreintegrationReset {
+            float fd_velocity_sigma = 0.1f;    ///< [m/s] floor on the velocity block of the covariance at each IMU reset
+            float icp_rotation_sigma = 0.01f;  ///< [rad] the same for the rotation block
+        };
+        /// safeguards for the weakly observable bias states
+        struct BiasEstimation {
+            bool freeze_on_low_excitation = false;    ///< hold the biases while the window shows no excitation
+            float gyro_excitation_threshold = 0.03f;  ///< [rad/s] max |w - mean w| above which the gyro counts as excited
+            float accel_excitation_threshold = 0.3f;  ///< [m/s^2] the same for the specific force
+            float max_accel_bias = 0.0f;              ///< [m/s^2] clamp on the bias norm; <= 0 disables
+            float max_gyro_bias = 0.0f;               ///< [rad/s]
+        };
+        PreintegrationReset preintegration_reset;
+        BiasEstimation bias_estimation;
+    };
+
+    LIO lio;
+};
+
+/// pipeline/lidar_inertial_odometry.hpp:55-710 — what the reference's ROS 2 LIO node calls once per scan. The state x_ is the LiDAR
+/// pose, velocity and the IMU biases in the gravity-aligned odom frame; each frame predicts it from the IMU window, hands
+/// prediction and covariance to lio::LIORegistration and starts the next window from the posterior. The 15x15 arithmetic and
+/// the decisions are the C library's (sp_lio_predict_state_host, sp_lio_reset_covariance_host, sp_lio_bias_observable_host,
+/// sp_lio_clamp_bias_host); this class sequences them.
+class LidarInertialOdometryPipeline : public odometry::PipelineCommon {
+public:
+    using Ptr = std::shared_ptr<LidarInertialOdometryPipeline>;
+    using ConstPtr = std::shared_ptr<const LidarInertialOdometryPipeline>;
+
+    enum class ResultType : std::int8_t {
+        success = 0,
+        first_frame,
+        waiting_initial_alignment,
+        imu_only,
+        error = 100,
+        old_timestamp,
+        small_number_of_points,
+    };
+
+    /// :70-82
+    explicit LidarInertialOdometryPipeline(const Parameters& params)
+        : PipelineCommon("[LidarInertialOdometry]", "3. lio registration") {
+        params_ = params;
+        params_.imu.enable = true;
+        adopt_imu_params(params_.imu);
+        initialize();
+    }
+
+    auto get_device_queue() const { return queue_ptr_; }
+    /// current / previous LiDAR pose in the gravity-aligned odom frame
+    const auto& get_odom() const { return odom_; }
+    const auto& get_prev_odom() const { return prev_odom_; }
+    const auto& get_last_keyframe_pose() const { return submap_->get_last_keyframe_pose(); }
+    const auto& get_keyframe_poses() const { return submap_->get_keyframe_poses(); }
+    const PointCloudShared& get_preprocessed_point_cloud() const { return *preprocessed_pc_; }
+    const PointCloudShared& get_submap_point_cloud() const { return submap_->get_submap_point_cloud(); }
+    const PointCloudShared& get_last_keyframe_point_cloud() const { return submap_->get_last_keyframe_point_cloud(); }
+    const auto& get_registration_result() const { return *reg_result_; }
+    const imu::State& get_lio_state() const { return x_; }
+    /// MI355X extension: the parameters as the constructor adjusted them (imu.enable, buffer_duration_sec)
+    const Parameters& get_params() const { return params_; }
+    /// MI355X extension: the posterior covariance the next IMU window starts from (LiDAR error state, 15x15)
+    const Eigen::Matrix<float, 15, 15>& get_posterior_covariance() const { return P_post_; }
+
+    /// :131-278. A first stamp of 0 reads as "no frame yet" (last_frame_time_ > 0.0, as the reference): the frame after it is not
+    /// checked against it and keeps dt = -1.
+    ResultType process(const PointCloudShared::Ptr scan, double timestamp) {
+        error_message_.clear();
+        // initial roll / pitch from stationary IMU samples, once, before the first scan becomes the reference frame (:136-144)
+        if (is_first_frame_ && alignment_estimator_->enabled() && !alignment_estimator_->is_done()) {
+            const imu::IMUBias current_bias{x_.gyro_bias, x_.accel_bias};
+            const auto out = alignment_estimator_->try_align(timestamp, get_imu_buffer(), current_bias);
+            if (out.status != imu::InitialAlignmentEstimator::Status::success) {
+                error_message_ = std::string("initial_alignment: ") + out.error_message;
+                return ResultType::waiting_initial_alignment;
+            }
+            apply_initial_alignment(out);
+        }
+        if (last_frame_time_ > 0.0) {  // :146-154
+            const float dt = static_cast<float>(timestamp - last_frame_time_);
+            if (dt > 0.0f) {
+                dt_ = dt;
+            } else {
+                error_message_ = "old timestamp";
+                return ResultType::old_timestamp;
+            }
+        }
+        clear_current_processing_time();
+
+        double dt_preprocessing = 0.0;
+        if (!run_stage("preprocess", [&]() { time_utils::measure_execution([&]() { preprocess(scan); }, dt_preprocessing); }))
+            return ResultType::error;
+        {
+            double dt_covariance = 0.0;
+            if (!run_stage("compute_covariances", [&]() { time_utils::measure_execution([&]() { compute_covariances(); }, dt_covariance); }))
+                return ResultType::error;
+            add_delta_time(ProcessName::compute_covariances, dt_covariance);
+        }
+        {
+            double dt_refine_filter = 0.0;
+            if (!run_stage("refine_filter", [&]() { time_utils::measure_execution([&]() { refine_filter(); }, dt_refine_filter); }))
+                return ResultType::error;
+            dt_preprocessing += dt_refine_filter;
+            add_delta_time(ProcessName::preprocessing, dt_preprocessing);
+        }
+
+        const bool insufficient_points = preprocessed_pc_->size() <= params_.registration.min_num_points;
+        // the first frame founds the submap and cannot fall back on the IMU; rejected before the integrator advances (:198-205)
+        if (is_first_frame_ && insufficient_points) {
+            error_message_ = "point cloud size is too small";
+            return ResultType::small_number_of_points;
+        }
+
+        integrate_imu_window(timestamp);
+
+        if (insufficient_points) return process_imu_only(timestamp);
+
+        if (is_first_frame_) {  // :214-244 — anchored at odom_ (post-alignment), so later frames share its frame
+            if (!run_stage("build_submap (first frame)", [&]() { submap_->add_first_frame(*preprocessed_pc_, timestamp, odom_); }))
+                return ResultType::error;
+            is_first_frame_ = false;
+            last_frame_time_ = timestamp;
+            last_imu_reset_timestamp_ = timestamp;
+            x_.position = odom_.translation();
+            x_.rotation = sycl_points::detail::rotation_of(odom_);
+            x_.velocity = Eigen::Vector3f::Zero();
+            // (the biases: the parameters', the gyro's from the initial alignment when it ran)
+            reset_imu_preintegration();
+            return ResultType::first_frame;
+        }
+
+        {
+            double dt_registration = 0.0;
+            if (!run_stage("lio_registration", [&]() {
+                    *reg_result_ = time_utils::measure_execution([&]() { return register_frame(); }, dt_registration);
+                }))
+                return ResultType::error;
+            add_delta_time(ProcessName::registration, dt_registration);
+        }
+        last_imu_reset_timestamp_ = timestamp;
+
+        {
+            double dt_build_submap = 0.0;
+            if (!run_stage("submapping", [&]() {
+                    time_utils::measure_execution([&]() { submapping(*reg_result_, timestamp); }, dt_build_submap);
+                }))
+                return ResultType::error;
+            add_delta_time(ProcessName::build_submap, dt_build_submap);
+        }
+
+        prev_odom_ = odom_;
+        odom_ = reg_result_->T;
+        last_frame_time_ = timestamp;
+        return ResultType::success;
+    }
+
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+
+private:
+    static Eigen::Isometry3f state_to_pose(const imu::State& s) {  // :352-357
+        Eigen::Isometry3f T = Eigen::Isometry3f::Identity();
+        sycl_points::detail::set_rotation(T, s.rotation);
+        for (int i = 0; i < 3; ++i) T.matrix()(i, 3) = s.position[i];
+        return T;
+    }
+    static bool all_finite(const float* v, int n) {
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(v[i])) return false;
+        return true;
+    }
+
+    /// :371-393 (sp_lio_bias_observable_host) — on the window integrate_imu_window built
+    bool imu_bias_observable() const {
+        const auto& be = params_.lio.bias_estimation;
+        std::vector<float> gyro, accel;
+        gyro.reserve(3 * imu_batch_.size());
+        accel.reserve(3 * imu_batch_.size());
+        for (const imu::IMUMeasurement& m : imu_batch_)
+            for (int k = 0; k < 3; ++k) {
+                gyro.push_back(m.gyro[k]);
+                accel.push_back(m.accel[k]);
+            }
+        int observable = 0;
+        throw_on_error(sp_lio_bias_observable_host(gyro.data(), accel.data(), imu_batch_.size(), be.freeze_on_low_excitation ? 1 : 0,
+                                                   be.gyro_excitation_threshold, be.accel_excitation_threshold, &observable));
+        return observable != 0;
+    }
+
+    /// :402-429 (sp_lio_reset_covariance_host) — the next window starts at x_ with P_post_ plus the two floors, in the IMU's
+    /// error state
+    void reset_imu_preintegration() {
+        const TransformMatrix T_i2l = params_.imu.T_imu_to_lidar.matrix();
+        Eigen::Matrix<float, 15, 15> P_initial_imu;
+        Eigen::Matrix3f R_world_imu;
+        throw_on_error(sp_lio_reset_covariance_host(P_post_.data(), params_.lio.preintegration_reset.fd_velocity_sigma,
+                                                    params_.lio.preintegration_reset.icp_rotation_sigma, T_i2l.data(), x_.rotation.data(),
+                                                    P_initial_imu.data(), R_world_imu.data()));
+        imu_preintegration_->reset(imu::IMUBias{x_.gyro_bias, x_.accel_bias}, P_initial_imu, R_world_imu);
+        imu_R_world_at_reset_ = R_world_imu;
+        imu_v_world_at_reset_ = x_.velocity;
+    }
+
+    /// :432-459 (sp_lio_predict_state_host)
+    imu::State predict_state() const {
+        const imu::IMUBias current_bias{x_.gyro_bias, x_.accel_bias};
+        const TransformMatrix T_imu_rel =
+            imu_preintegration_->predict_relative_transform(imu_R_world_at_reset_, imu_v_world_at_reset_, current_bias);
+        const imu::PreintegrationResult c = imu_preintegration_->get_corrected(current_bias);
+        const TransformMatrix T_i2l = params_.imu.T_imu_to_lidar.matrix();
+        float predicted[21];
+        throw_on_error(sp_lio_predict_state_host(imu::detail::PackedState(x_).v, T_i2l.data(), T_imu_rel.data(), c.Delta_v.data(),
+                                                 static_cast<float>(c.dt_total), params_.imu.preintegration.gravity.data(), predicted));
+        return imu::detail::unpack_state(predicted);
+    }
+
+    /// :461-470 — the IMU window [last reset, timestamp]
+    void integrate_imu_window(double timestamp) {
+        imu_batch_.clear();
+        {
+            std::lock_guard<std::mutex> lock(imu_mutex_);
+            imu_batch_.reserve(imu_buffer_.size());
+            imu::build_measurement_window(imu_buffer_, last_imu_reset_timestamp_, timestamp, imu_batch_);
+        }
+        imu_preintegration_->integrate_batch(imu_batch_);
+    }
+
+    /// :472-509 — no LiDAR update for this frame: the IMU prediction is the posterior
+    ResultType process_imu_only(double timestamp) {
+        const imu::State predicted_state = predict_state();
+        const Eigen::Matrix<float, 15, 15> predicted_covariance = algorithms::lio::transform_covariance_imu_to_lidar(
+            imu_preintegration_->get_raw().covariance, params_.imu.T_imu_to_lidar, predicted_state.rotation);
+        if (!all_finite(predicted_state.position.data(), 3) || !all_finite(predicted_state.rotation.data(), 9) ||
+            !all_finite(predicted_state.velocity.data(), 3) || !all_finite(predicted_covariance.data(), 225)) {
+            error_message_ = "imu-only propagation produced non-finite state or covariance";
+            return ResultType::error;
+        }
+        prev_odom_ = odom_;
+        x_ = predicted_state;
+        P_post_ = predicted_covariance;
+        odom_ = state_to_pose(x_);
+
+        // the previous ICP result must not stay visible as the latest one
+        reg_result_->T = odom_;
+        reg_result_->converged = true;
+        reg_result_->iterations = 0;
+        reg_result_->H.setZero();
+        reg_result_->b.setZero();
+        reg_result_->error = 0.0f;
+        reg_result_->H_raw.setZero();
+        reg_result_->b_raw.setZero();
+        reg_result_->error_raw = 0.0f;
+        reg_result_->inlier = 0;
+
+        last_frame_time_ = timestamp;
+        last_imu_reset_timestamp_ = timestamp;
+        reset_imu_preintegration();
+
+        error_message_ = "point cloud size is too small; propagated with IMU only";
+        return ResultType::imu_only;
+    }
+
+    /// :512-537 — prediction, covariance and the sampled source go to lio::LIORegistration; its posterior starts the next window
+    algorithms::registration::RegistrationResult register_frame() {
+        const imu::State predicted_state = predict_state();
+        const Eigen::Matrix<float, 15, 15> predicted_covariance = algorithms::lio::transform_covariance_imu_to_lidar(
+            imu_preintegration_->get_raw().covariance, params_.imu.T_imu_to_lidar, predicted_state.rotation);
+
+        const auto& sampling = params_.registration_sampling;
+        PointCloudShared::ConstPtr source = preprocessed_pc_;
+        if (sampling.enable && preprocessed_pc_->size() > sampling.num) {
+            pc_processor_->random_sampling(*preprocessed_pc_, *registration_input_pc_, sampling.num);
+            source = registration_input_pc_;
+        }
+        registration_source_pc_ = source;
+
+        auto result = lio_registration_->align(*source, submap_->get_submap_point_cloud(), submap_->get_submap_kdtree(), predicted_state,
+                                               predicted_covariance, P_post_, imu_bias_observable(), dt_, odom_.matrix());
+        P_post_ = result.posterior_covariance;
+        x_ = result.state;
+        throw_on_error(sp_lio_clamp_bias_host(x_.accel_bias.data(), params_.lio.bias_estimation.max_accel_bias));
+        throw_on_error(sp_lio_clamp_bias_host(x_.gyro_bias.data(), params_.lio.bias_estimation.max_gyro_bias));
+        reset_imu_preintegration();
+        return result.registration_result;
+    }
+
+    /// :542-601
+    void initialize() {
+        queue_ptr_ = std::make_shared<sycl_utils::DeviceQueue>(0);  // (params_.device is not consulted)
+        preprocessed_pc_ = std::make_shared<PointCloudShared>(*queue_ptr_);
+        registration_input_pc_ = std::make_shared<PointCloudShared>(*queue_ptr_);
+        icp_weights_ = std::make_shared<shared_vector<float>>(*queue_ptr_);
+        odom_ = params_.pose.initial;
+        prev_odom_ = params_.pose.initial;
+        pc_processor_ = std::make_shared<pointcloud_processing::PCProcessor>(*queue_ptr_, params_.scan, params_.covariance_estimation,
+                                                                             params_.imu);
+        submap_ = std::make_shared<submapping::Submap>(*queue_ptr_, params_);
+        lio_registration_ =
+            std::make_shared<algorithms::lio::LIORegistration>(*queue_ptr_, params_.registration.factor, params_.lio.registration);
+        reg_result_ = std::make_shared<algorithms::registration::RegistrationResult>();
+        {  // the first frame's reset_imu_preintegration() overwrites this with the post-alignment value before anything is integrated
+            imu_preintegration_ = std::make_shared<imu::IMUPreintegration>(params_.imu.preintegration);
+            const Eigen::Matrix3f R_world_imu =
+                sycl_points::detail::rotation_of(params_.pose.initial) * sycl_points::detail::rotation_of(params_.imu.T_imu_to_lidar);
+            imu_preintegration_->reset(params_.imu.bias, Eigen::Matrix<float, 15, 15>::Zero(), R_world_imu);
+            imu_R_world_at_reset_ = R_world_imu;
+            imu_v_world_at_reset_ = Eigen::Vector3f::Zero();
+        }
+        alignment_estimator_ = std::make_shared<imu::InitialAlignmentEstimator>(
+            params_.imu.initial_alignment, params_.imu.preintegration.gravity, params_.imu.T_imu_to_lidar);
+        // preprocess() deskews with the state's biases before the first frame sets the rest of the state
+        x_.accel_bias = params_.imu.bias.accel_bias;
+        x_.gyro_bias = params_.imu.bias.gyro_bias;
+        clear_total_processing_times();
+    }
+
+    /// :619-627 — the gravity-corrected rotation with the user's yaw layered on the left; the gyro bias the alignment found. The
+    /// integrator is reset by the first-frame branch.
+    void apply_initial_alignment(const imu::InitialAlignmentEstimator::Output& out) {
+        const float yaw_user = imu::detail::yaw_from_rotation(sycl_points::detail::rotation_of(params_.pose.initial));
+        const Eigen::Matrix3f R_odom_lidar =
+            Eigen::AngleAxisf(yaw_user, Eigen::Vector3f(0.0f, 0.0f, 1.0f)).toRotationMatrix() * out.R_gravity_lidar;
+        x_.rotation = R_odom_lidar;
+        x_.gyro_bias = out.gyro_bias;
+        sycl_points::detail::set_rotation(odom_, R_odom_lidar);
+        sycl_points::detail::set_rotation(prev_odom_, R_odom_lidar);
+    }
+
+    /// :632-640 — the IMU deskew gets the STATE's bias and velocity, not the parameters'
+    void preprocess(const PointCloudShared::Ptr scan) {
+        if (params_.imu.deskew.enable) {
+            auto imu_buf = get_imu_buffer();
+            const imu::IMUBias current_bias{x_.gyro_bias, x_.accel_bias};
+            pc_processor_->deskew_with_imu(*scan, *scan, imu_buf, odom_, current_bias, x_.velocity);
+        }
+        pc_processor_->prefilter(*scan, *preprocessed_pc_);
+    }
+
+    /// :642-660
+    void refine_filter() { pc_processor_->refine_filter(*preprocessed_pc_, processing_ctx_); }
+    void compute_covariances() { PipelineCommon::compute_covariances(params_, *pc_processor_, *preprocessed_pc_, processing_ctx_); }
+
+    /// :665-693 — the cloud register_frame() aligned goes into the map; robust ICP weights only when it is larger than the
+    /// submap's sample
+    bool submapping(const algorithms::registration::RegistrationResult& reg_result, double timestamp) {
+        PointCloudShared::ConstPtr reg_pc_ptr = registration_source_pc_ != nullptr ? registration_source_pc_ : registration_input_pc_;
+        bool computed_icp_weights = false;
+        if (reg_pc_ptr->size() > params_.submap.point_random_sampling_num) {
+            const auto& robust = params_.lio.registration.robust;
+            const float robust_scale = robust.auto_scale ? robust.min_scale : params_.registration.factor.robust.default_scale;
+            lio_registration_->registration_backend()->compute_icp_robust_weights(
+                *reg_pc_ptr, submap_->get_submap_point_cloud(), submap_->get_submap_kdtree(), reg_result.T.matrix(), robust_scale,
+                *icp_weights_);
+            computed_icp_weights = true;
+        }
+        const float inlier_ratio =
+            reg_pc_ptr->size() > 0 ? static_cast<float>(reg_result.inlier) / static_cast<float>(reg_pc_ptr->size()) : 0.0f;
+        if (computed_icp_weights) return submap_->add_frame(*reg_pc_ptr, reg_result, inlier_ratio, timestamp, icp_weights_);
+        return submap_->add_frame(*reg_pc_ptr, reg_result, inlier_ratio, timestamp);
+    }
+
+    sycl_utils::DeviceQueue::Ptr queue_ptr_ = nullptr;
+    PointCloudShared::Ptr preprocessed_pc_ = nullptr;         // sensor frame
+    PointCloudShared::Ptr registration_input_pc_ = nullptr;   // the random sample register_frame() draws
+    PointCloudShared::ConstPtr registration_source_pc_ = nullptr;  // what register_frame() aligned: the sample, or preprocessed_pc_
+    bool is_first_frame_ = true;
+    imu::InitialAlignmentEstimator::Ptr alignment_estimator_ = nullptr;
+    pointcloud_processing::ProcessingContext processing_ctx_;
+    shared_vector_ptr<float> icp_weights_ = nullptr;
+    pointcloud_processing::PCProcessor::Ptr pc_processor_ = nullptr;
+    algorithms::lio::LIORegistration::Ptr lio_registration_ = nullptr;
+    algorithms::registration::RegistrationResult::Ptr reg_result_ = nullptr;
+    Eigen::Isometry3f prev_odom_;  // T_odom_to_lidar; odom_ == state_to_pose(x_) after each frame
+    Eigen::Isometry3f odom_;
+    submapping::Submap::Ptr submap_ = nullptr;
+    double last_frame_time_ = -1.0;           // [s]
+    double last_imu_reset_timestamp_ = -1.0;  // LiDAR stamp of the last preintegration reset
+    float dt_ = -1.0f;                        // [s]
+    Parameters params_;
+    imu::State x_;
+    Eigen::Matrix<float, 15, 15> P_post_ = Eigen::Matrix<float, 15, 15>::Zero();  // LiDAR error state
+    imu::IMUPreintegration::Ptr imu_preintegration_ = nullptr;
+    // the linearisation point of predict_relative_transform(): frozen at the reset, whatever happens to x_ afterwards
+    Eigen::Matrix3f imu_R_world_at_reset_ = Eigen::Matrix3f::Identity();
+    Eigen::Vector3f imu_v_world_at_reset_ = Eigen::Vector3f::Zero();
+    std::vector<imu::IMUMeasurement> imu_batch_;
+};
+
+}  // namespace lidar_inertial_odometry
 }  // namespace pipeline
 }  // namespace sycl_points

@@ -1191,6 +1191,28 @@ int sp_lio_stepper_linearized(sp_lio_stepper* stepper, const sp_linearized* lin_
 int sp_lio_stepper_trial(sp_lio_stepper* stepper, float error, uint32_t inlier);
 int sp_lio_stepper_result(const sp_lio_stepper* stepper, sp_lio_result* out);
 
+/* ---- the per-frame LiDAR-inertial odometry loop (pipeline/lidar_inertial_odometry.hpp = L): what LidarInertialOdometryPipeline
+ * computes and decides between its stages. HOST memory only, no device is touched, no stream; the conventions above. */
+/* imu_bias_observable (L:371-393) on the n samples of the IMU window, gyro and accel as n x 3. *observable_out = 1 when
+ * freeze_on_low_excitation == 0 (nothing is read); else 0 for n < 2; else 1 when max_i |gyro_i - mean gyro| > the gyro threshold
+ * or max_i |accel_i - mean accel| > the accel threshold (the norms of the full difference vectors, strict >), 0 otherwise. The
+ * means are float32 sums in sample order divided by (float)n. */
+int sp_lio_bias_observable_host(const float* gyro_host, const float* accel_host, size_t n, int freeze_on_low_excitation,
+                                float gyro_excitation_threshold, float accel_excitation_threshold, int* observable_out);
+/* clamp_bias_norm (L:396-400), in place: nothing for max_norm <= 0 or |bias| <= max_norm, else bias *= max_norm / |bias|. */
+int sp_lio_clamp_bias_host(float* bias3, float max_norm);
+/* predict_state (L:432-459) from what the integrator reports for the current bias: T_imu_rel16 = predict_relative_transform,
+ * Delta_v3 and dt_total = get_corrected. T_pred = pose(x) * (T_imu_to_lidar * T_imu_rel * T_imu_to_lidar^-1) gives position and
+ * rotation; velocity = v + gravity * dt_total + (R * R_imu_to_lidar) * Delta_v; both biases are copied. */
+int sp_lio_predict_state_host(const float* x21, const float* T_imu_to_lidar16, const float* T_imu_rel16, const float* Delta_v3,
+                              float dt_total, const float* gravity3, float* x_pred_out21);
+/* the covariance and rotation reset_imu_preintegration (L:402-426) hands to the integrator: P_post + fd_velocity_sigma^2 I on the
+ * velocity block + icp_rotation_sigma^2 I on the rotation block, then sp_lio_transform_covariance_host(..., lidar_to_imu = 1)
+ * (the same code); R_world_imu = R_world_lidar * R_imu_to_lidar, column-major. P_initial_imu225_out must not be P_post225. */
+int sp_lio_reset_covariance_host(const float* P_post225, float fd_velocity_sigma, float icp_rotation_sigma,
+                                 const float* T_imu_to_lidar16, const float* R_world_lidar9, float* P_initial_imu225_out,
+                                 float* R_world_imu9_out);
+
 /* ----------------------------------------------------------------------------------------- multi-GPU */
 
 /* One process per GPU; the source cloud is sharded over the ranks, the target (points, covariances, grid, prepared rows)

@@ -366,6 +366,10 @@ SIGNATURES = {
     "sp_lio_stepper_linearized": (_i, [_vp, C.POINTER(Linearized)]),
     "sp_lio_stepper_trial": (_i, [_vp, _f, C.c_uint32]),
     "sp_lio_stepper_result": (_i, [_vp, C.POINTER(LioResult)]),
+    "sp_lio_bias_observable_host": (_i, [_vp, _vp, _sz, _i, _f, _f, C.POINTER(_i)]),
+    "sp_lio_clamp_bias_host": (_i, [_vp, _f]),
+    "sp_lio_predict_state_host": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "sp_lio_reset_covariance_host": (_i, [_vp, _f, _f, _vp, _vp, _vp, _vp]),
     "sp_vhm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
     "sp_vhm_destroy": (None, [_vp]),
     "sp_vhm_set": (_i, [_vp, _i, _f]),

@@ -2685,6 +2685,44 @@ class LIORegistration:
         return out
 
 
+# ---- the per-frame loop of pipeline/lidar_inertial_odometry.hpp: what LidarInertialOdometryPipeline computes between its stages
+def lio_bias_observable(gyro, accel, freeze_on_low_excitation=False, gyro_excitation_threshold=0.03, accel_excitation_threshold=0.3):
+    """imu_bias_observable (lidar_inertial_odometry.hpp:371-393) on the window's samples, gyro and accel as (n, 3)"""
+    g = np.ascontiguousarray(np.asarray(gyro, np.float32).reshape(-1, 3))
+    a = np.ascontiguousarray(np.asarray(accel, np.float32).reshape(-1, 3))
+    if g.shape != a.shape:
+        raise SpError(1, f"gyro has {g.shape[0]} samples, accel {a.shape[0]}")
+    out = C.c_int(-1)
+    check(_lib.lib().sp_lio_bias_observable_host(_hp(g), _hp(a), g.shape[0], int(bool(freeze_on_low_excitation)),
+                                                 C.c_float(gyro_excitation_threshold), C.c_float(accel_excitation_threshold),
+                                                 C.byref(out)))
+    return bool(out.value)
+
+
+def lio_clamp_bias(bias, max_norm):
+    """clamp_bias_norm (lidar_inertial_odometry.hpp:396-400) -> the clamped copy"""
+    b = _f32(bias, 3).copy()
+    check(_lib.lib().sp_lio_clamp_bias_host(_hp(b), C.c_float(max_norm)))
+    return b
+
+
+def lio_predict_state(state, T_imu_to_lidar, T_imu_rel, Delta_v, dt_total, gravity=(0.0, 0.0, -9.80665)):
+    """predict_state (lidar_inertial_odometry.hpp:432-459) from the integrator's predict_relative_transform and get_corrected"""
+    out = np.zeros(21, np.float32)
+    check(_lib.lib().sp_lio_predict_state_host(_hp(state.pack()), _hp(_T16(T_imu_to_lidar).reshape(-1)), _hp(_T16(T_imu_rel).reshape(-1)),
+                                               _hp(_f32(Delta_v, 3)), C.c_float(dt_total), _hp(_f32(gravity, 3)), _hp(out)))
+    return IMUState.unpack(out)
+
+
+def lio_reset_covariance(P_post, fd_velocity_sigma, icp_rotation_sigma, T_imu_to_lidar, R_world_lidar):
+    """what reset_imu_preintegration (lidar_inertial_odometry.hpp:402-426) hands to the integrator -> (P_initial_imu, R_world_imu)"""
+    P, R = np.zeros(225, np.float32), np.zeros(9, np.float32)
+    check(_lib.lib().sp_lio_reset_covariance_host(_hp(_cm15(P_post)), C.c_float(fd_velocity_sigma), C.c_float(icp_rotation_sigma),
+                                                  _hp(_T16(T_imu_to_lidar).reshape(-1)),
+                                                  _hp(_f32(np.asarray(R_world_lidar, np.float32).T, 9)), _hp(P), _hp(R)))
+    return P.reshape(15, 15).T.copy(), R.reshape(3, 3).T.copy()
+
+
 # ------------------------------------------------------------------ sensor_msgs/PointCloud2 (ros2/convert.hpp, ros2/enhanced_reflectivity.hpp)
 def _pc2_type(t):
     return _lib.PC2_TYPE[t] if isinstance(t, str) else int(t)

@@ -1,7 +1,9 @@
 // Host numerics and control flow of the tightly coupled LiDAR-inertial alignment: the IMU prior factor (imu_factor.hpp = A), the
 // 15x15 algebra of lio_registration.hpp (= B) and LIORegistration::align (B:396-648) as a state machine in the shape of
 // sp_opt_stepper_*: the caller linearises and evaluates trials with the kernels Registration already has, everything else is
-// decided here. Plain host arithmetic (the reference runs all of it on the host with Eigen); no kernel is in this file.
+// decided here; and what the per-frame loop of pipeline/lidar_inertial_odometry.hpp (= L) computes between its stages (the bias
+// observability test, the bias clamp, the state prediction, the covariance handed to the next IMU window).
+// Plain host arithmetic (the reference runs all of it on the host with Eigen); no kernel is in this file.
 // 15x15 matrices are column-major, a state is p3 | R9 column-major | v3 | b_a3 | b_g3.
 #include <cmath>
 #include <cstdio>
@@ -259,6 +261,24 @@ void fill_jacobian(const float Brr[3][3], const float Bpr[3][3], float* J) {
             at(J, kPos + i, kRot + j) = Bpr[i][j];
         }
 }
+// J P J^T (B:340-345) or J^-1 P J^-T (B:366-381); P_out is not P
+void transform_covariance(const float* P, const float* T16, const float* R9, bool lidar_to_imu, float* P_out) {
+    float Brr[3][3], Bpr[3][3], J[225], JP[225];
+    extrinsic_blocks(T16, R9, lidar_to_imu, Brr, Bpr);
+    fill_jacobian(Brr, Bpr, J);
+    for (int i = 0; i < kN; ++i)
+        for (int j = 0; j < kN; ++j) {
+            float s = 0.0f;
+            for (int k = 0; k < kN; ++k) s += J[k * kN + i] * P[j * kN + k];
+            JP[j * kN + i] = s;
+        }
+    for (int i = 0; i < kN; ++i)
+        for (int j = 0; j < kN; ++j) {
+            float s = 0.0f;
+            for (int k = 0; k < kN; ++k) s += JP[k * kN + i] * J[k * kN + j];
+            P_out[j * kN + i] = s;
+        }
+}
 
 }  // namespace
 }  // namespace sp
@@ -423,21 +443,103 @@ extern "C" int sp_lio_imu_to_lidar_jacobian_host(const float* T_imu_to_lidar16, 
 extern "C" int sp_lio_transform_covariance_host(const float* P225, const float* T_imu_to_lidar16, const float* R_world_lidar9,
                                                 int lidar_to_imu, float* P_out225) {
     if (!P225 || !T_imu_to_lidar16 || !R_world_lidar9 || !P_out225 || P225 == P_out225) return SP_ERR_INVALID_ARGUMENT;
-    float Brr[3][3], Bpr[3][3], J[225], JP[225];
-    sp::extrinsic_blocks(T_imu_to_lidar16, R_world_lidar9, lidar_to_imu != 0, Brr, Bpr);
-    sp::fill_jacobian(Brr, Bpr, J);
-    for (int i = 0; i < 15; ++i)
-        for (int j = 0; j < 15; ++j) {
-            float s = 0.0f;
-            for (int k = 0; k < 15; ++k) s += J[k * 15 + i] * P225[j * 15 + k];
-            JP[j * 15 + i] = s;
+    sp::transform_covariance(P225, T_imu_to_lidar16, R_world_lidar9, lidar_to_imu != 0, P_out225);
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the per-frame LIO loop
+// What LidarInertialOdometryPipeline (pipeline/lidar_inertial_odometry.hpp = L) computes and decides between its stages.
+
+extern "C" int sp_lio_bias_observable_host(const float* gyro_host, const float* accel_host, size_t n, int freeze_on_low_excitation,
+                                           float gyro_excitation_threshold, float accel_excitation_threshold, int* observable_out) {
+    if (!observable_out) return SP_ERR_INVALID_ARGUMENT;
+    if (!freeze_on_low_excitation) { *observable_out = 1; return SP_OK; }  // L:373
+    if (n < 2) { *observable_out = 0; return SP_OK; }                       // L:374
+    if (!gyro_host || !accel_host) return SP_ERR_INVALID_ARGUMENT;
+    float gyro_mean[3] = {0.0f, 0.0f, 0.0f}, accel_mean[3] = {0.0f, 0.0f, 0.0f};
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            gyro_mean[k] += gyro_host[3 * i + k];
+            accel_mean[k] += accel_host[3 * i + k];
         }
-    for (int i = 0; i < 15; ++i)
-        for (int j = 0; j < 15; ++j) {
-            float s = 0.0f;
-            for (int k = 0; k < 15; ++k) s += JP[k * 15 + i] * J[k * 15 + j];
-            P_out225[j * 15 + i] = s;
+    const float count = (float)n;
+    for (int k = 0; k < 3; ++k) {
+        gyro_mean[k] /= count;
+        accel_mean[k] /= count;
+    }
+    float gyro_dev = 0.0f, accel_dev = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        float dg[3], da[3];
+        for (int k = 0; k < 3; ++k) {
+            dg[k] = gyro_host[3 * i + k] - gyro_mean[k];
+            da[k] = accel_host[3 * i + k] - accel_mean[k];
         }
+        gyro_dev = fmaxf(gyro_dev, sqrtf(sp::dot_n(dg, dg, 3)));
+        accel_dev = fmaxf(accel_dev, sqrtf(sp::dot_n(da, da, 3)));
+    }
+    *observable_out = (gyro_dev > gyro_excitation_threshold || accel_dev > accel_excitation_threshold) ? 1 : 0;
+    return SP_OK;
+}
+
+extern "C" int sp_lio_clamp_bias_host(float* bias3, float max_norm) {
+    if (!bias3) return SP_ERR_INVALID_ARGUMENT;
+    if (max_norm <= 0.0f) return SP_OK;
+    const float norm = sqrtf(sp::dot_n(bias3, bias3, 3));
+    if (norm > max_norm) {
+        const float scale = max_norm / norm;
+        for (int k = 0; k < 3; ++k) bias3[k] *= scale;
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_lio_predict_state_host(const float* x21, const float* T_imu_to_lidar16, const float* T_imu_rel16,
+                                         const float* Delta_v3, float dt_total, const float* gravity3, float* x_pred_out21) {
+    if (!x21 || !T_imu_to_lidar16 || !T_imu_rel16 || !Delta_v3 || !gravity3 || !x_pred_out21) return SP_ERR_INVALID_ARGUMENT;
+    using namespace sp;
+    const LioState x = load_state(x21);
+    const Rigid T_i2l = load_rigid_colmajor(T_imu_to_lidar16);
+    // T_lidar_rel = T_i2l * T_imu_rel * T_i2l^-1, T_pred = pose(x) * T_lidar_rel (L:443-445)
+    const Rigid T_lidar_rel = rigid_mul(rigid_mul(T_i2l, load_rigid_colmajor(T_imu_rel16)), rigid_inverse(T_i2l));
+    Rigid pose;
+    std::memcpy(pose.R, x.R, sizeof(pose.R));
+    std::memcpy(pose.t, x.p, sizeof(pose.t));
+    const Rigid T_pred = rigid_mul(pose, T_lidar_rel);
+    LioState pred = x;  // the biases are copied (L:456-457)
+    std::memcpy(pred.R, T_pred.R, sizeof(pred.R));
+    std::memcpy(pred.p, T_pred.t, sizeof(pred.p));
+    float R_world_imu[3][3];
+    mul33(x.R, T_i2l.R, R_world_imu);
+    for (int i = 0; i < 3; ++i) {  // v + g dt + R_world_imu Delta_v (L:455)
+        float s = 0.0f;
+        for (int k = 0; k < 3; ++k) s += R_world_imu[i][k] * Delta_v3[k];
+        pred.v[i] = (x.v[i] + gravity3[i] * dt_total) + s;
+    }
+    store_state(pred, x_pred_out21);
+    return SP_OK;
+}
+
+extern "C" int sp_lio_reset_covariance_host(const float* P_post225, float fd_velocity_sigma, float icp_rotation_sigma,
+                                            const float* T_imu_to_lidar16, const float* R_world_lidar9, float* P_initial_imu225_out,
+                                            float* R_world_imu9_out) {
+    if (!P_post225 || !T_imu_to_lidar16 || !R_world_lidar9 || !P_initial_imu225_out || !R_world_imu9_out ||
+        P_post225 == P_initial_imu225_out)
+        return SP_ERR_INVALID_ARGUMENT;
+    using namespace sp;
+    float P_initial[225];
+    std::memcpy(P_initial, P_post225, sizeof(P_initial));
+    const float sv2 = fd_velocity_sigma * fd_velocity_sigma, sr2 = icp_rotation_sigma * icp_rotation_sigma;
+    for (int i = 0; i < 3; ++i) {  // the floors (L:412-417)
+        at(P_initial, kVel + i, kVel + i) += sv2;
+        at(P_initial, kRot + i, kRot + i) += sr2;
+    }
+    transform_covariance(P_initial, T_imu_to_lidar16, R_world_lidar9, true, P_initial_imu225_out);  // L:423-424
+    const Rigid T_i2l = load_rigid_colmajor(T_imu_to_lidar16);
+    float Rwl[3][3], Rwi[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rwl[i][j] = R_world_lidar9[j * 3 + i];
+    mul33(Rwl, T_i2l.R, Rwi);  // L:404
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R_world_imu9_out[j * 3 + i] = Rwi[i][j];
     return SP_OK;
 }
 
