@@ -412,6 +412,8 @@ INTERNAL_SIGNATURES = {
     "sp_internal_bvh_option": (_i, [_vp, _i, _i]),
     "sp_internal_grid_small_build": (_i, [_i]),
     "sp_internal_align_searched_log": (_vp, [_vp, _vp]),
+    "sp_internal_source_tile_floats": (_sz, [_vp]),
+    "sp_internal_source_tiles_copy": (_i, [_vp, _vp, _sz, _i, _vp]),
     "sp_internal_radix_sort_workspace_bytes": (_sz, [_sz]),
     "sp_internal_radix_sort_u32": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]),
     "sp_internal_radix_sort_u32_ex": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_uint, C.c_uint, _i, _vp, _sz, _vp, _vp]),

@@ -482,24 +482,24 @@ __global__ __launch_bounds__(kBlock) void query_cell_kernel(const float4* __rest
 __global__ __launch_bounds__(kBlock) void prepare_source_kernel(const float4* __restrict__ pts,
                                                                 const float4* __restrict__ covs,
                                                                 unsigned* __restrict__ order, bool identity, unsigned n,
-                                                                unsigned stride, float* __restrict__ out_pts,
-                                                                float* __restrict__ out_covp) {
-    // Output as planes (x | y | z and xx | xy | xz | yy | yz | zz, `stride` floats apart): the per-iteration kernel is
-    // bound by the bytes it streams, and the planes carry 36 bytes per point where float4 rows carry 48.
+                                                                float* __restrict__ tiles) {
+    // Output in wave tiles (registration_device.h, FusedParams): nine words per point, 36 bytes where float4 rows carry
+    // 48, and each of the nine stores of a wave is one 256-byte run of its tile.
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const unsigned src = identity ? i : order[i];
     if (identity) order[i] = i;  // (the source is used as it lies: the permutation is written here instead of by a launch of its own)
     const float4 p = pts[src];
-    out_pts[i] = p.x; out_pts[stride + i] = p.y; out_pts[2 * (size_t)stride + i] = p.z;
-    if (!covs) return;  // point-to-distribution: the covariance planes are never read
+    float* const w = tiles + ((size_t)(i / kWave) * kSrcTileWords + (i % kWave));
+    w[0] = p.x; w[kWave] = p.y; w[2 * kWave] = p.z;
+    if (!covs) return;  // point-to-distribution: the covariance sub-planes are never read
     const Mat3 P = plane_regularize(load_cov(covs + 4 * (size_t)src));
-    out_covp[i] = P.m[0][0];
-    out_covp[stride + i] = (P.m[0][1] + P.m[1][0]) * 0.5f;
-    out_covp[2 * (size_t)stride + i] = (P.m[0][2] + P.m[2][0]) * 0.5f;
-    out_covp[3 * (size_t)stride + i] = P.m[1][1];
-    out_covp[4 * (size_t)stride + i] = (P.m[1][2] + P.m[2][1]) * 0.5f;
-    out_covp[5 * (size_t)stride + i] = P.m[2][2];
+    w[3 * kWave] = P.m[0][0];
+    w[4 * kWave] = (P.m[0][1] + P.m[1][0]) * 0.5f;
+    w[5 * kWave] = (P.m[0][2] + P.m[2][0]) * 0.5f;
+    w[6 * kWave] = P.m[1][1];
+    w[7 * kWave] = (P.m[1][2] + P.m[2][1]) * 0.5f;
+    w[8 * kWave] = P.m[2][2];
 }
 
 
@@ -1366,7 +1366,7 @@ extern "C" int sp_gicp_target_has_certificates(const sp_gicp_target* t) { return
 
 extern "C" void sp_gicp_source_destroy(sp_gicp_source* s) {
     if (!s) return;
-    (void)hipFree(s->pts); (void)hipFree(s->covp); (void)hipFree(s->perm); (void)hipFree(s->ccache); (void)hipFree(s->ccache2); (void)hipFree(s->qcert); (void)hipFree(s->qcert2); (void)hipFree(s->opt_rows);
+    (void)hipFree(s->tiles); (void)hipFree(s->perm); (void)hipFree(s->ccache); (void)hipFree(s->ccache2); (void)hipFree(s->qcert); (void)hipFree(s->qcert2); (void)hipFree(s->opt_rows);
     (void)hipFree(s->keys_in); (void)hipFree(s->keys_out); (void)hipFree(s->vals_in); (void)hipFree(s->sort_tmp);
     delete s;
 }
@@ -1379,8 +1379,7 @@ extern "C" int sp_gicp_source_create(size_t n_max, sp_gicp_source** out) {
     s->n_max = n_max;
     const size_t n = n_max ? n_max : 1;
     s->sort_tmp_bytes = radix_sort_u32_workspace_bytes(n);  // radix_sort.hip
-    hipError_t e = hipMalloc(&s->pts, (n + 64) * sizeof(float4));  // planes, each padded to a multiple of 64 floats
-    if (e == hipSuccess) e = hipMalloc(&s->covp, (n + 64) * 2 * sizeof(float4));
+    hipError_t e = hipMalloc(&s->tiles, src_tile_words(n) * sizeof(float));  // whole wave tiles
     if (e == hipSuccess) e = hipMalloc(&s->perm, n * 4);
     if (e == hipSuccess) e = hipMalloc(&s->ccache, n * 3 * sizeof(float4));
     if (e == hipSuccess) e = hipMalloc(&s->ccache2, std::min<size_t>(n, 2048) * 3 * sizeof(float4));
@@ -1448,9 +1447,7 @@ extern "C" int sp_gicp_source_prepare(sp_gicp_source* s, const sp_gicp_target* t
     s->cache_target = target;
     s->cache_version = target->version;
     prepare_source_kernel<<<nb, kBlock, 0, st>>>(pts, target->reg_type == SP_REG_GICP ? reinterpret_cast<const float4*>(src_covs) : nullptr,
-                                                 s->perm, sort_by_cell != SP_SOURCE_SORT, (unsigned)n,
-                                                 (unsigned)((n + 63) / 64 * 64), reinterpret_cast<float*>(s->pts),
-                                                 reinterpret_cast<float*>(s->covp));
+                                                 s->perm, sort_by_cell != SP_SOURCE_SORT, (unsigned)n, s->tiles);
     return launch_status();
 }
 
@@ -1872,6 +1869,17 @@ extern "C" int sp_gicp_source_set_wave_per_point(sp_gicp_source* s, int mode) {
 extern "C" const uint32_t* sp_internal_align_searched_log(void* workspace, size_t* n_entries_out) {
     if (n_entries_out) *n_entries_out = sp::kSearchedLog;
     return workspace ? sp::align_ws(workspace).searched_log : nullptr;
+}
+// The prepared source's wave tiles (sp_internal.h), for the layout's test: their size, and a copy out of or into them.
+extern "C" size_t sp_internal_source_tile_floats(const sp_gicp_source* s) {
+    return s ? sp::src_tile_words(s->n_max ? s->n_max : 1) : 0;
+}
+extern "C" int sp_internal_source_tiles_copy(sp_gicp_source* s, float* device_buffer, size_t n_floats, int to_source, void* stream) {
+    if (!s || !device_buffer || n_floats != sp_internal_source_tile_floats(s)) return SP_ERR_INVALID_ARGUMENT;
+    const hipError_t e = hipMemcpyAsync(to_source ? s->tiles : device_buffer, to_source ? device_buffer : s->tiles,
+                                        n_floats * sizeof(float), hipMemcpyDeviceToDevice, sp::as_stream(stream));
+    if (e != hipSuccess) { sp_set_error(hipGetErrorString(e)); return SP_ERR_HIP; }
+    return SP_OK;
 }
 // Per-handle measurement / tuning switches (sp_internal.h): exported for tests/, bench.py and scratch/ only.
 extern "C" int sp_internal_source_option(sp_gicp_source* s, int option, int value) {

@@ -237,10 +237,18 @@ __device__ __forceinline__ Sym3 load_sym(const float4* __restrict__ p) {
     return Sym3{a.x, a.y, a.z, a.w, b.x, b.y};
 }
 
+// The prepared source lies in WAVE TILES: 64 consecutive prepared points are one contiguous block of kSrcTileWords floats
+// (2304 bytes), sub-plane k (x y z | xx xy xz yy yz zz) at word 64 k of the block, the point's lane l = i % 64 at word l of the
+// sub-plane. A point has ONE address, base + (i / 64) * 2304 + (i % 64) * 4 bytes; its nine words are nine loads of that
+// address at the immediate offsets 0, 256, ..., 2048, each still one coalesced 256-byte request of a wave, all in one run of
+// memory. Whole tiles are allocated (src_tile_words); the unused lanes of the last one are never read. POINT_TO_DISTRIBUTION
+// has no source covariance: the same tile, its six covariance sub-planes neither written nor read.
+constexpr unsigned kSrcPlanes = 9;
+constexpr unsigned kSrcTileWords = kSrcPlanes * kWave;
+__host__ __device__ inline size_t src_tile_words(size_t n) { return (n + kWave - 1) / kWave * kSrcTileWords; }
+
 struct FusedParams {
-    const float* src;      // prepared source: planes x | y | z, sstride floats apart
-    const float* scovp;    // prepared source covariances: planes xx | xy | xz | yy | yz | zz
-    unsigned sstride;
+    const float* src;      // prepared source in wave tiles (src_words)
     const float4* tpts;    // grid-ordered target points
     const unsigned* tstart;
     const float4* tcovp;   // grid-ordered prepared target covariances
@@ -251,11 +259,22 @@ struct FusedParams {
     Mat4Arg T_val;
     const float* T_dev;
     const unsigned* perm;  // prepared-source order -> original source index (for the optional neighbour outputs)
-    float4* ccache;        // per prepared source point: its previous correspondence (point, covariance row), 3 x float4
+    float4* ccache;        // per prepared source point: its previous correspondence (point, covariance row), 3 x float4; never null
     int cache_valid;       // 0: first linearisation after sp_gicp_source_prepare, the cache holds nothing yet
     int32_t* nn_idx;
     float* nn_d2;
 };
+
+// The nine words of prepared source point i: the one address, then the words at fixed offsets from it.
+__device__ __forceinline__ const float* src_words(const FusedParams& P, unsigned i) {
+    return P.src + ((size_t)(i / kWave) * kSrcTileWords + (i % kWave));
+}
+__device__ __forceinline__ float4 src_point(const float* __restrict__ w) {
+    return make_float4(w[0], w[kWave], w[2 * kWave], 1.0f);
+}
+__device__ __forceinline__ Sym3 src_cov(const float* __restrict__ w) {
+    return Sym3{w[3 * kWave], w[4 * kWave], w[5 * kWave], w[6 * kWave], w[7 * kWave], w[8 * kWave]};
+}
 
 // Linearisation of one correspondence (source point s with q = T s, winner nn, packed covariances) and accumulation.
 // P2D (linearize_point_to_distribution, factor.hpp:311-354): Ct is the target's information matrix M = inverse(Ct_raw)
@@ -403,14 +422,16 @@ __device__ __forceinline__ float search_bound2_margin(const FusedParams& P, floa
 // One source point of the fused iteration: q = T p -> correspondence (cache row by certificate, else exact NN on the target
 // grid) -> linearise -> accumulate.
 // P.cache_valid: 0 the cache holds nothing (every point is searched), 1 a row is used when its certificate holds: while
-// correspondences hold, an iteration is a pure coalesced stream of 84 bytes per point (12 p + 24 Cs' as planes + 48 cache
-// row) with no search and no gather, and a wave whose lanes all pass never enters the search code.
+// correspondences hold, an iteration is a pure coalesced stream of 84 bytes per point (12 p + 24 Cs' of its wave tile + 48
+// cache row) with no search and no gather, and a wave whose lanes all pass never enters the search code.
 // SEED: a point whose certificate fails starts its search from the previous winner (grid_nn1_fast's `seed`).
 // NEG: a search that finds nothing is made with the widened bound and recorded as a negative certificate (store_correspondence).
 template <int LOSS, bool FAST_NN, bool P2D = false, bool SEED = true, bool NEG = true>
 __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T, unsigned i, float (&acc)[kAcc - 1],
                                             unsigned& cnt, unsigned& searched) {
-    const float4 s = make_float4(P.src[i], P.src[P.sstride + i], P.src[2 * (size_t)P.sstride + i], 1.0f);
+    const float* const sw = src_words(P, i);
+    const float4 s = src_point(sw);
+    float4* const row = P.ccache + 3 * (size_t)i;  // (a prepared source always has its cache rows)
     float qx, qy, qz;
     transform_point(T, s.x, s.y, s.z, qx, qy, qz);
     Nearest nn;
@@ -419,8 +440,7 @@ __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T
     bool seeded = false;
     Nearest seed;
     seed.d2 = FLT_MAX; seed.idx = -1; seed.pos = 0; seed.x = seed.y = seed.z = 0.0f;
-    float4* const row = P.ccache ? P.ccache + 3 * (size_t)i : nullptr;
-    if (row && P.cache_valid) {
+    if (P.cache_valid) {
         const float4 r0 = row[0], r1 = row[1], r2 = row[2];
         const float d = dist2(qx, qy, qz, r0.x, r0.y, r0.z);
         const unsigned pos = __float_as_uint(r2.w);
@@ -445,10 +465,8 @@ __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T
         } else {
             nn = grid_nn1(P.tpts, P.tstart, P.g, qx, qy, qz, &seed, 0);
         }
-        if (row) {
-            if (NEG) store_correspondence(row, P, nn, Ct, qx, qy, qz, margin2);
-            else store_correspondence(row, P, nn, Ct);
-        } else if (nn.idx >= 0) Ct = load_sym(P.tcovp + 2 * (size_t)nn.pos);
+        if (NEG) store_correspondence(row, P, nn, Ct, qx, qy, qz, margin2);
+        else store_correspondence(row, P, nn, Ct);
     }
     if (P.nn_idx) {
         const unsigned o = P.perm[i];
@@ -456,11 +474,16 @@ __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T
         P.nn_d2[o] = nn.d2;
     }
     if (nn.idx < 0 || nn.d2 > P.max_d2) return;
-    const float* const cp = P.scovp + i;
-    const size_t st = P.sstride;
-    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}
-                        : Sym3{cp[0], cp[st], cp[2 * st], cp[3 * st], cp[4 * st], cp[5 * st]};
-    fused_math<LOSS, P2D>(P, T, s, qx, qy, qz, nn, Cs, Ct, acc, cnt);
+    // What the arithmetic reads of the source is requested HERE, the coordinates a second time with the covariance (one trip,
+    // the same tile that the loop's head has just brought in), from an address formed again from i: neither the three
+    // coordinates nor the address then occupy registers across the search, which at the kernels' 128-register budget is the
+    // difference between no spill and up to three in the GICP instantiations. (The empty asm only keeps the compiler from
+    // merging this address, and with it these loads, with the ones at the head.)
+    unsigned i_again = i;
+    asm volatile("" : "+v"(i_again));
+    const float* const sw_again = src_words(P, i_again);
+    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f} : src_cov(sw_again);
+    fused_math<LOSS, P2D>(P, T, src_point(sw_again), qx, qy, qz, nn, Cs, Ct, acc, cnt);
 }
 
 // fused_point with the wave working together where a lane alone would hold it up: EVERY lane of the wave calls this
@@ -480,7 +503,8 @@ __device__ __forceinline__ void fused_point_wave(const FusedParams& P, const Rig
                                                  float (&acc)[kAcc - 1], unsigned& cnt, unsigned& searched) {
     const unsigned ii = valid ? i : 0u;
     SP_PSTAMP(0);
-    const float4 s = make_float4(P.src[ii], P.src[P.sstride + ii], P.src[2 * (size_t)P.sstride + ii], 1.0f);
+    const float* const sw = src_words(P, ii);
+    const float4 s = src_point(sw);
     float qx, qy, qz;
     transform_point(T, s.x, s.y, s.z, qx, qy, qz);
     Nearest nn;
@@ -548,10 +572,7 @@ __device__ __forceinline__ void fused_point_wave(const FusedParams& P, const Rig
         P.nn_d2[o] = nn.d2;
     }
     if (!valid || nn.idx < 0 || nn.d2 > P.max_d2) return;
-    const float* const cp = P.scovp + ii;
-    const size_t st = P.sstride;
-    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}
-                        : Sym3{cp[0], cp[st], cp[2 * st], cp[3 * st], cp[4 * st], cp[5 * st]};
+    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f} : src_cov(sw);
     fused_math<LOSS, P2D>(P, T, s, qx, qy, qz, nn, Cs, Ct, acc, cnt);
     SP_PSTAMP(6);
 }
@@ -581,7 +602,8 @@ __device__ __forceinline__ void fused_query_wave(const FusedParams& P, const Rig
                                                  unsigned& cnt, unsigned& searched, float4* rows_out = nullptr,
                                                  const float4* qc_in = nullptr, float4* qc_out = nullptr) {
     SP_PSTAMP(0);
-    const float4 s = make_float4(P.src[i], P.src[P.sstride + i], P.src[2 * (size_t)P.sstride + i], 1.0f);
+    const float* const sw = src_words(P, i);
+    const float4 s = src_point(sw);
     float qx, qy, qz;
     transform_point(T, s.x, s.y, s.z, qx, qy, qz);
     Nearest nn;
@@ -652,10 +674,7 @@ __device__ __forceinline__ void fused_query_wave(const FusedParams& P, const Rig
         SP_PSTAMP(5);
     }
     if (nn.idx < 0 || nn.d2 > P.max_d2) return;
-    const float* const cp = P.scovp + i;
-    const size_t st = P.sstride;
-    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}
-                        : Sym3{cp[0], cp[st], cp[2 * st], cp[3 * st], cp[4 * st], cp[5 * st]};
+    const Sym3 Cs = P2D ? Sym3{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f} : src_cov(sw);
     fused_math<LOSS, P2D>(P, T, s, qx, qy, qz, nn, Cs, Ct, acc, cnt);
     SP_PSTAMP(6);
 }
@@ -667,7 +686,8 @@ __device__ __forceinline__ void fused_query_wave(const FusedParams& P, const Rig
 template <int LOSS, bool P2D>
 __device__ __forceinline__ void error_prepared_point(const FusedParams& P, const Rigid& T, const Rigid& TL, unsigned i,
                                                      float (&acc)[1], unsigned& cnt) {
-    const float4 s = make_float4(P.src[i], P.src[P.sstride + i], P.src[2 * (size_t)P.sstride + i], 1.0f);
+    const float* const sw = src_words(P, i);
+    const float4 s = src_point(sw);
     const float4* const row = P.ccache + 3 * (size_t)i;
     const float4 tp = row[0], c0 = row[1], c1 = row[2];
     if (__float_as_int(c1.z) < 0) return;  // no neighbour found
@@ -678,10 +698,8 @@ __device__ __forceinline__ void error_prepared_point(const FusedParams& P, const
     transform_point(T, s.x, s.y, s.z, qx, qy, qz);
     Nearest nn;
     nn.x = tp.x; nn.y = tp.y; nn.z = tp.z; nn.idx = __float_as_int(c1.z); nn.pos = 0; nn.d2 = 0.0f;
-    const float* const cp = P.scovp + i;
-    const size_t st = P.sstride;
     Sym3 Cs{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (!P2D) Cs = Sym3{cp[0], cp[st], cp[2 * st], cp[3 * st], cp[4 * st], cp[5 * st]};
+    if (!P2D) Cs = src_cov(sw);
     const Sym3 Ct{c0.x, c0.y, c0.z, c0.w, c1.x, c1.y};
     fused_math<LOSS, P2D, true, 1>(P, T, s, qx, qy, qz, nn, Cs, Ct, acc, cnt);
 }
@@ -810,8 +828,7 @@ constexpr size_t kOptRowsBytes = 2 * (size_t)256 * 32 * sizeof(unsigned long lon
 }  // namespace sp
 struct sp_gicp_source {
     size_t n_max = 0, n = 0;
-    float4* pts = nullptr;    // n points in prepared order
-    float4* covp = nullptr;   // 2 x float4 per point, prepared order
+    float* tiles = nullptr;   // the prepared points and covariances in wave tiles (src_tile_words(n_max) floats, see FusedParams)
     unsigned* perm = nullptr; // prepared position -> original index
     float4* ccache = nullptr;      // 3 x float4 per prepared point: its previous correspondence (see fused_point)
     float4* qcert = nullptr;       // margin certificates of the wave-per-point optimiser launch (fused_query_wave), qcert_points of them
@@ -844,9 +861,7 @@ FusedParams make_fused_params(const sp_gicp_target* target, const sp_gicp_source
                               const float* transT, int transT_on_device, int32_t* nn_idx_out, float* nn_d2_out) {
     const size_t n = source->n;
     FusedParams P;
-    P.src = reinterpret_cast<const float*>(source->pts);
-    P.scovp = reinterpret_cast<const float*>(source->covp);
-    P.sstride = (unsigned)((n + 63) / 64 * 64);
+    P.src = source->tiles;
     P.tpts = target->grid->d_pts;
     P.tstart = target->grid->d_start;
     P.tcovp = target->covp;

@@ -60,6 +60,13 @@ int sp_internal_grid_small_build(int enable);
 /* Device pointer to the per-launch log of an sp_gicp_align_* workspace: entry k = number of source points launch k had to
  * search for (the others reused their previous correspondence by certificate). *n_entries_out = entries kept (64). */
 const uint32_t* sp_internal_align_searched_log(void* workspace, size_t* n_entries_out);
+/* The prepared source's buffer: whole tiles for the n_max of sp_gicp_source_create, sp_internal_source_tile_floats floats. Tile t
+ * holds the prepared points 64 t .. 64 t + 63 in 9 x 64 floats: word 64 k + l of the tile is sub-plane k (x y z | xx xy xz yy yz zz:
+ * the point, the plane-regularised covariance's upper triangle) of point 64 t + l. The lanes of the last tile past the prepared n
+ * and, for POINT_TO_DISTRIBUTION, the covariance sub-planes are not written. sp_internal_source_tiles_copy copies the whole buffer
+ * to (to_source = 0) or from (1) a device buffer of that many floats. */
+size_t sp_internal_source_tile_floats(const sp_gicp_source* source);
+int sp_internal_source_tiles_copy(sp_gicp_source* source, float* device_buffer, size_t n_floats, int to_source, void* stream);
 /* The library's own stable radix sort of (u32 key, u32 value) pairs on the low `bits` key bits (csrc/radix_sort.hip), for its
  * test: all pointers are device pointers, the four arrays are overwritten, *result_in_b_out (host) says which pair holds
  * the sorted data. workspace: sp_internal_radix_sort_workspace_bytes(n). */
