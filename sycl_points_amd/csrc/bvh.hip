@@ -22,6 +22,7 @@
 #include "grid_device.h"
 #include "radix_sort.h"
 #include "sp_internal.h"
+#include "sp_spatial.h"
 #include "sp_wave_select.h"
 
 void sp_set_error(const char* msg);
@@ -46,60 +47,10 @@ constexpr int kBvhLeaf = 16;
 constexpr int kBvhStack = 48;
 constexpr uint64_t kBvhInvalidKey = (1ull << 48) - 1ull;  // cell (65535, 65535, 65535): no valid point gets it
 
-__device__ __forceinline__ unsigned enc_f(float f) {  // order-preserving float -> uint
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
-__global__ void bvh_bbox_init_kernel(unsigned* bbox) {
-    if (threadIdx.x < 3) bbox[threadIdx.x] = 0xffffffffu;
-    else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;
-}
-// bbox[0..2] = min xyz, bbox[3..5] = max xyz (encoded), over the finite points; four loads in flight per lane.
-__global__ __launch_bounds__(kBlock) void bvh_bbox_kernel(const float4* __restrict__ pts, unsigned n, unsigned* bbox) {
-    __shared__ unsigned red[kBlock / kWave][6];
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    const unsigned stride = gridDim.x * kBlock;
-    for (unsigned i0 = blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += 4 * stride) {
-        float4 p[4];
+// The cloud's box as floats, from the six order-preserving words the build left.
+__device__ __forceinline__ void bvh_load_box(const unsigned* __restrict__ bbox, float (&box)[6]) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = pts[min(i0 + u * stride, n - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i0 + u * stride < n && isfinite(p[u].x) && isfinite(p[u].y) && isfinite(p[u].z)) {
-                const unsigned e[3] = {enc_f(p[u].x), enc_f(p[u].y), enc_f(p[u].z)};
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], e[a]); mx[a] = max(mx[a], e[a]); }
-            }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o, 64));
-            mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o, 64));
-        }
-    const unsigned wave = threadIdx.x / kWave;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        unsigned v = red[0][threadIdx.x];
-        for (int w = 1; w < kBlock / kWave; ++w) v = threadIdx.x < 3 ? min(v, red[w][threadIdx.x]) : max(v, red[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&bbox[threadIdx.x], v);
-        else atomicMax(&bbox[threadIdx.x], v);
-    }
-}
-
-__device__ __forceinline__ uint64_t spread21(uint64_t x) {  // up to 21 bits -> every third bit
-    x = (x | (x << 32)) & 0x001f00000000ffffull;
-    x = (x | (x << 16)) & 0x001f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
+    for (int a = 0; a < 6; ++a) box[a] = ordered_float(bbox[a]);
 }
 __global__ __launch_bounds__(kBlock) void bvh_key_kernel(const float4* __restrict__ pts, unsigned n,
                                                          const unsigned* __restrict__ bbox, uint64_t* __restrict__ keys,
@@ -109,28 +60,12 @@ __global__ __launch_bounds__(kBlock) void bvh_key_kernel(const float4* __restric
     const float4 p = pts[i];
     uint64_t key = kBvhInvalidKey;  // non-finite points: behind all others, in no box, never a neighbour (their distance is NaN)
     if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-        const float v[3] = {p.x, p.y, p.z};
-        uint64_t c[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float lo = dec_f(bbox[a]), hi = dec_f(bbox[3 + a]);
-            const float ext = hi - lo;
-            const float t = ext > 0.0f ? (v[a] - lo) / ext * 65535.0f : 0.0f;
-            c[a] = (uint64_t)fminf(fmaxf(t, 0.0f), 65534.0f);
-        }
-        key = spread21(c[0]) | (spread21(c[1]) << 1) | (spread21(c[2]) << 2);
+        float box[6];
+        bvh_load_box(bbox, box);
+        key = morton_key_in_box(p.x, p.y, p.z, box, kBvhCells);
     }
     keys[i] = key;
     vals[i] = i;
-}
-__global__ __launch_bounds__(kBlock) void bvh_gather_kernel(const float4* __restrict__ pts, const unsigned* __restrict__ order,
-                                                            unsigned n, float4* __restrict__ out) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const unsigned src = order[i];
-    float4 p = pts[src];
-    p.w = __uint_as_float(src);
-    out[i] = p;
 }
 
 // Length of the common prefix of the (key, position) pairs i and j; -1 outside the array.
@@ -285,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void bvh_search_kernel(const float4* __rest
                 const bool seen = skip_window && b + s >= w0 && b + s <= w1;
                 // (a non-finite point gives a NaN distance: every comparison fails, it is never taken)
                 if (b + s <= last && !seen && (!RADIUS || d <= radius_sq) && (d < kth || (d == kth && pi < kth_idx)))
-                    lex_insert<KCAP>(bd, bi, k, d, pi, kth, kth_idx);
+                    sorted_insert<KCAP, InsertOrder::kByDistanceIndex>(bd, bi, k, d, pi, kth, &kth_idx);
             }
         }
     };
@@ -479,19 +414,13 @@ __global__ __launch_bounds__(kBlock) void bvh_query_key_kernel(const float4* __r
     if (i >= nq) return;
     const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
     const float4 q4 = queries[i];
-    float v[3];
-    transform_point(T, q4.x, q4.y, q4.z, v[0], v[1], v[2]);
+    float x, y, z;
+    transform_point(T, q4.x, q4.y, q4.z, x, y, z);
     uint64_t key = kBvhInvalidKey;
-    if (isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2])) {  // (the key of bvh_key_kernel, clamped to the tree's box)
-        uint64_t c[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float lo = dec_f(bbox[a]), hi = dec_f(bbox[3 + a]);
-            const float ext = hi - lo;
-            const float t = ext > 0.0f ? (v[a] - lo) / ext * 65535.0f : 0.0f;
-            c[a] = (uint64_t)fminf(fmaxf(t, 0.0f), 65534.0f);
-        }
-        key = spread21(c[0]) | (spread21(c[1]) << 1) | (spread21(c[2]) << 2);
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {  // (the key of bvh_key_kernel, clamped to the tree's box)
+        float box[6];
+        bvh_load_box(bbox, box);
+        key = morton_key_in_box(x, y, z, box, kBvhCells);
     }
     keys[i] = key;
     vals[i] = i;
@@ -865,14 +794,14 @@ extern "C" int sp_bvh_create(const float* points, size_t n, void* stream, sp_bvh
         unsigned* const bbox = b->bbox;
         uint64_t *kin = b_kin.as<uint64_t>(), *kout = b_kout.as<uint64_t>();
         unsigned *vin = b_vin.as<unsigned>(), *vout = b_vout.as<unsigned>();
-        bvh_bbox_init_kernel<<<1, 64, 0, st>>>(bbox);
+        bbox_init_kernel<><<<1, 64, 0, st>>>(bbox);
         unsigned g = div_up(n, (size_t)kBlock * 16);
-        bvh_bbox_kernel<<<g > 256u ? 256u : (g ? g : 1u), kBlock, 0, st>>>(pts, (unsigned)n, bbox);
+        bbox_kernel<><<<g > 256u ? 256u : (g ? g : 1u), kBlock, 0, st>>>(pts, (unsigned)n, bbox);
         bvh_key_kernel<<<div_up(n, kBlock), kBlock, 0, st>>>(pts, (unsigned)n, bbox, kin, vin);
         bool in_b = false;
         if (radix_sort_pairs_u64(kin, kout, vin, vout, n, 48, b_tmp.p, tmp_bytes, &in_b, st) != SP_OK) return fail("[BVH] sort failed");
         if (!in_b) { kout = kin; vout = vin; }
-        bvh_gather_kernel<<<div_up(n, kBlock), kBlock, 0, st>>>(pts, vout, (unsigned)n, b->pts);
+        gather_by_order_kernel<><<<div_up(n, kBlock), kBlock, 0, st>>>(pts, vout, (unsigned)n, b->pts);
         if (n > 1) {
             bvh_hierarchy_kernel<<<div_up(n - 1, kBlock), kBlock, 0, st>>>(kout, (int)n, b->node, b_parent.as<int>(),
                                                                           b_lparent.as<int>(), b_tickets.as<unsigned>());

@@ -29,6 +29,7 @@
 void sp_set_error(const char* msg);
 
 #include "sp_internal.h"
+#include "sp_spatial.h"
 #include "sp_wave_select.h"
 
 // The (cell id, index) pairs are sorted by radix_sort.hip (3 passes for a 22-bit cell id: 63 us per 1M pairs; the library's
@@ -36,59 +37,6 @@ void sp_set_error(const char* msg);
 
 namespace sp {
 namespace {
-
-__device__ __forceinline__ unsigned enc(float f) {  // order-preserving float -> uint
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float dec(unsigned u) {
-    const unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
-
-// bbox[0..2] = min xyz, bbox[3..5] = max xyz (encoded), over finite points.
-// Grid-stride over <= 256 workgroups, wave butterfly, LDS across the 4 waves, then 6 integer atomics per workgroup
-// (exact, order independent).
-__global__ __launch_bounds__(kBlock) void bbox_kernel(const float4* __restrict__ pts, unsigned n, unsigned* bbox) {
-    __shared__ unsigned red[kBlock / kWave][6];
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    // (four loads in flight per lane: one at a time, 16 dependent trips made this the longest kernel of the build, 18 us)
-    const unsigned stride = gridDim.x * kBlock;
-    for (unsigned i0 = blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += 4 * stride) {
-        float4 p[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = pts[min(i0 + u * stride, n - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i0 + u * stride < n && isfinite(p[u].x) && isfinite(p[u].y) && isfinite(p[u].z)) {
-                const unsigned e[3] = {enc(p[u].x), enc(p[u].y), enc(p[u].z)};
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], e[a]); mx[a] = max(mx[a], e[a]); }
-            }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o, 64));
-            mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o, 64));
-        }
-    }
-    const unsigned wave = threadIdx.x / kWave;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        unsigned v = red[0][threadIdx.x];
-        for (int w = 1; w < kBlock / kWave; ++w) v = threadIdx.x < 3 ? min(v, red[w][threadIdx.x]) : max(v, red[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&bbox[threadIdx.x], v);
-        else atomicMax(&bbox[threadIdx.x], v);
-    }
-}
 
 // bounds_error (sp_grid_create_bounded): the box came from the caller — a finite point outside it would sit in a border cell whose
 // geometry does not contain it, and the searches' pruning would be wrong without anybody noticing: it raises the device error word.
@@ -368,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void grid_search_kernel(const float4* __res
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int pi = __float_as_int(p[j].w);
-                    if (i + j < e && (d[j] < kth || (d[j] == kth && pi < kth_idx))) lex_insert<KCAP>(bd, bi, k, d[j], pi, kth, kth_idx);
+                    if (i + j < e && (d[j] < kth || (d[j] == kth && pi < kth_idx))) sorted_insert<KCAP, InsertOrder::kByDistanceIndex>(bd, bi, k, d[j], pi, kth, &kth_idx);
                 }
                 if (bound2 < kth) { kth = bound2; kth_idx = -1; }  // (a list that is not full yet says FLT_MAX)
             }
@@ -799,7 +747,7 @@ __global__ __launch_bounds__(kBlock) void grid_self_knn_lane_kernel(const float4
                 for (int j = 0; j < 4; ++j) {
                     const int pi = __float_as_int(p[j].w);
                     if (i + j < e && (d[j] < kth || (d[j] == kth && pi < kth_idx)))
-                        lex_insert<KCAP>(bd, bi, k, d[j], pi, kth, kth_idx, bp, (int)(i + j));
+                        sorted_insert<KCAP, InsertOrder::kByDistanceIndex>(bd, bi, k, d[j], pi, kth, &kth_idx, bp, (int)(i + j));
                 }
             }
         });
@@ -1254,7 +1202,6 @@ int grid_create_impl(const float* points, size_t n, float cell_size, float point
     ScratchBuf bbox_buf;
     if ((e = bbox_buf.get(6 * sizeof(unsigned), st)) != hipSuccess) return fail(e);
     unsigned* const d_bbox = bbox_buf.as<unsigned>();
-    const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     unsigned h_bbox_own[6];
     unsigned* const h_bbox = pinned_mailbox() ? static_cast<unsigned*>(pinned_mailbox()) : h_bbox_own;
     float mn[3], mx[3];
@@ -1262,17 +1209,15 @@ int grid_create_impl(const float* points, size_t n, float cell_size, float point
         for (int a = 0; a < 3; ++a) { mn[a] = bounds6[a]; mx[a] = bounds6[3 + a]; }
         e = hipSuccess;
     } else {
-        e = hipMemcpyAsync(d_bbox, init, sizeof init, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            bbox_kernel<<<std::min(stream_grid(n, kBlock, 4), 256u), kBlock, 0, st>>>(pts, (unsigned)n, d_bbox);  // (1024 workgroups: 26 us — their 6 atomics each share one cache line)
-            e = hipMemcpyAsync(h_bbox, d_bbox, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st);
-        }
+        bbox_init_kernel<><<<1, 64, 0, st>>>(d_bbox);
+        bbox_kernel<><<<std::min(stream_grid(n, kBlock, 4), 256u), kBlock, 0, st>>>(pts, (unsigned)n, d_bbox);
+        e = hipMemcpyAsync(h_bbox, d_bbox, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return fail(e);
         bool any = h_bbox[0] != 0xffffffffu;
         for (int a = 0; a < 3; ++a) {
-            mn[a] = any ? dec(h_bbox[a]) : 0.0f;
-            mx[a] = any ? dec(h_bbox[3 + a]) : 0.0f;
+            mn[a] = any ? ordered_float(h_bbox[a]) : 0.0f;
+            mx[a] = any ? ordered_float(h_bbox[3 + a]) : 0.0f;
         }
     }
     // 2. cell size: given, or chosen for `points_per_cell` points per cell on average over the bounding box

@@ -62,47 +62,6 @@ __device__ __forceinline__ int cell_coord(float v, float o, float inv_h, int dim
     return (int)fminf(fmaxf(t, 0.0f), (float)(dim - 1));
 }
 
-// (distance, index) lexicographic sorted insertion into the first k slots. With `bp` the grid positions of the entries ride
-// along (the fused covariance reads the neighbours by position).
-template <int KCAP>
-__device__ __forceinline__ void lex_insert(float (&bd)[KCAP], int (&bi)[KCAP], int k, float d, int idx, float& kth,
-                                           int& kth_idx, int* bp = nullptr, int pos = 0) {
-    if (KCAP == 1) {
-        const bool better = d < bd[0] || (d == bd[0] && idx < bi[0]);
-        bi[0] = better ? idx : bi[0];
-        bd[0] = better ? d : bd[0];
-        if (bp) bp[0] = better ? pos : bp[0];
-        kth = bd[0];
-        kth_idx = bi[0];
-        return;
-    }
-    float cd = d;
-    int ci = idx, cp = pos;
-    bool shifting = false;
-#pragma unroll
-    for (int i = 0; i < KCAP; ++i) {
-        if (i < k) {
-            const bool sw = shifting || cd < bd[i] || (cd == bd[i] && ci < bi[i]);
-            const float td = bd[i];
-            const int ti = bi[i];
-            const float nd = sw ? cd : td;
-            const int ni = sw ? ci : ti;
-            bd[i] = nd;
-            bi[i] = ni;
-            cd = sw ? td : cd;
-            ci = sw ? ti : ci;
-            if (bp) {  // (known when the call is inlined: no test remains)
-                const int tp = bp[i];
-                bp[i] = sw ? cp : tp;
-                cp = sw ? tp : cp;
-            }
-            shifting = sw;
-            kth = nd;
-            kth_idx = ni;
-        }
-    }
-}
-
 // squared distance from coordinate v to the interval [lo, hi], made conservative by eps
 __device__ __forceinline__ float gap2(float v, float lo, float hi, float eps) {
     const float g = fmaxf(fmaxf(lo - v, v - hi) - eps, 0.0f);

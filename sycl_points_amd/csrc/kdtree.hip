@@ -22,6 +22,7 @@
 
 #include "sp_common.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 
 void sp_set_error(const char* msg);
 
@@ -203,36 +204,6 @@ void build_host(const float* pts, size_t n, size_t leaf_threshold, std::vector<H
     root = t.root;
 }
 
-// Sorted insertion into the first k slots, strict '<' (kdtree.hpp:119-137): the first visited wins ties.
-template <int KCAP>
-__device__ __forceinline__ void best_insert(float (&bd)[KCAP], int (&bi)[KCAP], int k, float d, int idx, float& kth) {
-    if (KCAP == 1) {
-        const bool better = d < bd[0];
-        bi[0] = better ? idx : bi[0];
-        bd[0] = better ? d : bd[0];
-        kth = bd[0];
-        return;
-    }
-    float cd = d;
-    int ci = idx;
-    bool shifting = false;
-#pragma unroll
-    for (int i = 0; i < KCAP; ++i) {
-        if (i < k) {
-            const bool sw = shifting || (cd < bd[i]);
-            const float td = bd[i];
-            const int ti = bi[i];
-            const float nd = sw ? cd : td;
-            bd[i] = nd;
-            bi[i] = sw ? ci : ti;
-            cd = sw ? td : cd;
-            ci = sw ? ti : ci;
-            shifting = sw;
-            kth = nd;  // after the last executed iteration (i == k-1) this is bestK[k-1].dist_sq
-        }
-    }
-}
-
 template <int KCAP, bool RADIUS, bool BATCH_LEAF>
 __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __restrict__ internal,
                                                                const float4* __restrict__ leaf, int root,
@@ -281,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __r
                 const float d = valid ? dist2(qx, qy, qz, p.x, p.y, p.z) : FLT_MAX;
                 const bool take = RADIUS ? (valid && d <= radius_sq && d < kth) : (d < kth);
                 if (take) {
-                    best_insert<KCAP>(bd, bi, k, d, pidx, kth);
+                    sorted_insert<KCAP, InsertOrder::kByDistance>(bd, bi, k, d, pidx, kth);
                 }
             };
             if (KCAP == 1 && stride == 16) {
@@ -322,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __r
         const float d = valid ? chain3(dx, dx, dy, dy, dz, dz) : FLT_MAX;
         const bool take = RADIUS ? (valid && d <= radius_sq && d < kth) : (d < kth);
         if (take) {
-            best_insert<KCAP>(bd, bi, k, d, nidx, kth);
+            sorted_insert<KCAP, InsertOrder::kByDistance>(bd, bi, k, d, nidx, kth);
         }
         const float axis_dist = axis == 0 ? dx : (axis == 1 ? dy : dz);
         const int nearer = (axis_dist <= 0) ? left : right;
@@ -346,11 +317,6 @@ __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __r
 #pragma unroll
     for (int i = 0; i < KCAP; ++i)
         if (i < k) { d2_out[o + i] = bd[i]; idx_out[o + i] = bi[i]; }
-}
-
-__global__ void fill_empty_kernel(int32_t* idx, float* d2, size_t n) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) { idx[i] = -1; d2[i] = FLT_MAX; }
 }
 
 // K4: rewrite idx of every stored point (kdtree.hpp:743-755). valid <=> idx >= 0.
@@ -476,7 +442,7 @@ extern "C" int sp_kdtree_search(const sp_kdtree* tree, const float* queries, siz
     hipStream_t st = as_stream(stream);
     tree->streams.note(st);
     if (tree->root == kNone) {
-        fill_empty_kernel<<<div_up(nq * k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
+        fill_empty_kernel<><<<div_up(nq * k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
         return launch_status();
     }
     return dispatch_search<false>(tree, queries, nq, k, -1.0f, transT, transT_on_device, idx_out, d2_out, st);
@@ -495,7 +461,7 @@ extern "C" int sp_kdtree_radius_search(const sp_kdtree* tree, const float* queri
     hipStream_t st = as_stream(stream);
     tree->streams.note(st);
     if (tree->root == kNone) {
-        fill_empty_kernel<<<div_up(nq * max_k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * max_k);
+        fill_empty_kernel<><<<div_up(nq * max_k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * max_k);
         return launch_status();
     }
     return dispatch_search<true>(tree, queries, nq, max_k, radius * radius, transT, transT_on_device, idx_out, d2_out,

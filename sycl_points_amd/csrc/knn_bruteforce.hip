@@ -12,43 +12,13 @@
 // query's candidates (8.5 ms single pass -> 3.6 ms bounded lists in round 2 -> see knn_bf_collect_kernel).
 #include "sp_common.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 #include "sp_wave_select.h"
 
 namespace sp {
 namespace {
 
 constexpr int kTile = 1024;
-
-// Sorted insertion into the first k slots (strict '<', later arrivals go after equal distances), written as a
-// fully unrolled carry chain so the arrays stay in registers.
-template <int KCAP>
-__device__ __forceinline__ void topk_insert(float (&bd)[KCAP], int (&bi)[KCAP], int k, float d, int idx, float& kth) {
-    if (KCAP == 1) {
-        const bool better = d < bd[0];
-        bi[0] = better ? idx : bi[0];
-        bd[0] = better ? d : bd[0];
-        kth = bd[0];
-        return;
-    }
-    float cd = d;
-    int ci = idx;
-    bool shifting = false;
-#pragma unroll
-    for (int i = 0; i < KCAP; ++i) {
-        if (i < k) {
-            const bool sw = shifting || (cd < bd[i]);
-            const float td = bd[i];
-            const int ti = bi[i];
-            const float nd = sw ? cd : td;
-            bd[i] = nd;
-            bi[i] = sw ? ci : ti;
-            cd = sw ? td : cd;
-            ci = sw ? ti : ci;
-            shifting = sw;
-            kth = nd;  // after the last executed iteration (i == k-1) this is bestK[k-1].dist_sq
-        }
-    }
-}
 
 template <int KCAP, int QPT>
 __global__ __launch_bounds__(kBlock) void knn_bf_kernel(const float4* __restrict__ queries, unsigned nq,
@@ -87,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void knn_bf_kernel(const float4* __restrict
             for (int u = 0; u < QPT; ++u) {
                 const float d = dist2(qx[u], qy[u], qz[u], p.x, p.y, p.z);
                 if (d < kth[u]) {
-                    topk_insert<KCAP>(bd[u], bi[u], k, d, (int)(base + j), kth[u]);
+                    sorted_insert<KCAP, InsertOrder::kByDistance>(bd[u], bi[u], k, d, (int)(base + j), kth[u]);
                 }
             }
         }
@@ -219,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void knn_bf_merge_kernel(const int32_t* __r
         for (int i = 0; i < k; ++i) {
             const float d = pd2[o + i];
             if (!(d < kth)) break;  // list is ascending: nothing further in this chunk can enter
-            topk_insert<KCAP>(bd, bi, k, d, pidx[o + i], kth);
+            sorted_insert<KCAP, InsertOrder::kByDistance>(bd, bi, k, d, pidx[o + i], kth);
         }
     }
     const size_t o = (size_t)q * (size_t)k;
@@ -271,47 +241,6 @@ struct BfFrame {
     float cx, cy, cz;  // centre of the finite targets' bounding box
     float pmax;        // >= |p - c| for every finite target
 };
-__device__ __forceinline__ unsigned enc_ordered(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_ordered(unsigned e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-__global__ void knn_bf_box_init_kernel(unsigned* box) {
-    if (threadIdx.x < 6) box[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
-}
-__global__ __launch_bounds__(kBlock) void knn_bf_box_kernel(const float4* __restrict__ targets, unsigned nt, unsigned* box) {
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < nt; i += gridDim.x * kBlock) {
-        const float4 p = targets[i];
-        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-            const unsigned e[3] = {enc_ordered(p.x), enc_ordered(p.y), enc_ordered(p.z)};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], e[a]); mx[a] = max(mx[a], e[a]); }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o, 64));
-            mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o, 64));
-        }
-    }
-    __shared__ unsigned red[kBlock / kWave][6];
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[threadIdx.x >> 6][a] = mn[a]; red[threadIdx.x >> 6][3 + a] = mx[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {  // one atomic per workgroup and bound (64 workgroups: the six words share a cache line)
-        unsigned v = red[0][threadIdx.x];
-        for (int w = 1; w < kBlock / kWave; ++w) v = threadIdx.x < 3 ? min(v, red[w][threadIdx.x]) : max(v, red[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&box[threadIdx.x], v);
-        else atomicMax(&box[threadIdx.x], v);
-    }
-}
 __global__ void knn_bf_frame_kernel(const unsigned* __restrict__ box, BfFrame* __restrict__ frame) {
     if (threadIdx.x != 0) return;
     BfFrame f{0.0f, 0.0f, 0.0f, 0.0f};
@@ -320,7 +249,7 @@ __global__ void knn_bf_frame_kernel(const unsigned* __restrict__ box, BfFrame* _
         float c[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const float lo = dec_ordered(box[a]), hi = dec_ordered(box[3 + a]);
+            const float lo = ordered_float(box[a]), hi = ordered_float(box[3 + a]);
             c[a] = 0.5f * lo + 0.5f * hi;
             const float h = fmaxf(hi - c[a], c[a] - lo);
             h2 += h * h;
@@ -549,7 +478,7 @@ __global__ __launch_bounds__(kBlock) void knn_bf_bound_kernel(const float* __res
         for (int j = 0; j < 8; ++j) d[j] = c0 + j < nchunks ? chunk_min[(size_t)(c0 + j) * nq + qc] : FLT_MAX;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (d[j] < kth) topk_insert<20>(bd, bi, k, d[j], 0, kth);
+            if (d[j] < kth) sorted_insert<20, InsertOrder::kByDistance>(bd, bi, k, d[j], 0, kth);
     }
     float E = 0.0f;  // |approximate - reference| distance, see knn_bf_chunkmin_kernel
     if (frame) {
@@ -1134,8 +1063,8 @@ int run_bounded(const float* q, size_t nq, const float* t, size_t nt, size_t k, 
         uint4* tA = reinterpret_cast<uint4*>(w + P.off_operands);
         uint4* qB = tA + 2 * (size_t)rows;
         float* qq = reinterpret_cast<float*>(qB + 2 * (size_t)cols);
-        knn_bf_box_init_kernel<<<1, 64, 0, st>>>(box);
-        knn_bf_box_kernel<<<std::min(div_up(nt, kBlock), 64u), kBlock, 0, st>>>(t4, (unsigned)nt, box);
+        bbox_init_kernel<><<<1, 64, 0, st>>>(box);
+        bbox_kernel<><<<std::min(div_up(nt, kBlock), 64u), kBlock, 0, st>>>(t4, (unsigned)nt, box);  // (64 workgroups: the six words share a cache line)
         knn_bf_frame_kernel<<<1, 64, 0, st>>>(box, frame);
         if (g_pass_a_valu) {
             knn_bf_chunkmin_kernel<<<dim3(P.a.qblocks, G), kBlock, 0, st>>>(q4, (unsigned)nq, t4, (unsigned)nt, P.a.chunk, frame, amin, il);
@@ -1161,11 +1090,6 @@ int run_bounded(const float* q, size_t nq, const float* t, size_t nt, size_t k, 
                                                          blk_off, G, subs, chunk_list, cand_cnt, cand, il);
     knn_bf_select_kernel<<<div_up(nq * 64, kBlock), kBlock, 0, st>>>(q4, (unsigned)nq, t4, (unsigned)nt, (int)k, cand_cnt, cand, idx, d2);
     return launch_status();
-}
-
-__global__ void fill_empty_kernel(int32_t* idx, float* d2, size_t n) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) { idx[i] = -1; d2[i] = FLT_MAX; }
 }
 
 }  // namespace
@@ -1202,7 +1126,7 @@ extern "C" int sp_knn_bruteforce(const float* queries, size_t nq, const float* t
     if (nq == 0) return SP_OK;
     hipStream_t st = as_stream(stream);
     if (nt == 0) {  // no targets: every slot keeps its initial -1 / FLT_MAX (knn/result.hpp:21-27)
-        fill_empty_kernel<<<div_up(nq * k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
+        fill_empty_kernel<><<<div_up(nq * k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
         return launch_status();
     }
     if (g_small_path && small_applies(nq, nt)) return run_small(queries, nq, targets, nt, k, idx_out, d2_out, st);

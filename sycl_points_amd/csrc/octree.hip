@@ -25,6 +25,7 @@
 
 #include "radix_sort.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 #include "sp_wave_select.h"
 
 void sp_set_error(const char* msg);
@@ -49,48 +50,9 @@ static_assert(sizeof(OctNode) == 64, "sp_octree_export promises 64 bytes per nod
 // device words of a build
 enum { kMetaStored = 0, kMetaNodes = 1, kMetaLeaves = 2, kMetaDepth = 3, kMetaError = 4, kMetaWords = 8 };
 
-__device__ __forceinline__ unsigned enc_f(float f) {  // order-preserving float -> uint
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
 __global__ void oct_init_kernel(unsigned* bbox, unsigned* meta) {
-    if (threadIdx.x < 3) bbox[threadIdx.x] = 0xffffffffu;
-    else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;
+    bbox_sentinel(bbox);
     if (threadIdx.x < kMetaWords) meta[threadIdx.x] = 0u;
-}
-// bbox[0..2] = min xyz, bbox[3..5] = max xyz (encoded), over the finite points.
-__global__ __launch_bounds__(kBlock) void oct_bbox_kernel(const float4* __restrict__ pts, unsigned n, unsigned* bbox) {
-    __shared__ unsigned red[kBlock / kWave][6];
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    const unsigned stride = gridDim.x * kBlock;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const float4 p = pts[i];
-        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-            const unsigned e[3] = {enc_f(p.x), enc_f(p.y), enc_f(p.z)};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], e[a]); mx[a] = max(mx[a], e[a]); }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o, 64));
-            mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o, 64));
-        }
-    const unsigned wave = threadIdx.x / kWave;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        unsigned v = red[0][threadIdx.x];
-        for (int w = 1; w < kBlock / kWave; ++w) v = threadIdx.x < 3 ? min(v, red[w][threadIdx.x]) : max(v, red[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&bbox[threadIdx.x], v);
-        else atomicMax(&bbox[threadIdx.x], v);
-    }
 }
 // root[0..2] / root[3..5]: the box of the root CELL (the points' box widened by max(1e-5, resolution / 2) per side,
 // octree.hpp:267-269); root[6]: its longest edge. Only the keys and the split rule use it.
@@ -99,7 +61,7 @@ __global__ void oct_root_kernel(const unsigned* __restrict__ bbox, float resolut
     const float eps = fmaxf(1e-5f, resolution * 0.5f);
     float edge = 0.0f;
     for (int a = 0; a < 3; ++a) {
-        const float lo = dec_f(bbox[a]) - eps, hi = dec_f(bbox[3 + a]) + eps;
+        const float lo = ordered_float(bbox[a]) - eps, hi = ordered_float(bbox[3 + a]) + eps;
         root[a] = lo;
         root[3 + a] = hi;
         edge = fmaxf(edge, hi - lo);
@@ -107,14 +69,6 @@ __global__ void oct_root_kernel(const unsigned* __restrict__ bbox, float resolut
     root[6] = edge;
 }
 
-__device__ __forceinline__ uint64_t spread21(uint64_t x) {  // 21 bits -> every third bit
-    x = (x | (x << 32)) & 0x001f00000000ffffull;
-    x = (x | (x << 16)) & 0x001f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
 __global__ __launch_bounds__(kBlock) void oct_key_kernel(const float4* __restrict__ pts, unsigned n, const float* __restrict__ root,
                                                          uint64_t* __restrict__ keys, unsigned* __restrict__ vals,
                                                          unsigned* __restrict__ meta) {
@@ -125,30 +79,14 @@ __global__ __launch_bounds__(kBlock) void oct_key_kernel(const float4* __restric
         uint64_t key = kOctInvalidKey;  // non-finite points: behind all others, in no leaf, never a neighbour
         ok = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
         if (ok) {
-            const float v[3] = {p.x, p.y, p.z};
-            uint64_t c[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float lo = root[a], ext = root[3 + a] - lo;
-                const float t = ext > 0.0f ? (v[a] - lo) / ext * 2097152.0f : 0.0f;
-                c[a] = (uint64_t)fminf(fmaxf(t, 0.0f), 2097151.0f);
-            }
-            key = spread21(c[0]) | (spread21(c[1]) << 1) | (spread21(c[2]) << 2);
+            const float box[6] = {root[0], root[1], root[2], root[3], root[4], root[5]};
+            key = morton_key_in_box(p.x, p.y, p.z, box, kOctCells);
         }
         keys[i] = key;
         vals[i] = i;
     }
     const unsigned long long m = __ballot(ok);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&meta[kMetaStored], (unsigned)__builtin_popcountll(m));
-}
-__global__ __launch_bounds__(kBlock) void oct_gather_kernel(const float4* __restrict__ pts, const unsigned* __restrict__ order,
-                                                            const unsigned* __restrict__ meta, float4* __restrict__ out) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= meta[kMetaStored]) return;
-    const unsigned src = order[i];
-    float4 p = pts[src];
-    p.w = __uint_as_float(src);
-    out[i] = p;
 }
 
 // Per stored point i (keys sorted): the depth L of its leaf, the first point of that leaf, the shallowest depth d0 at which i
@@ -273,9 +211,9 @@ __global__ __launch_bounds__(kBlock) void oct_leaf_box_kernel(const float4* __re
         const unsigned f = leaf_first[i];
         id = base[f] + (unsigned)((int)leaf_depth[i] - (int)first_depth[f]);
         const float4 p = spts[i];
-        e[0] = e[3] = enc_f(p.x);
-        e[1] = e[4] = enc_f(p.y);
-        e[2] = e[5] = enc_f(p.z);
+        e[0] = e[3] = ordered_bits(p.x);
+        e[1] = e[4] = ordered_bits(p.y);
+        e[2] = e[5] = ordered_bits(p.z);
     }
     const bool ok = act && id < node_cap;
     const unsigned id0 = (unsigned)__builtin_amdgcn_readfirstlane((int)id);
@@ -328,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void oct_finish_kernel(OctNode* __restrict_
     if (act) {
         unsigned* const box = reinterpret_cast<unsigned*>(nodes + j);
 #pragma unroll
-        for (int a = 0; a < 6; ++a) box[a] = __float_as_uint(dec_f(box[a]));
+        for (int a = 0; a < 6; ++a) box[a] = __float_as_uint(ordered_float(box[a]));
         leaf = nodes[j].is_leaf;
         depth = nodes[j].depth;
     }
@@ -588,14 +526,14 @@ extern "C" int sp_octree_create(const float* points, size_t n, float resolution,
     const unsigned n32 = (unsigned)n, cap32 = (unsigned)cap, g = div_up(n, kBlock), gn = div_up(cap, kBlock);
     // 1. the root cell and the keys
     oct_init_kernel<<<1, 64, 0, st>>>(bbox, meta);
-    oct_bbox_kernel<<<std::min(stream_grid(n, kBlock, 4), 256u), kBlock, 0, st>>>(pts, n32, bbox);
+    bbox_kernel<><<<std::min(stream_grid(n, kBlock, 4), 256u), kBlock, 0, st>>>(pts, n32, bbox);
     oct_root_kernel<<<1, 64, 0, st>>>(bbox, resolution, root);
     oct_key_kernel<<<g, kBlock, 0, st>>>(pts, n32, root, kin, vin, meta);
     // 2. key order
     bool in_b = false;
     if (radix_sort_pairs_u64(kin, kout, vin, vout, n, 64, b_tmp.p, tmp_bytes, &in_b, st) != SP_OK) return fail("[Octree::build] sort failed");
     if (!in_b) { kout = kin; vout = vin; }
-    oct_gather_kernel<<<g, kBlock, 0, st>>>(pts, vout, meta, t->pts);
+    gather_by_order_kernel<><<<g, kBlock, 0, st>>>(pts, vout, n32, t->pts, meta + kMetaStored);
     // 3. leaf depths, node numbers (pre-order), nodes
     oct_depth_kernel<<<g, kBlock, 0, st>>>(kout, n32, meta, root, resolution, (unsigned)max_points, b_ld.as<uint8_t>(),
                                           b_fd.as<uint8_t>(), b_lf.as<unsigned>(), b_base.as<unsigned>());

@@ -29,6 +29,7 @@
 
 #include "sp_common.h"
 #include "sp_internal.h"
+#include "sp_spatial.h"
 
 void sp_set_error(const char* msg);
 
@@ -101,8 +102,7 @@ __device__ __forceinline__ void load4(const T* __restrict__ a, size_t i, size_t 
 // Order-preserving u32 of a key (<= 0, never NaN); 0 is kept for "no key" (the smallest key, -inf, maps to 0x007fffff).
 __device__ __forceinline__ unsigned key_bits(float key) {
     key += 0.0f;  // -0 -> +0 (the reference's heap compares floats)
-    const unsigned b = __float_as_uint(key);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ordered_bits(key);
 }
 
 // ------------------------------------------------------------------------------------------------------------ weight check

@@ -101,6 +101,20 @@ int sp_internal_fps(int form, const float* points, size_t n, size_t sampling_num
  * ascending; column k of a vecs_out row is the eigenvector of eigenvalue k. All device pointers, rows 16-byte aligned. */
 int sp_internal_eigen3(const float* covs, size_t n, float* vals_out, float* vecs_out, void* stream);
 int sp_internal_inverse3(const float* mats, size_t n, float* out, void* stream);
+/* The pieces the search structures share (csrc/sp_spatial.h) on their own, for their tests; all pointers are device pointers,
+ * points are rows of 4 floats.
+ * sp_internal_bbox: the sentinel, then (n > 0) the shared bounding-box kernel on `workgroups` (1 .. 256) workgroups: six
+ * order-preserving words, min xyz | max xyz over the finite points. */
+int sp_internal_bbox(const float* points, size_t n, unsigned workgroups, uint32_t* box6_words_out, void* stream);
+/* The Morton key of every point in the box [lo3, hi3] with the BVH's cells per axis (mode 0) or the octree's (mode 1);
+ * ~0 for a non-finite point. */
+int sp_internal_morton_keys(const float* points, size_t n, const float* lo3, const float* hi3, int mode, uint64_t* keys_out,
+                            void* stream);
+/* sorted_insert<kcap, order>, one lane per row: the row's m candidates (d, idx: rows x m) in the given sequence into a list of
+ * (FLT_MAX, -1); the first k slots go to d_out / idx_out (rows x k). order 0: by distance, first arrival wins ties (kcap 1, 10,
+ * 100); 1: (distance, index) lexicographic (kcap 1, 10, 32). */
+int sp_internal_sorted_insert(int order, int kcap, int k, const float* d, const int32_t* idx, size_t rows, size_t m, float* d_out,
+                              int32_t* idx_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #include "sp_common.h"
 #include "sp_internal.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 #include "sp_wave_select.h"
 
 void sp_set_error(const char* msg);
@@ -88,7 +89,7 @@ __global__ void box_init_kernel(int32_t* box, bool eight = false) {  // eight: a
 template <class POL>
 __global__ __launch_bounds__(kBlock) void key_box_kernel(const float4* __restrict__ pts, unsigned n, const POL pol,
                                                          int32_t* __restrict__ box) {
-    int lo0 = INT32_MAX, lo1 = INT32_MAX, lo2 = INT32_MAX, hi0 = INT32_MIN, hi1 = INT32_MIN, hi2 = INT32_MIN;
+    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
     // four independent loads per trip (the loop is a latency chain otherwise: 13.8 us per 1M points with one)
     const unsigned stride = gridDim.x * kBlock;
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += 4 * stride) {
@@ -99,30 +100,12 @@ __global__ __launch_bounds__(kBlock) void key_box_kernel(const float4* __restric
         for (int u = 0; u < 4; ++u) {
             int c0, c1, c2;
             if (i + u * stride < n && pol.coords(p[u], c0, c1, c2)) {
-                lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
-                hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
+                lo[0] = min(lo[0], c0); lo[1] = min(lo[1], c1); lo[2] = min(lo[2], c2);
+                hi[0] = max(hi[0], c0); hi[1] = max(hi[1], c1); hi[2] = max(hi[2], c2);
             }
         }
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        lo0 = min(lo0, __shfl_xor(lo0, off)); lo1 = min(lo1, __shfl_xor(lo1, off)); lo2 = min(lo2, __shfl_xor(lo2, off));
-        hi0 = max(hi0, __shfl_xor(hi0, off)); hi1 = max(hi1, __shfl_xor(hi1, off)); hi2 = max(hi2, __shfl_xor(hi2, off));
-    }
-    // one set of atomics per workgroup (a few hundred per launch): wave results meet in LDS first
-    __shared__ int red[kBlock / kWave][6];
-    const unsigned wave = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        red[wave][0] = lo0; red[wave][1] = lo1; red[wave][2] = lo2;
-        red[wave][3] = hi0; red[wave][4] = hi1; red[wave][5] = hi2;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        int v = red[0][threadIdx.x];
-        for (unsigned w = 1; w < kBlock / kWave; ++w) v = threadIdx.x < 3 ? min(v, red[w][threadIdx.x]) : max(v, red[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&box[threadIdx.x], v);
-        else atomicMax(&box[threadIdx.x], v);
-    }
+    block_minmax3_atomic(lo, hi, box);  // one set of atomics per workgroup (a few hundred per launch)
 }
 
 // Compressed key: the position of the voxel in its bounding box, z-major like the 63-bit key, so the order is the same;
