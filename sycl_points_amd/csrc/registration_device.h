@@ -7,6 +7,7 @@
 
 #include "grid_device.h"
 #include "radix_sort.h"
+#include "sp_linearize.h"
 #include "sp_xchg.h"
 
 #include <type_traits>
@@ -228,10 +229,6 @@ __host__ __device__ inline void gn_update_impl(sp_linearized* lin, float* T, flo
     }
 }
 
-struct Sym3 {
-    float xx, xy, xz, yy, yz, zz;
-};
-
 __device__ __forceinline__ Sym3 load_sym(const float4* __restrict__ p) {
     const float4 a = p[0], b = p[1];
     return Sym3{a.x, a.y, a.z, a.w, b.x, b.y};
@@ -276,84 +273,18 @@ __device__ __forceinline__ Sym3 src_cov(const float* __restrict__ w) {
     return Sym3{w[3 * kWave], w[4 * kWave], w[5 * kWave], w[6 * kWave], w[7 * kWave], w[8 * kWave]};
 }
 
-// Linearisation of one correspondence (source point s with q = T s, winner nn, packed covariances) and accumulation.
-// P2D (linearize_point_to_distribution, factor.hpp:311-354): Ct is the target's information matrix M = inverse(Ct_raw)
-// (prepared once per target) and there is no source covariance: N = R^T M R, nothing to invert per point.
-// ERR_ONLY (calculate_gicp_error / calculate_point_to_distribution_error, factor.hpp:280-306, 356-373): only the robust
-// error and the count, into acc[0] — the K12 of a trial pose (sp_gicp_error_prepared).
+// Linearisation of one correspondence (source point s with q = T s, winner nn, packed covariances) and accumulation. The
+// algebra is linearize_terms (sp_linearize.h: one body for GICP / P2D / ERR_ONLY and every loss).
+// ERR_ONLY: only the robust error and the count, into acc[0] — the K12 of a trial pose (sp_gicp_error_prepared).
 template <int LOSS, bool P2D = false, bool ERR_ONLY = false, int NACC = kAcc - 1>
 __device__ __forceinline__ void fused_math(const FusedParams& P, const Rigid& T, const float4 s, float qx, float qy,
                                            float qz, const Nearest& nn, const Sym3& Cs, const Sym3& Ct,
                                            float (&acc)[NACC], unsigned& cnt) {
-    const float r0 = nn.x - qx, r1 = nn.y - qy, r2 = nn.z - qz;
-    // Source-frame form of factor.hpp:239-278. With S = skew(p), J = [R S | -R] and M = (Ct' + R Cs' R^T)^-1:
-    //   N := R^T M R = (Cs' + R^T Ct' R)^-1,  v := R^T r,  u := N v,  G := S N
-    //   H = [[-G S, G], [G^T, N]],   b = [u x p, -u],   e = v . u
-    // (same mathematics as J^T M J / J^T M r, about half the multiply-adds).
-    const float (&R)[3][3] = T.R;
-    float W[3][3];  // W = Ct' R
+    float t[NACC];
+    linearize_terms<LOSS, P2D, ERR_ONLY>(T, s.x, s.y, s.z, qx, qy, qz, nn.x, nn.y, nn.z, Cs, Ct, P.scale, t);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        W[0][j] = chain3(Ct.xx, R[0][j], Ct.xy, R[1][j], Ct.xz, R[2][j]);
-        W[1][j] = chain3(Ct.xy, R[0][j], Ct.yy, R[1][j], Ct.yz, R[2][j]);
-        W[2][j] = chain3(Ct.xz, R[0][j], Ct.yz, R[1][j], Ct.zz, R[2][j]);
-    }
-    // A = Cs' + R^T Ct' R (symmetric); P2D: R^T M R with no source term, and A is N itself
-    const float g00 = chain3(R[0][0], W[0][0], R[1][0], W[1][0], R[2][0], W[2][0]);
-    const float g01 = chain3(R[0][0], W[0][1], R[1][0], W[1][1], R[2][0], W[2][1]);
-    const float g02 = chain3(R[0][0], W[0][2], R[1][0], W[1][2], R[2][0], W[2][2]);
-    const float g11 = chain3(R[0][1], W[0][1], R[1][1], W[1][1], R[2][1], W[2][1]);
-    const float g12 = chain3(R[0][1], W[0][2], R[1][1], W[1][2], R[2][1], W[2][2]);
-    const float g22 = chain3(R[0][2], W[0][2], R[1][2], W[1][2], R[2][2], W[2][2]);
-    float n00, n01, n02, n11, n12, n22;
-    if constexpr (P2D) {
-        n00 = g00; n01 = g01; n02 = g02; n11 = g11; n12 = g12; n22 = g22;
-    } else {
-        const float a00 = g00 + Cs.xx, a01 = g01 + Cs.xy, a02 = g02 + Cs.xz, a11 = g11 + Cs.yy, a12 = g12 + Cs.yz,
-                    a22 = g22 + Cs.zz;
-        // symmetric inverse by the adjugate; Zero when |det| < 1e-6 (eigen_utils::inverse, eigen_utils.hpp:403-423;
-        // det is invariant under the rotation)
-        const float c00 = fmaf(a11, a22, -a12 * a12);
-        const float c01 = fmaf(a02, a12, -a01 * a22);
-        const float c02 = fmaf(a01, a12, -a02 * a11);
-        const float det = fmaf(a00, c00, fmaf(a01, c01, a02 * c02));
-        const float inv_det = fabsf(det) < 1e-6f ? 0.0f : 1.0f / det;
-        n00 = c00 * inv_det; n01 = c01 * inv_det; n02 = c02 * inv_det;
-        n11 = fmaf(a00, a22, -a02 * a02) * inv_det;
-        n12 = fmaf(a01, a02, -a00 * a12) * inv_det;
-        n22 = fmaf(a00, a11, -a01 * a01) * inv_det;
-    }
-    const float v0 = chain3(R[0][0], r0, R[1][0], r1, R[2][0], r2);
-    const float v1 = chain3(R[0][1], r0, R[1][1], r1, R[2][1], r2);
-    const float v2 = chain3(R[0][2], r0, R[1][2], r1, R[2][2], r2);
-    const float u0 = chain3(n00, v0, n01, v1, n02, v2);
-    const float u1 = chain3(n01, v0, n11, v1, n12, v2);
-    const float u2 = chain3(n02, v0, n12, v1, n22, v2);
-    const float sq = chain3(v0, u0, v1, u1, v2, u2);
-    const float rn = sqrtf(sq);
-    if constexpr (ERR_ONLY) {
-        acc[0] += robust_error<LOSS>(rn, P.scale);
-        ++cnt;
-    } else {
-    const float w = robust_weight<LOSS>(rn, P.scale);
-    const float px = s.x, py = s.y, pz = s.z;
-    // G = S N, rows: p x (columns of N)
-    const float g00 = fmaf(py, n02, -pz * n01), g01 = fmaf(py, n12, -pz * n11), g02 = fmaf(py, n22, -pz * n12);
-    const float g10 = fmaf(pz, n00, -px * n02), g11 = fmaf(pz, n01, -px * n12), g12 = fmaf(pz, n02, -px * n22);
-    const float g20 = fmaf(px, n01, -py * n00), g21 = fmaf(px, n11, -py * n01), g22 = fmaf(px, n12, -py * n02);
-    // H_rr = -G S (symmetric)
-    const float h00 = fmaf(g02, py, -g01 * pz), h01 = fmaf(g00, pz, -g02 * px), h02 = fmaf(g01, px, -g00 * py);
-    const float h11 = fmaf(g10, pz, -g12 * px), h12 = fmaf(g11, px, -g10 * py), h22 = fmaf(g21, px, -g20 * py);
-    acc[0] += w * h00; acc[1] += w * h01; acc[2] += w * h02; acc[3] += w * g00; acc[4] += w * g01; acc[5] += w * g02;
-    acc[6] += w * h11; acc[7] += w * h12; acc[8] += w * g10; acc[9] += w * g11; acc[10] += w * g12;
-    acc[11] += w * h22; acc[12] += w * g20; acc[13] += w * g21; acc[14] += w * g22;
-    acc[15] += w * n00; acc[16] += w * n01; acc[17] += w * n02; acc[18] += w * n11; acc[19] += w * n12; acc[20] += w * n22;
-    // b = [u x p, -u]
-    acc[21] += w * fmaf(u1, pz, -u2 * py); acc[22] += w * fmaf(u2, px, -u0 * pz); acc[23] += w * fmaf(u0, py, -u1 * px);
-    acc[24] += w * -u0; acc[25] += w * -u1; acc[26] += w * -u2;
-    acc[27] += robust_error<LOSS>(rn, P.scale);
+    for (int e = 0; e < NACC; ++e) acc[e] += t[e];
     ++cnt;
-    }
 }
 
 // The cached correspondence of a source point: 3 x float4 in SOURCE order (sp_gicp_source::ccache)
