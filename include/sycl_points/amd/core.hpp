@@ -924,33 +924,44 @@ struct PointCloudShared {
     double start_time_ms = 0.0, end_time_ms = 0.0;
 
     explicit PointCloudShared(const sycl_utils::DeviceQueue& q) : queue(q) { alloc(); }
-    PointCloudShared(const sycl_utils::DeviceQueue& q, const PointCloudCPU& cpu) : queue(q) {
+    PointCloudShared(const sycl_utils::DeviceQueue& q, const PointCloudCPU& cpu)
+        : queue(q), start_time_ms(cpu.start_time_ms), end_time_ms(cpu.end_time_ms) {
         alloc();
-        copy_in(*points, *cpu.points);
-        if (cpu.has_cov()) copy_in(*covs, *cpu.covs);
-        if (cpu.has_normal()) copy_in(*normals, *cpu.normals);
-        if (cpu.has_rgb()) copy_in(*rgb, *cpu.rgb);
-        if (cpu.has_intensity()) copy_in(*intensities, *cpu.intensities);
-        if (cpu.has_timestamps()) copy_in(*timestamp_offsets, *cpu.timestamp_offsets);
-        start_time_ms = cpu.start_time_ms;
-        end_time_ms = cpu.end_time_ms;
+        zip(*this, cpu, [&](auto& mine, const auto& theirs) {  // the attributes the CPU cloud carries: a row per point
+            if (theirs && theirs->size() == cpu.size()) copy_in(*mine, *theirs);
+        });
     }
     PointCloudShared(const PointCloudShared& o) : queue(o.queue), start_time_ms(o.start_time_ms), end_time_ms(o.end_time_ms) {
-        points = std::make_shared<PointContainerShared>(*o.points);  // deep copy (point_cloud.hpp:202-236)
-        covs = std::make_shared<CovarianceContainerShared>(*o.covs);
-        normals = std::make_shared<NormalContainerShared>(*o.normals);
-        rgb = std::make_shared<RGBContainerShared>(*o.rgb);
-        intensities = std::make_shared<IntensityContainerShared>(*o.intensities);
-        timestamp_offsets = std::make_shared<TimestampContainerShared>(*o.timestamp_offsets);
+        // deep copy (point_cloud.hpp:202-236)
+        zip(*this, o, [](auto& mine, const auto& theirs) { mine = std::make_shared<std::remove_reference_t<decltype(*mine)>>(*theirs); });
     }
     PointCloudShared& operator=(const PointCloudShared&) = default;  // shallow, as the reference's implicit operator=
 
     size_t size() const { return points->size(); }
-    bool has_cov() const { return covs && covs->size() == points->size() && points->size() > 0; }
-    bool has_normal() const { return normals && normals->size() == points->size() && points->size() > 0; }
-    bool has_rgb() const { return rgb && rgb->size() == points->size() && points->size() > 0; }
-    bool has_intensity() const { return intensities && intensities->size() == points->size() && points->size() > 0; }
-    bool has_timestamps() const { return timestamp_offsets && timestamp_offsets->size() == points->size() && points->size() > 0; }
+    /// whether container `c` holds a row for each of `n` points, n > 0; has(c): for each of this cloud's
+    template <class C>
+    static bool carries(const std::shared_ptr<C>& c, size_t n) { return c && c->size() == n && n > 0; }
+    template <class C>
+    bool has(const std::shared_ptr<C>& c) const { return carries(c, points->size()); }
+    bool has_cov() const { return has(covs); }
+    bool has_normal() const { return has(normals); }
+    bool has_rgb() const { return has(rgb); }
+    bool has_intensity() const { return has(intensities); }
+    bool has_timestamps() const { return has(timestamp_offsets); }
+    /// THE list of the cloud's attribute containers: f(a's container, b's container) for each of the six, in this order. Whatever
+    /// does the same thing to every attribute goes through here (or for_each_attribute), so that a new attribute is added in one
+    /// place; `a` and `b` are clouds of any kind with these members (PointCloudShared, PointCloudCPU; const or not).
+    template <class A, class B, class F>
+    static void zip(A& a, B& b, F&& f) {
+        f(a.points, b.points);
+        f(a.covs, b.covs);
+        f(a.normals, b.normals);
+        f(a.rgb, b.rgb);
+        f(a.intensities, b.intensities);
+        f(a.timestamp_offsets, b.timestamp_offsets);
+    }
+    template <class F>
+    void for_each_attribute(F&& f) { zip(*this, *this, [&](auto& c, auto&) { f(c); }); }
     PointType* points_ptr() const { return points->data(); }
     Covariance* covs_ptr() const { return covs->data(); }
     Normal* normals_ptr() const { return normals->data(); }
@@ -968,40 +979,34 @@ struct PointCloudShared {
     void reserve_timestamps(size_t n) const { timestamp_offsets->reserve(n); }
     /// points/point_cloud.hpp:307-317 (the timestamp base goes with the offsets)
     void clear() {
-        points->clear(); covs->clear(); normals->clear(); rgb->clear(); intensities->clear(); timestamp_offsets->clear();
+        for_each_attribute([](auto& c) { c->clear(); });
         start_time_ms = 0.0; end_time_ms = 0.0;
     }
     /// points/point_cloud.hpp:319-338: the points of `other` appended; an attribute survives when both clouds have it
     void extend(const PointCloudShared& other) {
-        const size_t org_size = size();
-        const bool cov = has_cov() && other.has_cov(), nrm = has_normal() && other.has_normal(), col = has_rgb() && other.has_rgb(),
-                   inten = has_intensity() && other.has_intensity();
-        if (cov) covs->append(*other.covs);
-        if (nrm) normals->append(*other.normals);
-        if (col) rgb->append(*other.rgb);
-        if (inten) intensities->append(*other.intensities);
-        points->append(*other.points);
+        const size_t org_size = size(), other_size = other.size();
+        zip(*this, other, [&](auto& mine, const auto& theirs) {
+            if (is(mine, timestamp_offsets)) return;  // (merge_timestamp_offsets below)
+            if (is(mine, points) || (carries(mine, org_size) && carries(theirs, other_size))) mine->append(*theirs);
+        });
         merge_timestamp_offsets(other, org_size);
     }
     /// points/point_cloud.hpp:340-366: the points [start_idx, end_idx) and their attributes removed
     void erase(size_t start_idx, size_t end_idx) {
-        auto cut = [&](auto& v) { v->erase(std::as_const(*v).begin() + (std::ptrdiff_t)start_idx, std::as_const(*v).begin() + (std::ptrdiff_t)end_idx); };
-        const bool cov = has_cov(), nrm = has_normal(), col = has_rgb(), inten = has_intensity(), ts = has_timestamps();
-        if (cov) cut(covs);
-        if (nrm) cut(normals);
-        if (col) cut(rgb);
-        if (inten) cut(intensities);
-        if (ts) {
-            cut(timestamp_offsets);
-            if (timestamp_offsets->empty()) {
-                start_time_ms = 0.0;
-                end_time_ms = 0.0;
-            } else {
-                const auto& h = timestamp_offsets->host();
-                end_time_ms = start_time_ms + static_cast<double>(*std::max_element(h.begin(), h.end()));
-            }
+        const size_t N = size();
+        const bool ts = has_timestamps();
+        for_each_attribute([&](auto& c) {
+            if (is(c, points) || carries(c, N))  // (sizes as they were on entry: the points are the first to go)
+                c->erase(std::as_const(*c).begin() + (std::ptrdiff_t)start_idx, std::as_const(*c).begin() + (std::ptrdiff_t)end_idx);
+        });
+        if (!ts) return;
+        if (timestamp_offsets->empty()) {
+            start_time_ms = 0.0;
+            end_time_ms = 0.0;
+        } else {
+            const auto& h = timestamp_offsets->host();
+            end_time_ms = start_time_ms + static_cast<double>(*std::max_element(h.begin(), h.end()));
         }
-        cut(points);
     }
     void operator+=(const PointCloudShared& pc) { extend(pc); }
 
@@ -1075,13 +1080,11 @@ public:
 
 private:
     void alloc() {
-        points = std::make_shared<PointContainerShared>(queue);
-        covs = std::make_shared<CovarianceContainerShared>(queue);
-        normals = std::make_shared<NormalContainerShared>(queue);
-        rgb = std::make_shared<RGBContainerShared>(queue);
-        intensities = std::make_shared<IntensityContainerShared>(queue);
-        timestamp_offsets = std::make_shared<TimestampContainerShared>(queue);
+        for_each_attribute([&](auto& c) { c = std::make_shared<std::remove_reference_t<decltype(*c)>>(queue); });
     }
+    /// whether `c` (as a lambda over zip sees it) is this cloud's member `member`
+    template <class C, class M>
+    static bool is(const C& c, const M& member) { return static_cast<const void*>(&c) == static_cast<const void*>(&member); }
     template <class S, class V>
     static void copy_in(S& dst, const V& src) {
         static_assert(sizeof(dst[0]) == sizeof(src[0]), "same element layout");

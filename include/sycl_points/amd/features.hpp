@@ -198,6 +198,94 @@ private:
     int32_t key_box_[6] = {0, 0, 0, 0, 0, 0};
     bool have_key_box_ = false;
 };
+/// What VoxelGrid::run and PolarGrid::run share: KeyBoxMemory's protocol around the class's two C calls. key_box(box6_dev) is its
+/// sp_*_key_box; downsample(tail...) its sp_*_downsample_report, handed the arguments both end with, from `rgb` on: the inputs the
+/// cloud has, the outputs sized for N rows at every launch. The outputs then get the V voxels the record (returned) reports.
+template <class KeyBoxFn, class DownsampleFn>
+std::array<int32_t, 8> downsample_run(KeyBoxMemory& boxes, hipStream_t st, size_t N, const RGBContainerShared* rgb,
+                                      const IntensityContainerShared* inten, const TimestampContainerShared* ts,
+                                      PointContainerShared& out_pts, RGBContainerShared* out_rgb, IntensityContainerShared* out_inten,
+                                      TimestampContainerShared* out_ts, KeyBoxFn&& key_box, DownsampleFn&& downsample) {
+    const std::array<int32_t, 8> h = boxes.run(N, st, key_box, [&](const int32_t* box, uint32_t* report, void* ws, size_t ws_bytes) {
+        downsample(rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr, inten ? inten->device_data() : nullptr,
+                   ts ? ts->device_data() : nullptr, reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
+                   rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
+                   inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr,
+                   static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), box, report, ws, ws_bytes, st);
+    });
+    const size_t V = static_cast<uint32_t>(h[0]);
+    out_pts.set_device_size(V);
+    if (rgb) out_rgb->set_device_size(V);
+    if (inten) out_inten->set_device_size(V);
+    if (ts) out_ts->set_device_size(V);
+    return h;
+}
+/// VoxelGrid's and PolarGrid's downsampling(cloud, result) around the class's run(points, N, the three inputs the cloud has, the
+/// four outputs): in place allowed; the result has no covariances and normals, and the cloud's times when it has timestamps.
+template <class RunFn>
+void downsample_cloud(const sycl_utils::DeviceQueue& queue, const PointCloudShared& cloud, PointCloudShared& result, RunFn&& run) {
+    const size_t N = cloud.size();
+    if (N == 0) { result.resize_points(0); return; }
+    const bool in_place = (&cloud == &result) || (cloud.points == result.points);
+    PointCloudShared tmp(queue);
+    PointCloudShared& out = in_place ? tmp : result;
+    run(cloud.points_device(), N, cloud.has_rgb() ? cloud.rgb.get() : nullptr,
+        cloud.has_intensity() ? cloud.intensities.get() : nullptr,
+        cloud.has_timestamps() ? cloud.timestamp_offsets.get() : nullptr, *out.points, out.rgb.get(),
+        out.intensities.get(), out.timestamp_offsets.get());
+    if (!cloud.has_rgb()) out.rgb->clear();
+    if (!cloud.has_intensity()) out.intensities->clear();
+    if (!cloud.has_timestamps()) out.timestamp_offsets->clear();
+    out.covs->clear();
+    out.normals->clear();
+    const double t0 = cloud.start_time_ms, t1 = cloud.end_time_ms;
+    const bool ts = cloud.has_timestamps();
+    if (in_place) PointCloudShared::zip(tmp, result, [](const auto& from, auto& to) { to = from; });
+    if (ts) { result.start_time_ms = t0; result.end_time_ms = t1; }
+}
+/// The rows of every attribute a cloud carries, on their way into fresh containers: the rows / dst / bytes table that
+/// sp_gather_rows_multi, sp_compact_by_flags_multi and sp_box_filter_compact_multi take, from the attributes `source` has (in
+/// PointCloudShared::zip's order: a new attribute is moved once it is listed there), each with a fresh container of `queue` sized
+/// for N rows. `points_src`, when given, is read in place of the device copy of the source's points. The caller launches and
+/// learns the count M; hand_over() then gives the containers away. Nothing here launches, synchronises or takes scratch memory.
+struct RowMover {
+    const void* rows[6];
+    void* dst[6];
+    size_t bytes[6];
+    int na = 0;
+    RowMover(const sycl_utils::DeviceQueue& queue, const PointCloudShared& source, size_t N, const PointType* points_src = nullptr)
+        : source_(source), fresh_(queue) {
+        int listed = 0;
+        PointCloudShared::zip(source, fresh_, [&](const auto& src, auto& out) {
+            const bool is_points = static_cast<const void*>(&src) == &source.points;
+            const int i = listed++;
+            if (!is_points && !source.has(src)) return;
+            moved_ |= 1u << i;
+            if (is_points && points_src) rows[na] = points_src;
+            else rows[na] = src->device_data();
+            dst[na] = out->device_data_for_write(N);
+            bytes[na] = sizeof(typename std::remove_reference_t<decltype(*src)>::value_type);
+            ++na;
+        });
+    }
+    /// The moved attributes, now M rows each, replace those of `output` (which may be the source). whole_cloud: the attributes the
+    /// source lacks become empty containers and the times are the source's; else those attributes and the times stay as they are.
+    void hand_over(PointCloudShared& output, size_t M, bool whole_cloud) {
+        const double t0 = source_.start_time_ms, t1 = source_.end_time_ms;
+        int listed = 0;
+        PointCloudShared::zip(fresh_, output, [&](auto& out, auto& to) {
+            const bool moved = (moved_ >> listed++) & 1u;
+            if (moved) out->set_device_size(M);
+            if (moved || whole_cloud) to = out;
+        });
+        if (whole_cloud) { output.start_time_ms = t0; output.end_time_ms = t1; }
+    }
+
+private:
+    const PointCloudShared& source_;
+    PointCloudShared fresh_;
+    unsigned moved_ = 0;  // bit i: zip's i-th attribute is in the table
+};
 }  // namespace detail
 
 // ================================================================================================ coordinate system
@@ -351,27 +439,7 @@ public:
         run(reinterpret_cast<const float*>(points.device_data()), N, nullptr, nullptr, nullptr, result, nullptr, nullptr, nullptr);
     }
     void downsampling(const PointCloudShared& cloud, PointCloudShared& result) {
-        const size_t N = cloud.size();
-        if (N == 0) { result.resize_points(0); return; }
-        const bool in_place = (&cloud == &result) || (cloud.points == result.points);
-        PointCloudShared tmp(queue_);
-        PointCloudShared& out = in_place ? tmp : result;
-        run(cloud.points_device(), N, cloud.has_rgb() ? cloud.rgb.get() : nullptr,
-            cloud.has_intensity() ? cloud.intensities.get() : nullptr,
-            cloud.has_timestamps() ? cloud.timestamp_offsets.get() : nullptr, *out.points, out.rgb.get(),
-            out.intensities.get(), out.timestamp_offsets.get());
-        if (!cloud.has_rgb()) out.rgb->clear();
-        if (!cloud.has_intensity()) out.intensities->clear();
-        if (!cloud.has_timestamps()) out.timestamp_offsets->clear();
-        out.covs->clear();
-        out.normals->clear();
-        const double t0 = cloud.start_time_ms, t1 = cloud.end_time_ms;
-        const bool ts = cloud.has_timestamps();
-        if (in_place) {
-            result.points = tmp.points; result.rgb = tmp.rgb; result.intensities = tmp.intensities;
-            result.timestamp_offsets = tmp.timestamp_offsets; result.covs = tmp.covs; result.normals = tmp.normals;
-        }
-        if (ts) { result.start_time_ms = t0; result.end_time_ms = t1; }
+        detail::downsample_cloud(queue_, cloud, result, [this](auto&&... io) { run(io...); });
     }
 
 private:
@@ -379,20 +447,11 @@ private:
              const TimestampContainerShared* ts, PointContainerShared& out_pts, RGBContainerShared* out_rgb,
              IntensityContainerShared* out_inten, TimestampContainerShared* out_ts) {
         hipStream_t st = queue_.stream();
-        const std::array<int32_t, 8> h = boxes_.run(
-            N, st, [&](int32_t* box6_dev) { throw_on_error(sp_voxel_key_box(pts, N, voxel_size_inv_, box6_dev, st)); },
-            [&](const int32_t* box, uint32_t* report, void* ws, size_t ws_bytes) {
-                throw_on_error(sp_voxel_downsample_report(
-                    pts, N, voxel_size_inv_, min_voxel_count_, rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr,
-                    inten ? inten->device_data() : nullptr, ts ? ts->device_data() : nullptr,
-                    reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
-                    rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
-                    inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr, nullptr,
-                    nullptr, box, report, ws, ws_bytes, st));
-            });
-        const size_t V = static_cast<uint32_t>(h[0]);
-        out_pts.set_device_size(V);
-        if (V > 0 && h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7]) {
+        const std::array<int32_t, 8> h = detail::downsample_run(
+            boxes_, st, N, rgb, inten, ts, out_pts, out_rgb, out_inten, out_ts,
+            [&](int32_t* box6_dev) { throw_on_error(sp_voxel_key_box(pts, N, voxel_size_inv_, box6_dev, st)); },
+            [&](auto... tail) { throw_on_error(sp_voxel_downsample_report(pts, N, voxel_size_inv_, min_voxel_count_, tail...)); });
+        if (h[0] != 0 && h[2] <= h[5] && h[3] <= h[6] && h[4] <= h[7]) {
             // every output point is the mean of points of one voxel, so it lies in that voxel; the voxels' key box is h[2..7]
             // (coordinates offset by 2^20, compute_voxel_bit): the cloud's bounding box, a voxel wider on every side against the
             // rounding of floor(p / size), for whoever builds a grid on the cloud next
@@ -403,9 +462,6 @@ private:
             }
             ::sycl_points::detail::BoundsHints::put(out_pts.generation(), box);
         }
-        if (rgb) out_rgb->set_device_size(V);
-        if (inten) out_inten->set_device_size(V);
-        if (ts) out_ts->set_device_size(V);
     }
     sycl_utils::DeviceQueue queue_;
     float voxel_size_ = 1.0f, voxel_size_inv_ = 1.0f;
@@ -475,27 +531,7 @@ public:
     }
     /// polar_downsampling.hpp:217-236 (in place allowed; start / end time kept when the cloud has timestamps)
     void downsampling(const PointCloudShared& cloud, PointCloudShared& result) {
-        const size_t N = cloud.size();
-        if (N == 0) { result.resize_points(0); return; }
-        const bool in_place = (&cloud == &result) || (cloud.points == result.points);
-        PointCloudShared tmp(queue_);
-        PointCloudShared& out = in_place ? tmp : result;
-        run(cloud.points_device(), N, cloud.has_rgb() ? cloud.rgb.get() : nullptr,
-            cloud.has_intensity() ? cloud.intensities.get() : nullptr,
-            cloud.has_timestamps() ? cloud.timestamp_offsets.get() : nullptr, *out.points, out.rgb.get(), out.intensities.get(),
-            out.timestamp_offsets.get());
-        if (!cloud.has_rgb()) out.rgb->clear();
-        if (!cloud.has_intensity()) out.intensities->clear();
-        if (!cloud.has_timestamps()) out.timestamp_offsets->clear();
-        out.covs->clear();
-        out.normals->clear();
-        const double t0 = cloud.start_time_ms, t1 = cloud.end_time_ms;
-        const bool ts = cloud.has_timestamps();
-        if (in_place) {
-            result.points = tmp.points; result.rgb = tmp.rgb; result.intensities = tmp.intensities;
-            result.timestamp_offsets = tmp.timestamp_offsets; result.covs = tmp.covs; result.normals = tmp.normals;
-        }
-        if (ts) { result.start_time_ms = t0; result.end_time_ms = t1; }
+        detail::downsample_cloud(queue_, cloud, result, [this](auto&&... io) { run(io...); });
     }
 
 private:
@@ -504,26 +540,16 @@ private:
              IntensityContainerShared* out_inten, TimestampContainerShared* out_ts) {
         hipStream_t st = queue_.stream();
         const int coord = static_cast<int>(coord_);
-        const std::array<int32_t, 8> h = boxes_.run(
-            N, st,
+        detail::downsample_run(
+            boxes_, st, N, rgb, inten, ts, out_pts, out_rgb, out_inten, out_ts,
             [&](int32_t* box6_dev) {
                 throw_on_error(sp_polar_key_box(pts, N, coord, distance_voxel_size_inv_, elevation_voxel_size_inv_,
                                                 azimuth_voxel_size_inv_, box6_dev, st));
             },
-            [&](const int32_t* box, uint32_t* report, void* ws, size_t ws_bytes) {
-                throw_on_error(sp_polar_downsample_report(
-                    pts, N, coord, distance_voxel_size_inv_, elevation_voxel_size_inv_, azimuth_voxel_size_inv_, min_voxel_count_,
-                    rgb ? reinterpret_cast<const float*>(rgb->device_data()) : nullptr, inten ? inten->device_data() : nullptr,
-                    ts ? ts->device_data() : nullptr, reinterpret_cast<float*>(out_pts.device_data_for_write(N)),
-                    rgb ? reinterpret_cast<float*>(out_rgb->device_data_for_write(N)) : nullptr,
-                    inten ? out_inten->device_data_for_write(N) : nullptr, ts ? out_ts->device_data_for_write(N) : nullptr, nullptr,
-                    nullptr, box, report, ws, ws_bytes, st));
+            [&](auto... tail) {
+                throw_on_error(sp_polar_downsample_report(pts, N, coord, distance_voxel_size_inv_, elevation_voxel_size_inv_,
+                                                          azimuth_voxel_size_inv_, min_voxel_count_, tail...));
             });
-        const size_t V = static_cast<uint32_t>(h[0]);
-        out_pts.set_device_size(V);
-        if (rgb) out_rgb->set_device_size(V);
-        if (inten) out_inten->set_device_size(V);
-        if (ts) out_ts->set_device_size(V);
     }
     sycl_utils::DeviceQueue queue_;
     float distance_voxel_size_ = 1.0f, elevation_voxel_size_ = 1.0f, azimuth_voxel_size_ = 1.0f;
@@ -576,7 +602,7 @@ private:
 class PreprocessFilter {
 public:
     using Ptr = std::shared_ptr<PreprocessFilter>;
-    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), by_flags_(queue), mt_(1234), fps_mt_(1234), weighted_mt_(1234), mixed_mt_(1234) {
+    explicit PreprocessFilter(const sycl_utils::DeviceQueue& queue) : queue_(queue), mt_(1234), fps_mt_(1234), weighted_mt_(1234), mixed_mt_(1234) {
         flags_ = std::make_shared<shared_vector<uint8_t>>(queue);
     }
     /// preprocess_filter.hpp:46-51: every sampling operator has a generator of its own; the call seeds them all
@@ -796,66 +822,26 @@ private:
     /// output = the rows `picked` of every attribute of source (sp_gather_rows_multi)
     void gather_rows(const PointCloudShared& source, PointCloudShared& output, const std::vector<uint32_t>& picked) {
         const size_t M = picked.size();
-        PointCloudShared out(queue_);
-        const void* rows[6];
-        void* dst[6];
-        size_t bytes[6];
-        int na = 0;
-        auto add = [&](auto& src_vec, auto& dst_vec) {
-            using T = typename std::remove_reference_t<decltype(src_vec)>::value_type;
-            rows[na] = src_vec.device_data();
-            dst[na] = dst_vec.device_data_for_write(M);
-            bytes[na] = sizeof(T);
-            ++na;
-        };
-        add(*source.points, *out.points);
-        if (source.has_cov()) add(*source.covs, *out.covs);
-        if (source.has_normal()) add(*source.normals, *out.normals);
-        if (source.has_rgb()) add(*source.rgb, *out.rgb);
-        if (source.has_intensity()) add(*source.intensities, *out.intensities);
-        if (source.has_timestamps()) add(*source.timestamp_offsets, *out.timestamp_offsets);
+        detail::RowMover mv(queue_, source, M);
         hipStream_t st = queue_.stream();
         size_t got = 0;
         void* idx = ::sycl_points::detail::DeviceBufferCache::acquire(std::max<size_t>(M, 1) * 4, &got, st);
         hipError_t e = hipMemcpyAsync(idx, picked.data(), M * 4, hipMemcpyHostToDevice, st);  // (pageable: staged before the call returns)
         int rc = SP_OK;
-        if (e == hipSuccess) rc = sp_gather_rows_multi(rows, bytes, dst, na, static_cast<const uint32_t*>(idx), M, st);
+        if (e == hipSuccess) rc = sp_gather_rows_multi(mv.rows, mv.bytes, mv.dst, mv.na, static_cast<const uint32_t*>(idx), M, st);
         ::sycl_points::detail::DeviceBufferCache::release(idx, got, st);
         hip_check(e, "H2D");
         throw_on_error(rc);
-        const double t0 = source.start_time_ms, t1 = source.end_time_ms;
-        output.points = out.points; output.covs = out.covs; output.normals = out.normals; output.rgb = out.rgb;
-        output.intensities = out.intensities; output.timestamp_offsets = out.timestamp_offsets;
-        output.start_time_ms = t0; output.end_time_ms = t1;
+        mv.hand_over(output, M, /*whole_cloud=*/true);
     }
     void apply_flags(const PointCloudShared& source, PointCloudShared& output, size_t known_count = SIZE_MAX) {
         // FilterByFlags over every attribute the cloud carries (preprocess_operator_base): one scan of the flags, one
         // compaction launch per attribute, written straight into the new containers (no staging copy), ONE count read-back.
         const size_t N = source.size();
-        PointCloudShared out(queue_);
-        const void* rows[6];
-        void* dst[6];
-        size_t bytes[6];
-        int na = 0;
-        auto add = [&](auto& src_vec, auto& dst_vec) {
-            using T = typename std::remove_reference_t<decltype(src_vec)>::value_type;
-            rows[na] = src_vec.device_data();
-            dst[na] = dst_vec.device_data_for_write(N);
-            bytes[na] = sizeof(T);
-            ++na;
-        };
         // the box filter reads the points once: straight out of the pinned host copy when that is the current one (a fresh scan)
         bool pts_in_place = false;
         const PointType* const pts = box_.on ? source.points->device_readable_once(&pts_in_place) : source.points->device_data();
-        rows[na] = pts;
-        dst[na] = out.points->device_data_for_write(N);
-        bytes[na] = sizeof(PointType);
-        ++na;
-        if (source.has_cov()) add(*source.covs, *out.covs);
-        if (source.has_normal()) add(*source.normals, *out.normals);
-        if (source.has_rgb()) add(*source.rgb, *out.rgb);
-        if (source.has_intensity()) add(*source.intensities, *out.intensities);
-        if (source.has_timestamps()) add(*source.timestamp_offsets, *out.timestamp_offsets);
+        detail::RowMover mv(queue_, source, N, pts);
         const size_t ws_bytes = sp_compact_workspace_bytes(N);
         hipStream_t st = queue_.stream();
         hipStream_t ws_release_stream = nullptr;
@@ -875,32 +861,22 @@ private:
         uint32_t* const count_dev = poll ? mapped.dev : static_cast<uint32_t*>(count.p);
         if (poll) mapped.arm();
         if (box_.on) {
-            const int rc = sp_box_filter_compact_multi(reinterpret_cast<const float*>(pts), N, box_.min_distance, box_.max_distance, rows,
-                                                       bytes, dst, na, flags_->device_data_for_write(N), nullptr, count_dev, ws.p,
-                                                       ws_bytes, st);
+            const int rc = sp_box_filter_compact_multi(reinterpret_cast<const float*>(pts), N, box_.min_distance, box_.max_distance,
+                                                       mv.rows, mv.bytes, mv.dst, mv.na, flags_->device_data_for_write(N), nullptr,
+                                                       count_dev, ws.p, ws_bytes, st);
             if (pts_in_place) source.points->host_read_enqueued(st);
             throw_on_error(rc);
         } else
-            throw_on_error(sp_compact_by_flags_multi(rows, bytes, dst, na, N, flags_->device_data(), nullptr, count_dev, ws.p, ws_bytes,
-                                                     st));
+            throw_on_error(sp_compact_by_flags_multi(mv.rows, mv.bytes, mv.dst, mv.na, N, flags_->device_data(), nullptr, count_dev,
+                                                     ws.p, ws_bytes, st));
         size_t M = known_count;
         if (poll) { M = mapped.wait(st); ws_release_stream = st; }  // (nothing synchronised: the scratch goes back behind the stream's work)
         else if (known_count == SIZE_MAX) M = detail::read_u32(count.p, st);  // (synchronises: the scratch is idle when it leaves scope)
         else ws_release_stream = st;
-        out.points->set_device_size(M);
-        if (source.has_cov()) out.covs->set_device_size(M);
-        if (source.has_normal()) out.normals->set_device_size(M);
-        if (source.has_rgb()) out.rgb->set_device_size(M);
-        if (source.has_intensity()) out.intensities->set_device_size(M);
-        if (source.has_timestamps()) out.timestamp_offsets->set_device_size(M);
-        const double t0 = source.start_time_ms, t1 = source.end_time_ms;
-        output.points = out.points; output.covs = out.covs; output.normals = out.normals; output.rgb = out.rgb;
-        output.intensities = out.intensities; output.timestamp_offsets = out.timestamp_offsets;
-        output.start_time_ms = t0; output.end_time_ms = t1;
+        mv.hand_over(output, M, /*whole_cloud=*/true);
     }
     struct BoxArgs { bool on = false; float min_distance = 0.0f, max_distance = 0.0f; } box_;  // apply_flags makes the flags itself
     sycl_utils::DeviceQueue queue_;
-    FilterByFlags by_flags_;
     shared_vector_ptr<uint8_t> flags_;
     std::mt19937 mt_;
     std::mt19937 fps_mt_;  // farthest point sampling's own generator (preprocess_filter.hpp:46-51)
@@ -978,37 +954,13 @@ private:
     void filter_by_flags(PointCloudShared& data) {
         const size_t N = data.size();
         hipStream_t st = queue_.stream();
-        const void* rows[6];
-        void* dst[6];
-        size_t bytes[6];
-        int na = 0;
-        auto add = [&](auto& src_ptr) {
-            using V = std::remove_reference_t<decltype(*src_ptr)>;
-            auto out = std::make_shared<V>(queue_);
-            rows[na] = src_ptr->device_data();
-            dst[na] = out->device_data_for_write(N);
-            bytes[na] = sizeof(typename V::value_type);
-            ++na;
-            return out;
-        };
-        const auto covs = data.has_cov() ? add(data.covs) : nullptr;
-        const auto normals = data.has_normal() ? add(data.normals) : nullptr;
-        const auto rgb = data.has_rgb() ? add(data.rgb) : nullptr;
-        const auto intensities = data.has_intensity() ? add(data.intensities) : nullptr;
-        const auto stamps = data.has_timestamps() ? add(data.timestamp_offsets) : nullptr;
-        const auto points = add(data.points);
+        detail::RowMover mv(queue_, data, N);
         const size_t ws_bytes = sp_compact_workspace_bytes(N);
         detail::DeviceScratch ws(ws_bytes, st), count(4, st);
-        throw_on_error(sp_compact_by_flags_multi(rows, bytes, dst, na, N, flags_->device_data(), indices_->device_data_for_write(N),
-                                                 static_cast<uint32_t*>(count.p), ws.p, ws_bytes, st));
+        throw_on_error(sp_compact_by_flags_multi(mv.rows, mv.bytes, mv.dst, mv.na, N, flags_->device_data(),
+                                                 indices_->device_data_for_write(N), static_cast<uint32_t*>(count.p), ws.p, ws_bytes, st));
         const size_t M = detail::read_u32(count.p, st);
-        auto take = [&](auto& dst_ptr, const auto& out) {
-            if (!out) return;
-            out->set_device_size(M);
-            dst_ptr = out;
-        };
-        take(data.covs, covs); take(data.normals, normals); take(data.rgb, rgb); take(data.intensities, intensities);
-        take(data.timestamp_offsets, stamps); take(data.points, points);
+        mv.hand_over(data, M, /*whole_cloud=*/false);  // (the attributes the cloud lacks and its times stay)
     }
 
     sycl_utils::DeviceQueue queue_;

@@ -57,6 +57,10 @@ def identity():
     return np.eye(4, dtype=np.float32)
 
 
+# THE list of a cloud's attribute tensors (the facade's PointCloudShared::zip): what treats every attribute alike iterates it
+_CLOUD_ATTRS = ("points", "covs", "normals", "rgb", "intensities", "timestamp_offsets")
+
+
 class PointCloudShared:
     """points/point_cloud.hpp:73-476 — attribute containers resident in HBM. covs are (N,16) column-major 4x4."""
 
@@ -83,10 +87,8 @@ class PointCloudShared:
 
     def reordered(self, perm):
         """A copy with every attribute gathered through `perm` (e.g. GridKNN.order())."""
-        g = lambda t: None if t is None else t[perm].contiguous()
-        return PointCloudShared(g(self.points), covs=g(self.covs), normals=g(self.normals), rgb=g(self.rgb),
-                                intensities=g(self.intensities), timestamp_offsets=g(self.timestamp_offsets),
-                                device=self.device)
+        return PointCloudShared(device=self.device, **{k: t[perm].contiguous() for k in _CLOUD_ATTRS
+                                                       if (t := getattr(self, k)) is not None})
 
     def has_cov(self):
         return self.covs is not None and self.covs.shape[0] == self.points.shape[0]
@@ -1114,6 +1116,32 @@ def _normals_or_covs(cloud):
     return nrm, covs
 
 
+def _compact_cloud_by_flags(cloud, flags, want_indices):
+    """Every attribute a (non-empty) cloud carries through one sp_compact_by_flags_multi: the new tensors by name, the count and,
+    if wanted, every point's new index (-1: removed). One count is read back."""
+    L = _lib.lib()
+    n = cloud.size()
+    names = [k for k in _CLOUD_ATTRS if (t := getattr(cloud, k)) is not None and t.shape[0] == n]
+    src = [getattr(cloud, k) for k in names]
+    for t in src:
+        if not (t.is_cuda and t.is_contiguous()):
+            raise SpError(1, "expected contiguous CUDA tensors")
+    dst = [torch.empty_like(t) for t in src]
+    na = len(src)
+    rows = (C.c_void_p * na)(*[t.data_ptr() for t in src])
+    rows_out = (C.c_void_p * na)(*[t.data_ptr() for t in dst])
+    row_bytes = (C.c_size_t * na)(*[t.element_size() * (t.numel() // n) for t in src])
+    dev = cloud.points.device
+    idx = torch.empty(n, dtype=torch.int32, device=dev) if want_indices else None
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = L.sp_compact_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.sp_compact_by_flags_multi(rows, row_bytes, rows_out, na, n, _ptr(flags), _ptr(idx), _ptr(n_out), _ptr(ws), nbytes,
+                                      _stream()))
+    m = int(n_out.item())
+    return {k: t[:m] for k, t in zip(names, dst)}, m, idx
+
+
 def angle_incidence_filter(cloud, min_angle, max_angle, return_flags=False):
     """PreprocessFilter::angle_incidence_filter (filter/preprocess_filter.hpp:147-160, preprocess_operator/
     angle_incidence_filter_operator.hpp:23-110): a new cloud with the points whose angle of incidence (between the ray from the
@@ -1128,25 +1156,8 @@ def angle_incidence_filter(cloud, min_angle, max_angle, return_flags=False):
     nrm, covs = _normals_or_covs(cloud)
     flags = torch.empty(n, dtype=torch.uint8, device=p.device)
     check(L.sp_angle_incidence_flags(_ptr(p), _ptr(nrm), _ptr(covs), n, min_angle, max_angle, _ptr(flags), _stream()))
-    names = [k for k, has in (("points", True), ("covs", cloud.has_cov()), ("normals", cloud.has_normal()), ("rgb", cloud.has_rgb()),
-                              ("intensities", cloud.has_intensity()), ("timestamp_offsets", cloud.has_timestamps())) if has]
-    src = [getattr(cloud, k) for k in names]
-    for t in src:
-        if not (t.is_cuda and t.is_contiguous()):
-            raise SpError(1, "expected contiguous CUDA tensors")
-    dst = [torch.empty_like(t) for t in src]
-    na = len(src)
-    rows = (C.c_void_p * na)(*[t.data_ptr() for t in src])
-    rows_out = (C.c_void_p * na)(*[t.data_ptr() for t in dst])
-    row_bytes = (C.c_size_t * na)(*[t.element_size() * (t.numel() // n) for t in src])
-    n_out = torch.zeros(1, dtype=torch.int32, device=p.device)
-    nbytes = L.sp_compact_workspace_bytes(n)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
-    check(L.sp_compact_by_flags_multi(rows, row_bytes, rows_out, na, n, _ptr(flags), None, _ptr(n_out), _ptr(ws), nbytes, _stream()))
-    m = int(n_out.item())
-    out = PointCloudShared(device=p.device)
-    for k, t in zip(names, dst):
-        setattr(out, k, t[:m])
+    moved, _, _ = _compact_cloud_by_flags(cloud, flags, False)
+    out = PointCloudShared(device=p.device, **moved)
     for k in ("start_time_ms", "end_time_ms"):
         if hasattr(cloud, k):
             setattr(out, k, getattr(cloud, k))
@@ -1223,8 +1234,6 @@ class OutlierRemoval:
     neighbour distances are averaged and compared as they are, radius() compares the squared distance with `radius` itself
     (:178-188), and too few points print its message and leave the cloud untouched."""
 
-    _ATTRS = ("covs", "normals", "rgb", "intensities", "timestamp_offsets", "points")  # the reference's order (:224-241)
-
     def __init__(self):
         self.neighbors = KNNResult()
         self.flags = None
@@ -1277,30 +1286,9 @@ class OutlierRemoval:
         return self.indices
 
     def _filter_by_flags(self, cloud):
-        L = _lib.lib()
-        n = cloud.size()
-        has = dict(points=True, covs=cloud.has_cov(), normals=cloud.has_normal(), rgb=cloud.has_rgb(),
-                   intensities=cloud.has_intensity(), timestamp_offsets=cloud.has_timestamps())
-        names = [k for k in OutlierRemoval._ATTRS if has[k]]
-        src = [getattr(cloud, k) for k in names]
-        for t in src:
-            if not (t.is_cuda and t.is_contiguous()):
-                raise SpError(1, "expected contiguous CUDA tensors")
-        dst = [torch.empty_like(t) for t in src]
-        na = len(src)
-        rows = (C.c_void_p * na)(*[t.data_ptr() for t in src])
-        rows_out = (C.c_void_p * na)(*[t.data_ptr() for t in dst])
-        row_bytes = (C.c_size_t * na)(*[t.element_size() * (t.numel() // n) for t in src])
-        dev = cloud.points.device
-        self.indices = torch.empty(n, dtype=torch.int32, device=dev)
-        n_out = torch.zeros(1, dtype=torch.int32, device=dev)
-        nbytes = L.sp_compact_workspace_bytes(n)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        check(L.sp_compact_by_flags_multi(rows, row_bytes, rows_out, na, n, _ptr(self.flags), _ptr(self.indices), _ptr(n_out),
-                                          _ptr(ws), nbytes, _stream()))
-        m = int(n_out.item())
-        for k, t in zip(names, dst):
-            setattr(cloud, k, t[:m])
+        moved, _, self.indices = _compact_cloud_by_flags(cloud, self.flags, True)
+        for k, t in moved.items():  # (the attributes the cloud lacks stay as they are)
+            setattr(cloud, k, t)
 
 
 @dataclass
