@@ -71,7 +71,8 @@ int sp_knn_bruteforce_set_pass_a(int valu);
  *   synchronises. leaf_threshold default in the reference is 16.
  * sp_kdtree_search: KDTree::knn_search_async (kdtree.hpp:203-224, 424-562, kernel K2): neighbours of transT*q,
  *   traversal order, tie rule (first visited wins) and the 16-entry far stack of the reference;
- *   k <= 100 else SP_ERR_RUNTIME ("`k` is too large", kdtree.hpp:221-223).
+ *   k <= 100 else SP_ERR_RUNTIME ("`k` is too large", kdtree.hpp:221-223). A query with a non-finite coordinate gets a row
+ *   of (-1, FLT_MAX), where the reference's tree writes NaN distances for k > 1.
  * sp_kdtree_radius_search: KDTree::radius_search_async (kdtree.hpp:251-280, 574-719, kernel K3).
  * sp_kdtree_remove_by_flags: KDTree::remove_nodes_by_flags (kdtree.hpp:282-284, 721-765, kernel K4);
  *   flags 1 = keep, 0 = remove; new_indices[p] must be >= 0 for kept points (filter_by_flags.hpp:97-99). */
@@ -273,6 +274,8 @@ int sp_octree_export(const sp_octree* octree, void* nodes_out, int32_t* point_id
  *   sp_knn_tree_search   as sp_kdtree_search, k <= 100 (SP_ERR_RUNTIME). own_cloud != 0: the caller states that the queries are
  *                        the points the tree was built on, unchanged since; it counts only while nothing was removed and
  *                        without a transform. transT NULL or a host identity: no transform; a device transT always is one.
+ *                        A query with a non-finite coordinate gets a row of (-1, FLT_MAX) from whichever structure answers,
+ *                        where the reference's tree writes NaN distances for k > 1.
  *   sp_knn_tree_radius_search / sp_knn_tree_remove_by_flags  as sp_kdtree_*; a removal reaches every structure, also one built
  *                        later, ends the own-cloud, grid and brute-force shortcuts, and synchronises.
  *   sp_knn_tree_set_reference_order  != 0: every search uses the reference's tree (its first-visited tie order).

@@ -130,6 +130,11 @@ bool own_cloud_of(const sp_knn_tree* t, size_t nq, bool transform, int own_cloud
 
 extern "C" int sp_knn_tree_create(const float* points, size_t n, size_t leaf_threshold, void* stream, sp_knn_tree** out) {
     if (!out) return SP_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (leaf_threshold == 0 || leaf_threshold > 4096) {  // (here, not when the reference's tree is first needed: as sp_kdtree_create)
+        sp_set_error("[KDTree::build] leaf_threshold must be in [1, 4096]");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
     hipStream_t st = sp::as_stream(stream);
     sp_knn_tree* t = new sp_knn_tree();
     t->n = n;
