@@ -145,11 +145,48 @@ def knn_search_bruteforce(queries, targets, k):
     return res
 
 
+def _trans_arg(transT):
+    """-> (pointer, on_device flag, keepalive). Accepts None, a 4x4 host matrix, or a 16-float CUDA tensor
+    (column-major) for device-resident loops."""
+    if transT is None:
+        return None, 0, None
+    if isinstance(transT, torch.Tensor) and transT.is_cuda:
+        if transT.numel() != 16 or transT.dtype != torch.float32:
+            raise SpError(1, "device transT must be 16 float32 (column-major)")
+        return _ptr(transT), 1, transT
+    a = _T16(transT.cpu().numpy() if isinstance(transT, torch.Tensor) else transT)
+    return a.ctypes.data_as(C.c_void_p), 0, a
+
+
 class KNNBase:
     """algorithms/knn/knn.hpp:14-61 — the operator boundary Registration::align sits on."""
 
     def knn_search_async(self, queries, k, result, transT=None):
         raise NotImplementedError
+
+    def _knn_search(self, entry, limit, too_large, queries, k, result, transT, own=()):
+        """knn_search_async of a structure behind the C ABI: `entry` is its sp_*_search, `limit` its longest list and `too_large`
+        its own error text; `own`: what sp_knn_tree_search takes between the pose and the outputs."""
+        q = _dev_f32(_points_of(queries), 4)
+        if k > limit:
+            raise SpError(2, too_large)
+        result.resize(q.shape[0], k, q.device)
+        if q.shape[0] == 0:
+            return
+        tp, on_dev, keep = _trans_arg(transT)
+        check(entry(self._h, _ptr(q), q.shape[0], k, tp, on_dev, *own, _ptr(result.indices), _ptr(result.distances), _stream()))
+
+    def _radius_search(self, entry, limit, too_large, queries, max_k, radius, result, transT):
+        """radius_search_async likewise, over sp_*_radius_search."""
+        q = _dev_f32(_points_of(queries), 4)
+        if max_k > limit:
+            raise SpError(2, too_large)
+        if q.shape[0] == 0 or max_k == 0:
+            result.resize(0, 0, q.device)
+            return
+        result.resize(q.shape[0], max_k, q.device)
+        tp, on_dev, keep = _trans_arg(transT)
+        check(entry(self._h, _ptr(q), q.shape[0], max_k, radius, tp, on_dev, _ptr(result.indices), _ptr(result.distances), _stream()))
 
     def knn_search(self, queries, k, transT=None):
         r = KNNResult()
@@ -163,19 +200,6 @@ class KNNBase:
     def nearest_neighbor_search(self, queries, result, transT=None):
         self.nearest_neighbor_search_async(queries, result, transT)
         torch.cuda.current_stream().synchronize()
-
-
-def _trans_arg(transT):
-    """-> (pointer, on_device flag, keepalive). Accepts None, a 4x4 host matrix, or a 16-float CUDA tensor
-    (column-major) for device-resident loops."""
-    if transT is None:
-        return None, 0, None
-    if isinstance(transT, torch.Tensor) and transT.is_cuda:
-        if transT.numel() != 16 or transT.dtype != torch.float32:
-            raise SpError(1, "device transT must be 16 float32 (column-major)")
-        return _ptr(transT), 1, transT
-    a = _T16(transT.cpu().numpy() if isinstance(transT, torch.Tensor) else transT)
-    return a.ctypes.data_as(C.c_void_p), 0, a
 
 
 class KDTree(KNNBase):
@@ -242,27 +266,12 @@ class KDTree(KNNBase):
 
     def knn_search_async(self, queries, k, result, transT=None):
         q = _dev_f32(_points_of(queries), 4)
-        if k > 100:
-            raise SpError(2, "[KDTree::knn_search_async] `k` is too large. not support.")
-        result.resize(q.shape[0], k, q.device)
-        if q.shape[0] == 0:
-            return
-        tp, on_dev, keep = _trans_arg(transT)
         own = (self._own_cloud(q),) if self._accelerated else ()
-        check(self._fn("search")(self._h, _ptr(q), q.shape[0], k, tp, on_dev, *own, _ptr(result.indices),
-                                 _ptr(result.distances), _stream()))
+        self._knn_search(self._fn("search"), 100, "[KDTree::knn_search_async] `k` is too large. not support.", q, k, result, transT, own)
 
     def radius_search_async(self, queries, max_k, radius, result, transT=None):
-        q = _dev_f32(_points_of(queries), 4)
-        if max_k > 100:
-            raise SpError(2, "[KDTree::radius_search_async] `max_k` is too large. not support.")
-        if q.shape[0] == 0 or max_k == 0:
-            result.resize(0, 0, q.device)
-            return
-        result.resize(q.shape[0], max_k, q.device)
-        tp, on_dev, keep = _trans_arg(transT)
-        check(self._fn("radius_search")(self._h, _ptr(q), q.shape[0], max_k, radius, tp, on_dev, _ptr(result.indices),
-                                        _ptr(result.distances), _stream()))
+        self._radius_search(self._fn("radius_search"), 100, "[KDTree::radius_search_async] `max_k` is too large. not support.",
+                            queries, max_k, radius, result, transT)
 
     def remove_nodes_by_flags(self, flags, indices):
         if flags.shape[0] != indices.shape[0]:
@@ -297,15 +306,8 @@ class BVH(KNNBase):
             pass
 
     def knn_search_async(self, queries, k, result, transT=None):
-        q = _dev_f32(_points_of(queries), 4)
-        if k > 32:
-            raise SpError(2, "[BVH::knn_search_async] `k` is too large. not support.")
-        result.resize(q.shape[0], k, q.device)
-        if q.shape[0] == 0:
-            return
-        tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_bvh_search(self._h, _ptr(q), q.shape[0], k, tp, on_dev, _ptr(result.indices),
-                                       _ptr(result.distances), _stream()))
+        self._knn_search(_lib.lib().sp_bvh_search, 32, "[BVH::knn_search_async] `k` is too large. not support.", queries, k, result,
+                         transT)
 
     def _set_option(self, name, value):
         """csrc/sp_internal.h switches of this handle (tests, comparisons)."""
@@ -321,16 +323,8 @@ class BVH(KNNBase):
 
     def radius_search_async(self, queries, max_k, radius, result, transT=None):
         """KDTree::radius_search_async (kdtree.hpp:574-719) on the device-built hierarchy (sp_bvh_radius_search), max_k <= 32."""
-        q = _dev_f32(_points_of(queries), 4)
-        if max_k > 32:
-            raise SpError(2, "[BVH::radius_search_async] `max_k` is too large (max 32).")
-        if q.shape[0] == 0 or max_k == 0:
-            result.resize(0, 0, q.device)
-            return
-        result.resize(q.shape[0], max_k, q.device)
-        tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_bvh_radius_search(self._h, _ptr(q), q.shape[0], max_k, radius, tp, on_dev, _ptr(result.indices),
-                                              _ptr(result.distances), _stream()))
+        self._radius_search(_lib.lib().sp_bvh_radius_search, 32, "[BVH::radius_search_async] `max_k` is too large (max 32).", queries,
+                            max_k, radius, result, transT)
 
     def radius_search(self, queries, max_k, radius, transT=None):
         r = KNNResult()
@@ -506,28 +500,13 @@ class GridKNN(KNNBase):
         return covs
 
     def knn_search_async(self, queries, k, result, transT=None):
-        q = _dev_f32(_points_of(queries), 4)
-        if k > 20:
-            raise SpError(2, "[GridKNN::knn_search_async] `k` is too large (max 20).")
-        result.resize(q.shape[0], k, q.device)
-        if q.shape[0] == 0:
-            return
-        tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_grid_search(self._h, _ptr(q), q.shape[0], k, tp, on_dev, _ptr(result.indices),
-                                        _ptr(result.distances), _stream()))
+        self._knn_search(_lib.lib().sp_grid_search, 20, "[GridKNN::knn_search_async] `k` is too large (max 20).", queries, k, result,
+                         transT)
 
     def radius_search_async(self, queries, max_k, radius, result, transT=None):
         """The grid's counterpart of KDTree::radius_search_async (kdtree.hpp:251-280): the max_k nearest within radius."""
-        q = _dev_f32(_points_of(queries), 4)
-        if max_k > 20:
-            raise SpError(2, "[GridKNN::radius_search_async] `max_k` is too large (max 20).")
-        if q.shape[0] == 0 or max_k == 0:
-            result.resize(0, 0, q.device)
-            return
-        result.resize(q.shape[0], max_k, q.device)
-        tp, on_dev, keep = _trans_arg(transT)
-        check(_lib.lib().sp_grid_radius_search(self._h, _ptr(q), q.shape[0], max_k, radius, tp, on_dev,
-                                               _ptr(result.indices), _ptr(result.distances), _stream()))
+        self._radius_search(_lib.lib().sp_grid_radius_search, 20, "[GridKNN::radius_search_async] `max_k` is too large (max 20).",
+                            queries, max_k, radius, result, transT)
 
     def radius_search(self, queries, max_k, radius, transT=None):
         result = KNNResult()

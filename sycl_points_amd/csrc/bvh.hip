@@ -170,9 +170,9 @@ __device__ __forceinline__ float box_d2(float lx, float ly, float lz, float hx, 
 template <int KCAP, bool RADIUS = false>
 __global__ __launch_bounds__(kBlock) void bvh_search_kernel(const float4* __restrict__ node, const float4* __restrict__ obox,
                                                             const float4* __restrict__ spts, unsigned n,
-                                                            const float4* __restrict__ queries, unsigned nq, int k, Mat4Arg T_val,
-                                                            const float* __restrict__ T_dev, int32_t* __restrict__ idx_out,
-                                                            float* __restrict__ d2_out, float radius_sq = 0.0f,
+                                                            const float4* __restrict__ queries, unsigned nq, int k, QueryPose pose,
+                                                            int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
+                                                            float radius_sq = 0.0f,
                                                             const unsigned* __restrict__ todo = nullptr,
                                                             const unsigned* __restrict__ todo_count = nullptr) {
     __shared__ unsigned st_node[kBvhStack][kBlock];
@@ -186,9 +186,7 @@ __global__ __launch_bounds__(kBlock) void bvh_search_kernel(const float4* __rest
     float qx, qy, qz;
     size_t row;
     if (queries) {
-        const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-        const float4 q4 = queries[qi];
-        transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+        load_query(queries, qi, load_pose(pose), qx, qy, qz);
         row = qi;
     } else {  // self-kNN: the cloud's own points in Morton order, results by original index
         const float4 q4 = spts[qi];
@@ -407,15 +405,13 @@ __device__ __forceinline__ bool bvh_walk(const float4* __restrict__ node, const 
 // leaf loads share cache lines, as they do for the cloud's own points (1 M queries in arbitrary order, k = 20: 5.8 ms on the
 // non-uniform cloud against 3.4 ms for the same points in tree order). Key = the build's 48-bit Morton code of the transformed
 // query in the tree's bounding box (clamped; non-finite queries last), sorted by the library's radix sort.
-__global__ __launch_bounds__(kBlock) void bvh_query_key_kernel(const float4* __restrict__ queries, unsigned nq, Mat4Arg T_val,
-                                                               const float* __restrict__ T_dev, const unsigned* __restrict__ bbox,
-                                                               uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+__global__ __launch_bounds__(kBlock) void bvh_query_key_kernel(const float4* __restrict__ queries, unsigned nq, QueryPose pose,
+                                                               const unsigned* __restrict__ bbox, uint64_t* __restrict__ keys,
+                                                               uint32_t* __restrict__ vals) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nq) return;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[i];
     float x, y, z;
-    transform_point(T, q4.x, q4.y, q4.z, x, y, z);
+    load_query(queries, i, load_pose(pose), x, y, z);
     uint64_t key = kBvhInvalidKey;
     if (isfinite(x) && isfinite(y) && isfinite(z)) {  // (the key of bvh_key_kernel, clamped to the tree's box)
         float box[6];
@@ -434,8 +430,7 @@ __global__ __launch_bounds__(kBlock) void bvh_query_key_kernel(const float4* __r
 template <int KCAP, int MODE>
 __global__ __launch_bounds__(kBlock) void bvh_heap_kernel(const float4* __restrict__ node, const float4* __restrict__ obox,
                                                           const float4* __restrict__ spts, unsigned n,
-                                                          const float4* __restrict__ queries, unsigned nq, int k, Mat4Arg T_val,
-                                                          const float* __restrict__ T_dev, float radius_sq,
+                                                          const float4* __restrict__ queries, unsigned nq, int k, QueryPose pose, float radius_sq,
                                                           int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
                                                           unsigned* __restrict__ todo, unsigned* __restrict__ todo_count,
                                                           const unsigned* __restrict__ order, unsigned* __restrict__ arena,
@@ -456,9 +451,7 @@ __global__ __launch_bounds__(kBlock) void bvh_heap_kernel(const float4* __restri
         if (__float_as_int(q4.w) < 0) return;  // a removed point: no row of its own
         o = (size_t)__float_as_uint(q4.w) * (size_t)k;
     } else {
-        const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-        const float4 q4 = queries[qi];
-        transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+        load_query(queries, qi, load_pose(pose), qx, qy, qz);
         o = (size_t)qi * (size_t)k;
     }
     const bool mine = isfinite(qx) && isfinite(qy) && isfinite(qz);  // false: handed on to bvh_search_kernel
@@ -646,14 +639,27 @@ __global__ __launch_bounds__(kBlock) void bvh_flags_to_u32_kernel(const uint8_t*
 }
 
 template <int KCAP>
-void launch_bvh(const sp_bvh* b, const float4* q, unsigned nq, int k, const Mat4Arg& Tv, const float* T_dev, int32_t* idx, float* d2,
-                hipStream_t st, float radius_sq) {
+void launch_bvh(const sp_bvh* b, const float4* q, unsigned nq, int k, const QueryPose& pose, int32_t* idx, float* d2, hipStream_t st,
+                float radius_sq) {
     if (radius_sq >= 0.0f)
-        bvh_search_kernel<KCAP, true><<<div_up(nq, kBlock), kBlock, 0, st>>>(b->node, b->obox, b->pts, (unsigned)b->n, q, nq, k, Tv,
-                                                                           T_dev, idx, d2, radius_sq);
+        bvh_search_kernel<KCAP, true><<<div_up(nq, kBlock), kBlock, 0, st>>>(b->node, b->obox, b->pts, (unsigned)b->n, q, nq, k, pose,
+                                                                           idx, d2, radius_sq);
     else
-        bvh_search_kernel<KCAP><<<div_up(nq, kBlock), kBlock, 0, st>>>(b->node, b->obox, b->pts, (unsigned)b->n, q, nq, k, Tv, T_dev,
-                                                                     idx, d2);
+        bvh_search_kernel<KCAP><<<div_up(nq, kBlock), kBlock, 0, st>>>(b->node, b->obox, b->pts, (unsigned)b->n, q, nq, k, pose, idx, d2);
+}
+
+// The heap kernel, then the sorted-insertion kernel over what it handed on (`todo`). MODE 0: the cloud's own points (no q),
+// 1: external queries, 2: the same within radius_sq >= 0.
+template <int KC, int OLDK>
+void launch_heap(const sp_bvh* b, const float4* q, unsigned nq, int k, const QueryPose& pose, float radius_sq, int32_t* idx, float* d2,
+                 unsigned* todo, unsigned* todo_count, const unsigned* order, unsigned* arena, unsigned arena_slots, hipStream_t st) {
+    const unsigned g = div_up(nq, kBlock), n = (unsigned)b->n;
+    const auto heap = !q ? bvh_heap_kernel<KC, 0> : radius_sq < 0.0f ? bvh_heap_kernel<KC, 1> : bvh_heap_kernel<KC, 2>;
+    heap<<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n, q, nq, k, pose, radius_sq, idx, d2, todo, todo_count, order, arena, arena_slots);
+    if (q && radius_sq >= 0.0f)
+        bvh_search_kernel<OLDK, true><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n, q, nq, k, pose, idx, d2, radius_sq, todo, todo_count);
+    else
+        bvh_search_kernel<OLDK><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n, q, nq, k, pose, idx, d2, 0.0f, todo, todo_count);
 }
 
 // radius_sq < 0: plain kNN
@@ -664,11 +670,7 @@ int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const 
         return SP_ERR_INVALID_ARGUMENT;
     }
     b->streams.note(st);
-    Mat4Arg Tv;
-    for (int i = 0; i < 16; ++i) Tv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (transT && !transT_on_device)
-        for (int i = 0; i < 16; ++i) Tv.m[i] = transT[i];
-    const float* T_dev = transT_on_device ? transT : nullptr;
+    const QueryPose pose = query_pose(transT, transT_on_device);
     const int kk = (int)k;
     if (k >= (q ? 1u : 2u) && b->n > (size_t)kBvhLeaf && b->self_heap) {
         // heap kernel; what it hands on (non-finite queries, a tree deeper than its stack) is finished by the sorted-insertion kernel
@@ -692,41 +694,16 @@ int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const 
                 uint64_t *ka = reinterpret_cast<uint64_t*>(sortbuf), *kb = ka + nq;
                 uint32_t *va = reinterpret_cast<uint32_t*>(kb + nq), *vb = va + nq;
                 void* const tmp = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(vb + nq) + 7) & ~uintptr_t(7));
-                bvh_query_key_kernel<<<div_up(nq, kBlock), kBlock, 0, st>>>(q, nq, Tv, T_dev, b->bbox, ka, va);
+                bvh_query_key_kernel<<<div_up(nq, kBlock), kBlock, 0, st>>>(q, nq, pose, b->bbox, ka, va);
                 bool in_b = false;
                 rc = radix_sort_pairs_u64(ka, kb, va, vb, nq, 48, tmp, wsb, &in_b, st);
                 order = in_b ? vb : va;
             }
         }
         if (rc == SP_OK) {
-            const unsigned g = div_up(nq, kBlock);
-            const unsigned n32 = (unsigned)b->n;
-            const float r2 = radius_sq;
-#define SP_BVH_HEAP(KC, OLDK)                                                                                                          \
-    do {                                                                                                                                \
-        if (!q) {                                                                                                                       \
-            bvh_heap_kernel<KC, 0><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, r2, idx_out, d2_out, todo, \
-                                                        todo_count, order, deep, arena_slots);                                                             \
-            bvh_search_kernel<OLDK><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, idx_out, d2_out, 0.0f,    \
-                                                         todo, todo_count);                                                            \
-        } else if (r2 < 0.0f) {                                                                                                         \
-            bvh_heap_kernel<KC, 1><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, r2, idx_out, d2_out, todo, \
-                                                        todo_count, order, deep, arena_slots);                                                             \
-            bvh_search_kernel<OLDK><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, idx_out, d2_out, 0.0f,    \
-                                                         todo, todo_count);                                                            \
-        } else {                                                                                                                        \
-            bvh_heap_kernel<KC, 2><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, r2, idx_out, d2_out, todo, \
-                                                        todo_count, order, deep, arena_slots);                                                             \
-            bvh_search_kernel<OLDK, true><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n32, q, nq, kk, Tv, T_dev, idx_out, d2_out,    \
-                                                               r2, todo, todo_count);                                                  \
-        }                                                                                                                               \
-    } while (0)
-            if (k <= 5) SP_BVH_HEAP(5, 10);
-            else if (k <= 10) SP_BVH_HEAP(10, 10);
-            else if (k <= 20) SP_BVH_HEAP(21, 20);
-            else if (k == 21) SP_BVH_HEAP(21, 32);
-            else SP_BVH_HEAP(32, 32);
-#undef SP_BVH_HEAP
+            const auto launch = k <= 5 ? launch_heap<5, 10> : k <= 10 ? launch_heap<10, 10> : k <= 20 ? launch_heap<21, 20>
+                                : k == 21 ? launch_heap<21, 32> : launch_heap<32, 32>;
+            launch(b, q, nq, kk, pose, radius_sq, idx_out, d2_out, todo, todo_count, order, deep, arena_slots, st);
             rc = launch_status();
         }
         StreamSet used;
@@ -735,10 +712,10 @@ int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const 
         if (sortbuf) pooled_free_after(sortbuf, used);
         return rc;
     }
-    if (k == 1) launch_bvh<1>(b, q, nq, kk, Tv, T_dev, idx_out, d2_out, st, radius_sq);
-    else if (k <= 10) launch_bvh<10>(b, q, nq, kk, Tv, T_dev, idx_out, d2_out, st, radius_sq);
-    else if (k <= 20) launch_bvh<20>(b, q, nq, kk, Tv, T_dev, idx_out, d2_out, st, radius_sq);
-    else launch_bvh<32>(b, q, nq, kk, Tv, T_dev, idx_out, d2_out, st, radius_sq);
+    if (k == 1) launch_bvh<1>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
+    else if (k <= 10) launch_bvh<10>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
+    else if (k <= 20) launch_bvh<20>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
+    else launch_bvh<32>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
     return launch_status();
 }
 

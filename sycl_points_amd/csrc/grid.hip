@@ -53,9 +53,7 @@ __global__ __launch_bounds__(kBlock) void cell_id_kernel(const float4* __restric
             if (p.x < g.ox || p.y < g.oy || p.z < g.oz || p.x > hx || p.y > hy || p.z > hz)
                 __hip_atomic_store(bounds_error, kDevErrBounds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        const int cx = cell_coord(p.x, g.ox, g.inv_h, g.nx), cy = cell_coord(p.y, g.oy, g.inv_h, g.ny),
-                  cz = cell_coord(p.z, g.oz, g.inv_h, g.nz);
-        key = ((unsigned)cz * g.ny + cy) * g.nx + cx;
+        key = cell_of_point(g, p.x, p.y, p.z);
     }
     keys[i] = key;
     vals[i] = i;
@@ -133,9 +131,7 @@ __global__ __launch_bounds__(kSbThreads) void grid_build_small_kernel(const floa
                     const float hx = g.ox + g.nx * g.h, hy = g.oy + g.ny * g.h, hz = g.oz + g.nz * g.h;
                     out_of_box |= p.x < g.ox || p.y < g.oy || p.z < g.oz || p.x > hx || p.y > hy || p.z > hz;
                 }
-                const int cx = cell_coord(p.x, g.ox, g.inv_h, g.nx), cy = cell_coord(p.y, g.oy, g.inv_h, g.ny),
-                          cz = cell_coord(p.z, g.oz, g.inv_h, g.nz);
-                k[c] = ((unsigned)cz * g.ny + cy) * g.nx + cx;
+                k[c] = cell_of_point(g, p.x, p.y, p.z);
             }
         }
     }
@@ -283,8 +279,7 @@ template <int KCAP>
 __global__ __launch_bounds__(kBlock) void grid_search_kernel(const float4* __restrict__ pts,
                                                              const unsigned* __restrict__ start, GridDesc g,
                                                              const float4* __restrict__ queries, unsigned nq, int k,
-                                                             Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                             int32_t* __restrict__ idx_out,
+                                                             QueryPose pose, int32_t* __restrict__ idx_out,
                                                              float* __restrict__ d2_out,
                                                              const unsigned* __restrict__ todo = nullptr,
                                                              const unsigned* __restrict__ todo_count = nullptr,
@@ -295,10 +290,8 @@ __global__ __launch_bounds__(kBlock) void grid_search_kernel(const float4* __res
     const unsigned t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= (todo ? *todo_count : nq)) return;
     const unsigned qi = todo ? todo[t] : t;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[qi];
     float qx, qy, qz;
-    transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+    load_query(queries, qi, load_pose(pose), qx, qy, qz);
 
     float bd[KCAP];
     int bi[KCAP];
@@ -691,20 +684,16 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_select_kernel(const float
 __global__ __launch_bounds__(kWave) void grid_search_select_kernel(const float4* __restrict__ pts,
                                                                    const unsigned* __restrict__ start, GridDesc g,
                                                                    const float4* __restrict__ queries, unsigned nq, int k,
-                                                                   Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                                   int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
+                                                                   QueryPose pose, int32_t* __restrict__ idx_out,
+                                                                   float* __restrict__ d2_out,
                                                                    unsigned* __restrict__ todo, unsigned* __restrict__ todo_count,
                                                                    const unsigned* __restrict__ order = nullptr) {
     __shared__ unsigned long long l_key8[kSelCand / 8][kWave];
     __shared__ int l_pos[kSelList][kWave];
     const unsigned gi = blockIdx.x * kWave + threadIdx.x;
-    // (order: the queries sorted by cell, grid_query_cell_kernel — an idle lane of the last wave is number nq, as without it)
+    // (order: the queries sorted by cell, query_cell_kernel — an idle lane of the last wave is number nq, as without it)
     const unsigned qi = (order && gi < nq) ? order[gi] : gi;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[min(qi, nq - 1u)];
-    float4 q;
-    transform_point(T, q4.x, q4.y, q4.z, q.x, q.y, q.z);
-    q.w = 0.0f;
+    const float4 q = load_query(queries, min(qi, nq - 1u), load_pose(pose), 0.0f);
     const bool finite_q = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
     const bool active = qi < nq && finite_q && g.n > 0;
     const int cx = cell_coord(q.x, g.ox, g.inv_h, g.nx), cy = cell_coord(q.y, g.oy, g.inv_h, g.ny),
@@ -977,17 +966,14 @@ __global__ __launch_bounds__(kWave) void grid_self_knn_wave_list_kernel(const fl
 // ... and for a list of EXTERNAL queries (what grid_search_select_kernel could not prove): rows by query number.
 __global__ __launch_bounds__(kWave) void grid_search_wave_list_kernel(const float4* __restrict__ pts,
                                                                       const unsigned* __restrict__ start, GridDesc g,
-                                                                      const float4* __restrict__ queries, int k, Mat4Arg T_val,
-                                                                      const float* __restrict__ T_dev, TileOut out) {
+                                                                      const float4* __restrict__ queries, int k, QueryPose pose,
+                                                                      TileOut out) {
     __shared__ float sm_terms[9][33];
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
+    const Rigid T = load_pose(pose);
     const unsigned n_items = *out.todo_count;
     for (unsigned item = blockIdx.x; item < n_items; item += gridDim.x) {  // (wave-uniform)
         const unsigned qi = out.todo[item];
-        const float4 q4 = queries[qi];
-        float4 q;
-        transform_point(T, q4.x, q4.y, q4.z, q.x, q.y, q.z);
-        q.w = __uint_as_float(qi);
+        const float4 q = load_query(queries, qi, T, __uint_as_float(qi));
         const int ry = cell_coord(q.y, g.oy, g.inv_h, g.ny), rz = cell_coord(q.z, g.oz, g.inv_h, g.nz);
         self_knn_wave_queries(pts, start, g, k, out, sm_terms, 0u, 1u, ry, rz, q);
     }
@@ -1054,50 +1040,23 @@ __global__ __launch_bounds__(kBlock) void radius_filter_kernel(int32_t* __restri
 __global__ __launch_bounds__(kBlock) void grid_search_k1_kernel(const float4* __restrict__ pts,
                                                                 const unsigned* __restrict__ start, GridDesc g,
                                                                 const float4* __restrict__ queries, unsigned nq,
-                                                                Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                                int32_t* __restrict__ idx_out,
+                                                                QueryPose pose, int32_t* __restrict__ idx_out,
                                                                 float* __restrict__ d2_out,
                                                                 const unsigned* __restrict__ order = nullptr) {
     const unsigned gi = blockIdx.x * kBlock + threadIdx.x;
     if (gi >= nq) return;
     const unsigned qi = order ? order[gi] : gi;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[qi];
     float qx, qy, qz;
-    transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+    load_query(queries, qi, load_pose(pose), qx, qy, qz);
     const Nearest nn = grid_nn1_auto(pts, start, g, qx, qy, qz);
     idx_out[qi] = nn.idx;
     d2_out[qi] = nn.d2;
 }
 
-// External queries in cell order (1 M queries in arbitrary order, k = 20: 2.1 ms against 0.68 ms for the same queries in cell
-// order): key = the cell the transformed query falls into (non-finite queries last), sorted by the library's radix sort.
-__global__ __launch_bounds__(kBlock) void grid_query_cell_kernel(const float4* __restrict__ queries, unsigned nq, GridDesc g,
-                                                                 Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                                 uint32_t* __restrict__ count) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i == 0) *count = nq;
-    if (i >= nq) return;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[i];
-    float qx, qy, qz;
-    transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
-    unsigned key = (unsigned)g.nx * g.ny * g.nz;
-    if (isfinite(qx) && isfinite(qy) && isfinite(qz))
-        key = ((unsigned)cell_coord(qz, g.oz, g.inv_h, g.nz) * g.ny + cell_coord(qy, g.oy, g.inv_h, g.ny)) * g.nx +
-              cell_coord(qx, g.ox, g.inv_h, g.nx);
-    keys[i] = key;
-    vals[i] = i;
-}
-
 template <int KCAP>
 int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* T, int T_dev, int32_t* idx, float* d2,
            hipStream_t st, bool queries_in_cell_order = false, float bound2 = FLT_MAX) {
-    Mat4Arg tv;
-    for (int i = 0; i < 16; ++i) tv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (T && !T_dev)
-        for (int i = 0; i < 16; ++i) tv.m[i] = T[i];
+    const QueryPose pose = query_pose(T, T_dev);
     const GridDesc g = grid_desc(gr);
     // many queries: in cell order (0.1 ms per million for the sort; a loss below a few hundred thousand)
     uint32_t* sortbuf = nullptr;
@@ -1112,8 +1071,8 @@ int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* 
         if (pooled_alloc(&sortbuf, (4 * nq + 4) * sizeof(uint32_t) + wsb, st) != hipSuccess) return SP_ERR_HIP;
         uint32_t *ka = sortbuf, *kb = ka + nq, *va = kb + nq, *vb = va + nq;
         order_count = vb + nq;
-        grid_query_cell_kernel<<<div_up(nq, kBlock), kBlock, 0, st>>>(reinterpret_cast<const float4*>(q), (unsigned)nq, g, tv,
-                                                                     T_dev ? T : nullptr, ka, va, order_count);
+        query_cell_kernel<><<<div_up(nq, kBlock), kBlock, 0, st>>>(reinterpret_cast<const float4*>(q), (unsigned)nq, g, pose, ka, va,
+                                                                   order_count);
         unsigned bits = 1;
         while ((1ull << bits) <= (unsigned long long)gr->ncells && bits < 32) ++bits;  // (the key `ncells` itself must fit)
         bool in_b = false;
@@ -1123,7 +1082,7 @@ int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* 
     if (KCAP == 1) {
         grid_search_k1_kernel<<<div_up(nq, kBlock), kBlock, 0, st>>>(gr->d_pts, gr->d_start, g,
                                                                       reinterpret_cast<const float4*>(q), (unsigned)nq,
-                                                                      tv, T_dev ? T : nullptr, idx, d2, order);
+                                                                      pose, idx, d2, order);
         return launch_status();
     }
     if (k > 10 && gr->n != 0 && (gr->self_knn_mode == 0 || gr->self_knn_mode == 3)) {  // (k <= 20: sp_grid_search)
@@ -1137,13 +1096,13 @@ int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* 
         int rc = zero_async(todo_count, 4, st);
         if (rc == SP_OK) {
             grid_search_select_kernel<<<div_up(nq, kWave), kWave, 0, st>>>(gr->d_pts, gr->d_start, g,
-                                                                        reinterpret_cast<const float4*>(q), (unsigned)nq, (int)k, tv,
-                                                                        T_dev ? T : nullptr, idx, d2, todo, todo_count, order);
+                                                                        reinterpret_cast<const float4*>(q), (unsigned)nq, (int)k, pose,
+                                                                        idx, d2, todo, todo_count, order);
             TileOut lo;
             lo.knn_idx = idx; lo.knn_d2 = d2; lo.covs = nullptr; lo.normals = nullptr;
             lo.todo = todo; lo.todo_count = todo_count; lo.pos_lo = 0u; lo.pos_hi = 0xffffffffu;
             grid_search_wave_list_kernel<<<kNumCU * 32, kWave, 0, st>>>(gr->d_pts, gr->d_start, g, reinterpret_cast<const float4*>(q),
-                                                                      (int)k, tv, T_dev ? T : nullptr, lo);
+                                                                      (int)k, pose, lo);
             rc = launch_status();
         }
         StreamSet used;
@@ -1153,7 +1112,7 @@ int launch(const sp_grid* gr, const float* q, size_t nq, size_t k, const float* 
     }
     grid_search_kernel<KCAP><<<div_up(nq, kBlock), kBlock, 0, st>>>(gr->d_pts, gr->d_start, g,
                                                                   reinterpret_cast<const float4*>(q), (unsigned)nq,
-                                                                  (int)k, tv, T_dev ? T : nullptr, idx, d2, order, order_count, bound2);
+                                                                  (int)k, pose, idx, d2, order, order_count, bound2);
     return launch_status();
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "sp_common.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 
 struct sp_grid {
     size_t n = 0;
@@ -60,6 +61,29 @@ inline GridDesc grid_desc(const sp_grid* gr) {
 __device__ __forceinline__ int cell_coord(float v, float o, float inv_h, int dim) {
     const float t = floorf((v - o) * inv_h);
     return (int)fminf(fmaxf(t, 0.0f), (float)(dim - 1));
+}
+
+// The linear cell of the cell coordinates (cx, cy, cz), x fastest, and of the (finite) point (x, y, z), clamped into the grid.
+__device__ __forceinline__ unsigned cell_index(const GridDesc& g, int cx, int cy, int cz) { return ((unsigned)cz * g.ny + cy) * g.nx + cx; }
+__device__ __forceinline__ unsigned cell_of_point(const GridDesc& g, float x, float y, float z) {
+    return cell_index(g, cell_coord(x, g.ox, g.inv_h, g.nx), cell_coord(y, g.oy, g.inv_h, g.ny), cell_coord(z, g.oz, g.inv_h, g.nz));
+}
+
+// External queries in cell order: key = the cell of the grid that T * q falls into (non-finite queries last: the trash cell past
+// the grid), val = the query's number, for the library's radix sort; `count`, when given, receives nq. GridKNN sorts its queries
+// by it (1 M queries in arbitrary order, k = 20: 2.1 ms against 0.68 ms in cell order), the GICP source its points, so that
+// consecutive lanes walk consecutive cells of a grid row and their extent / point / covariance loads share cache lines.
+template <int = 0>
+__global__ __launch_bounds__(kBlock) void query_cell_kernel(const float4* __restrict__ queries, unsigned nq, GridDesc g, QueryPose pose,
+                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                            uint32_t* __restrict__ count = nullptr) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (count && i == 0) *count = nq;
+    if (i >= nq) return;
+    float qx, qy, qz;
+    load_query(queries, i, load_pose(pose), qx, qy, qz);
+    keys[i] = isfinite(qx) && isfinite(qy) && isfinite(qz) ? cell_of_point(g, qx, qy, qz) : (unsigned)g.nx * g.ny * g.nz;
+    vals[i] = i;
 }
 
 // squared distance from coordinate v to the interval [lo, hi], made conservative by eps
@@ -244,7 +268,7 @@ __device__ __forceinline__ void fast_extents(const unsigned* __restrict__ start,
     const int za = max(cz - (lz ? 1 : 0), 0), zb = min(cz + (lz ? 0 : 1), g.nz - 1);
     cov_cells = fminf(fminf(lx ? 1.0f - tx : tx, ly ? 1.0f - ty : ty), lz ? 1.0f - tz : tz);
     // extents of the (up to) four rows; a row that does not exist repeats an existing one with an empty range
-    const unsigned r00 = ((unsigned)za * g.ny + ya) * g.nx + xa;
+    const unsigned r00 = cell_index(g, xa, ya, za);
     const unsigned dy = yb != ya ? (unsigned)g.nx : 0u, dz = zb != za ? (unsigned)g.ny * g.nx : 0u;
     const unsigned w = (unsigned)(xb - xa) + 1u;
     const unsigned r01 = r00 + dy, r10 = r00 + dz, r11 = r10 + dy;

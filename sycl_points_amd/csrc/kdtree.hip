@@ -208,8 +208,7 @@ template <int KCAP, bool RADIUS, bool BATCH_LEAF>
 __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __restrict__ internal,
                                                                const float4* __restrict__ leaf, int root,
                                                                unsigned stride, const float4* __restrict__ queries,
-                                                               unsigned nq, int k, float radius_sq, Mat4Arg T_val,
-                                                               const float* __restrict__ T_dev,
+                                                               unsigned nq, int k, float radius_sq, QueryPose pose,
                                                                int32_t* __restrict__ idx_out,
                                                                float* __restrict__ d2_out) {
     __shared__ float far_dist[kFarDepth][kBlock];
@@ -218,10 +217,8 @@ __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __r
     if (qi >= nq) return;  // no barrier below: safe
     const unsigned lane = threadIdx.x;
 
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 q4 = queries[qi];
     float qx, qy, qz;
-    transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+    load_query(queries, qi, load_pose(pose), qx, qy, qz);
 
     float bd[KCAP];
     int bi[KCAP];
@@ -319,45 +316,32 @@ __global__ __launch_bounds__(kBlock) void kdtree_search_kernel(const float4* __r
         if (i < k) { d2_out[o + i] = bd[i]; idx_out[o + i] = bi[i]; }
 }
 
-// K4: rewrite idx of every stored point (kdtree.hpp:743-755). valid <=> idx >= 0.
-__global__ void remove_internal_kernel(float4* internal, unsigned n_internal, const uint8_t* flags,
-                                       const int32_t* new_idx, unsigned n_flags) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_internal) return;
-    float4 n0 = internal[2 * (size_t)i];
-    const int p = __builtin_bit_cast(int, n0.w);
-    if (p < 0 || (unsigned)p >= n_flags) return;
-    const int ni = flags[p] ? new_idx[p] : -1;
-    n0.w = __builtin_bit_cast(float, ni);
-    internal[2 * (size_t)i] = n0;
-}
-__global__ void remove_leaf_kernel(float4* leaf, size_t n_slots, const uint8_t* flags, const int32_t* new_idx,
+// K4: rewrite idx of every stored point (kdtree.hpp:743-755), the .w of every stride-th row (internal nodes are two rows, leaf
+// slots one). valid <=> idx >= 0.
+__global__ void remove_rows_kernel(float4* rows, size_t n, unsigned stride, const uint8_t* flags, const int32_t* new_idx,
                                    unsigned n_flags) {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_slots) return;
-    float4 s = leaf[i];
-    const int p = __builtin_bit_cast(int, s.w);
+    if (i >= n) return;
+    float4 r = rows[stride * i];
+    const int p = __builtin_bit_cast(int, r.w);
     if (p < 0 || (unsigned)p >= n_flags) return;
     const int ni = flags[p] ? new_idx[p] : -1;
-    s.w = __builtin_bit_cast(float, ni);
-    leaf[i] = s;
+    r.w = __builtin_bit_cast(float, ni);
+    rows[stride * i] = r;
 }
 
 template <int KCAP, bool RADIUS>
 int launch_search(const sp_kdtree* t, const float* q, size_t nq, size_t k, float radius_sq, const float* T,
                   int T_dev, int32_t* idx, float* d2, hipStream_t st) {
-    Mat4Arg tv;
-    for (int i = 0; i < 16; ++i) tv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (T && !T_dev)
-        for (int i = 0; i < 16; ++i) tv.m[i] = T[i];
+    const QueryPose pose = query_pose(T, T_dev);
     if (KCAP > 1 && KCAP <= 20 && nq < 200000)
         kdtree_search_kernel<KCAP, RADIUS, true><<<div_up(nq, kBlock), kBlock, 0, st>>>(
             t->d_internal, t->d_leaf, t->root, t->stride, reinterpret_cast<const float4*>(q), (unsigned)nq, (int)k,
-            radius_sq, tv, T_dev ? T : nullptr, idx, d2);
+            radius_sq, pose, idx, d2);
     else
         kdtree_search_kernel<KCAP, RADIUS, false><<<div_up(nq, kBlock), kBlock, 0, st>>>(
             t->d_internal, t->d_leaf, t->root, t->stride, reinterpret_cast<const float4*>(q), (unsigned)nq, (int)k,
-            radius_sq, tv, T_dev ? T : nullptr, idx, d2);
+            radius_sq, pose, idx, d2);
     return launch_status();
 }
 
@@ -475,11 +459,11 @@ extern "C" int sp_kdtree_remove_by_flags(sp_kdtree* tree, const uint8_t* flags, 
     hipStream_t st = as_stream(stream);
     tree->streams.note(st);
     if (tree->n_internal)
-        remove_internal_kernel<<<div_up(tree->n_internal, kBlock), kBlock, 0, st>>>(tree->d_internal, tree->n_internal,
-                                                                                    flags, new_indices, (unsigned)n_flags);
+        remove_rows_kernel<<<div_up(tree->n_internal, kBlock), kBlock, 0, st>>>(tree->d_internal, tree->n_internal, 2u, flags,
+                                                                                new_indices, (unsigned)n_flags);
     const size_t slots = (size_t)tree->n_leaves * tree->stride;
     if (slots)
-        remove_leaf_kernel<<<div_up(slots, kBlock), kBlock, 0, st>>>(tree->d_leaf, slots, flags, new_indices,
+        remove_rows_kernel<<<div_up(slots, kBlock), kBlock, 0, st>>>(tree->d_leaf, slots, 1u, flags, new_indices,
                                                                     (unsigned)n_flags);
     return launch_status();
 }

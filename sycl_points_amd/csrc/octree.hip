@@ -291,19 +291,18 @@ __device__ __forceinline__ float box_d2(float lx, float ly, float lz, float hx, 
 template <bool TWO>
 __global__ __launch_bounds__(kBlock) void octree_search_kernel(const OctNode* __restrict__ nodes, const float4* __restrict__ spts,
                                                                unsigned stored, const float4* __restrict__ queries, unsigned nq, int k,
-                                                               Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                               int32_t* __restrict__ idx_out, float* __restrict__ d2_out) {
+                                                               QueryPose pose, int32_t* __restrict__ idx_out,
+                                                               float* __restrict__ d2_out) {
     __shared__ int st_node[kOctWaves][kOctStack];
     __shared__ float st_d[kOctWaves][kOctStack];
     const int lane = (int)(threadIdx.x & 63u);
     const unsigned w = threadIdx.x >> 6;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
+    const Rigid T = load_pose(pose);
     const int kth_lane = (k - 1) & 63;  // the k-th entry: lo for k <= 64, hi above
     // (no barrier below: the waves of a workgroup share nothing)
     for (size_t qi = (size_t)blockIdx.x * kOctWaves + w; qi < nq; qi += (size_t)gridDim.x * kOctWaves) {
-        const float4 q4 = queries[qi];
         float qx, qy, qz;
-        transform_point(T, q4.x, q4.y, q4.z, qx, qy, qz);
+        load_query(queries, (unsigned)qi, T, qx, qy, qz);
         unsigned long long lo = kNoCand, hi = kNoCand, kth = kNoCand;  // sorted ascending over lo[0..63], hi[0..63]
 
         // the slots [start, start + count) against the list: every candidate nearer than the k-th goes in at its rank, the
@@ -393,13 +392,6 @@ __global__ __launch_bounds__(kBlock) void octree_search_kernel(const OctNode* __
             d2_out[o + 64 + lane] = hi == kNoCand ? FLT_MAX : key_d2(hi);
         }
         __builtin_amdgcn_wave_barrier();
-    }
-}
-// The rows of a search that has nothing to walk (an empty tree): KNNResult's padding.
-__global__ __launch_bounds__(kBlock) void oct_pad_kernel(int32_t* __restrict__ idx_out, float* __restrict__ d2_out, size_t total) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kBlock) {
-        idx_out[i] = -1;
-        d2_out[i] = FLT_MAX;
     }
 }
 
@@ -611,22 +603,18 @@ extern "C" int sp_octree_search(const sp_octree* t, const float* queries, size_t
     hipStream_t st = as_stream(stream);
     t->streams.note(st);
     if (t->kept == 0) {
-        oct_pad_kernel<<<stream_grid(nq * k), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
+        fill_empty_kernel<><<<div_up(nq * k, kBlock), kBlock, 0, st>>>(idx_out, d2_out, nq * k);
         return launch_status();
     }
-    Mat4Arg Tv;
-    for (int i = 0; i < 16; ++i) Tv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (transT && !transT_on_device)
-        for (int i = 0; i < 16; ++i) Tv.m[i] = transT[i];
-    const float* T_dev = transT_on_device ? transT : nullptr;
+    const QueryPose pose = query_pose(transT, transT_on_device);
     const float4* q = reinterpret_cast<const float4*>(queries);
     const unsigned grid = (unsigned)std::min<size_t>(div_up(nq, kOctWaves), (size_t)kNumCU * 64);
     if (k <= 64)
-        octree_search_kernel<false><<<grid, kBlock, 0, st>>>(t->nodes, t->pts, (unsigned)t->stored, q, (unsigned)nq, (int)k, Tv, T_dev,
-                                                            idx_out, d2_out);
+        octree_search_kernel<false><<<grid, kBlock, 0, st>>>(t->nodes, t->pts, (unsigned)t->stored, q, (unsigned)nq, (int)k, pose, idx_out,
+                                                            d2_out);
     else
-        octree_search_kernel<true><<<grid, kBlock, 0, st>>>(t->nodes, t->pts, (unsigned)t->stored, q, (unsigned)nq, (int)k, Tv, T_dev,
-                                                           idx_out, d2_out);
+        octree_search_kernel<true><<<grid, kBlock, 0, st>>>(t->nodes, t->pts, (unsigned)t->stored, q, (unsigned)nq, (int)k, pose, idx_out,
+                                                           d2_out);
     return launch_status();
 }
 

@@ -260,14 +260,13 @@ struct KParams {
     float max_d2, scale, genz_alpha, genz_thr;
     int rot_enable;  // rotation constraint (registration.hpp:559-561): weight and its own robust scale
     float rot_weight, rot_scale;
-    Mat4Arg T_val;
-    const float* T_dev;
+    QueryPose pose;
 };
 
 
 template <int REG, int LOSS>
 __global__ __launch_bounds__(kBlock) void linearize_kernel(KParams P, float* __restrict__ partials) {
-    const Rigid T = load_rigid_colmajor(P.T_dev ? P.T_dev : P.T_val.m);
+    const Rigid T = load_pose(P.pose);
     float acc[kAcc - 1];
 #pragma unroll
     for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
@@ -313,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(KParams P, float* __r
 
 template <int REG, int LOSS>
 __global__ __launch_bounds__(kBlock) void error_kernel(KParams P, float* __restrict__ partials) {
-    const Rigid T = load_rigid_colmajor(P.T_dev ? P.T_dev : P.T_val.m);
+    const Rigid T = load_pose(P.pose);
     float acc[1] = {0.0f};
     unsigned cnt = 0;
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < P.n; i += gridDim.x * kBlock) {
@@ -337,7 +336,7 @@ __global__ __launch_bounds__(kBlock) void error_kernel(KParams P, float* __restr
 
 template <int REG, int LOSS>
 __global__ __launch_bounds__(kBlock) void weights_kernel(KParams P, float* __restrict__ out) {
-    const Rigid T = load_rigid_colmajor(P.T_dev ? P.T_dev : P.T_val.m);
+    const Rigid T = load_pose(P.pose);
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < P.n; i += gridDim.x * kBlock) {
         float w = 0.0f;
         if (P.nn_d2[i] <= P.max_d2) {
@@ -458,26 +457,6 @@ __global__ __launch_bounds__(kBlock) void certificate_kernel(const float4* __res
     nb[i] = r;
 }
 
-// Source ordering: key = cell (of the TARGET grid) that T*p falls into, so that consecutive lanes of the fused
-// kernel walk consecutive cells of a grid row and their extent / point / covariance loads share cache lines.
-__global__ __launch_bounds__(kBlock) void query_cell_kernel(const float4* __restrict__ pts, unsigned n, GridDesc g,
-                                                            Mat4Arg T_val, const float* __restrict__ T_dev,
-                                                            unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const Rigid T = load_rigid_colmajor(T_dev ? T_dev : T_val.m);
-    const float4 p = pts[i];
-    float qx, qy, qz;
-    transform_point(T, p.x, p.y, p.z, qx, qy, qz);
-    unsigned key = (unsigned)g.nx * g.ny * g.nz;
-    if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-        const int cx = cell_coord(qx, g.ox, g.inv_h, g.nx), cy = cell_coord(qy, g.oy, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-        key = ((unsigned)cz * g.ny + cy) * g.nx + cx;
-    }
-    keys[i] = key;
-    vals[i] = i;
-}
 // gather_points + prepare_cov for the source in one pass over the permutation
 __global__ __launch_bounds__(kBlock) void prepare_source_kernel(const float4* __restrict__ pts,
                                                                 const float4* __restrict__ covs,
@@ -505,7 +484,7 @@ __global__ __launch_bounds__(kBlock) void prepare_source_kernel(const float4* __
 
 template <int LOSS, bool FAST_NN, bool P2D = false>
 __global__ __launch_bounds__(kBlock) void gicp_fused_kernel(FusedParams P, float* __restrict__ partials) {
-    const Rigid T = load_rigid_colmajor(P.T_dev ? P.T_dev : P.T_val.m);
+    const Rigid T = load_pose(P.pose);
     float acc[kAcc - 1];
 #pragma unroll
     for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
@@ -525,7 +504,7 @@ __global__ __launch_bounds__(kBlock) void gicp_fused_kernel(FusedParams P, float
 template <int LOSS, bool P2D>
 __global__ __launch_bounds__(kBlock) void error_prepared_kernel(FusedParams P, Mat4Arg T_lin_val, const float* T_lin_dev,
                                                                 float* __restrict__ partials) {
-    const Rigid T = load_rigid_colmajor(P.T_dev ? P.T_dev : P.T_val.m);  // trial pose
+    const Rigid T = load_pose(P.pose);  // trial pose
     const Rigid TL = load_rigid_colmajor(T_lin_dev ? T_lin_dev : T_lin_val.m);
     float acc[1] = {0.0f};
     unsigned cnt = 0;
@@ -1090,10 +1069,7 @@ KParams make_params(const float* src, const float* scov, size_t n, const float* 
     P.rot_enable = fp->rotation_constraint_enable;
     P.rot_weight = fp->rotation_constraint_weight;
     P.rot_scale = fp->rotation_robust_scale;
-    for (int i = 0; i < 16; ++i) P.T_val.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (T && !T_dev)
-        for (int i = 0; i < 16; ++i) P.T_val.m[i] = T[i];
-    P.T_dev = T_dev ? T : nullptr;
+    P.pose = query_pose(T, T_dev);
     return P;
 }
 
@@ -1421,13 +1397,10 @@ extern "C" int sp_gicp_source_prepare(sp_gicp_source* s, const sp_gicp_target* t
     const float4* pts = reinterpret_cast<const float4*>(src_points);
     const unsigned nb = div_up(n, kBlock);
     if (sort_by_cell == SP_SOURCE_SORT) {
-        Mat4Arg tv;
-        for (int i = 0; i < 16; ++i) tv.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        if (transT && !transT_on_device)
-            for (int i = 0; i < 16; ++i) tv.m[i] = transT[i];
-        const GridDesc g = grid_desc(target->grid);
-        query_cell_kernel<<<nb, kBlock, 0, st>>>(pts, (unsigned)n, g, tv, transT_on_device ? transT : nullptr, s->keys_in,
-                                                 s->vals_in);
+        // Source ordering: key = cell (of the TARGET grid) that T*p falls into, so that consecutive lanes of the fused
+        // kernel walk consecutive cells of a grid row and their extent / point / covariance loads share cache lines.
+        query_cell_kernel<><<<nb, kBlock, 0, st>>>(pts, (unsigned)n, grid_desc(target->grid), query_pose(transT, transT_on_device),
+                                                   s->keys_in, s->vals_in);
         unsigned end_bit = 1;
         while ((1ull << end_bit) <= target->grid->ncells && end_bit < 32) ++end_bit;
         // Only locality matters, not a total order: the top 16 key bits put every run of 32 consecutive cells of an

@@ -253,8 +253,7 @@ struct FusedParams {
     GridDesc g;
     unsigned n;
     float max_d2, scale;
-    Mat4Arg T_val;
-    const float* T_dev;
+    QueryPose pose;
     const unsigned* perm;  // prepared-source order -> original source index (for the optional neighbour outputs)
     float4* ccache;        // per prepared source point: its previous correspondence (point, covariance row), 3 x float4; never null
     int cache_valid;       // 0: first linearisation after sp_gicp_source_prepare, the cache holds nothing yet
@@ -801,10 +800,7 @@ FusedParams make_fused_params(const sp_gicp_target* target, const sp_gicp_source
     P.n = (unsigned)n;
     P.max_d2 = params->max_correspondence_distance * params->max_correspondence_distance;
     P.scale = params->robust_scale;
-    for (int i = 0; i < 16; ++i) P.T_val.m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    if (transT && !transT_on_device)
-        for (int i = 0; i < 16; ++i) P.T_val.m[i] = transT[i];
-    P.T_dev = transT_on_device ? transT : nullptr;
+    P.pose = query_pose(transT, transT_on_device);
     P.perm = source->perm;
     // the cache rows are always written (sp_gicp_error_prepared reads the frozen correspondences from them); the reuse
     // switch only decides whether a later linearisation may trust them instead of searching

@@ -1,7 +1,9 @@
 // The building blocks the search structures share — GridKNN (grid.hip), the BVH (bvh.hip), the octree (octree.hip), the device
 // KD-tree search (kdtree.hip) and brute force (knn_bruteforce.hip); voxel.hip and sampling.hip borrow one piece each — held once:
 // the order-preserving float encoding, the bounding box of the finite points, the Morton key of a point in a box, the sorted
-// insertion into a register-resident list, and two one-line kernels. The kernels are templates (of nothing: launch them as
+// insertion into a register-resident list, and two one-line kernels — and, on the query side, the pose an external search is asked
+// at and the one way a kernel reads a query through it (QueryPose, query_pose, load_pose, load_query: a changed query argument
+// has one place to change; the cell key of a query lives with the grid, grid_device.h). The kernels are templates (of nothing: launch them as
 // `bbox_kernel<><<<...>>>`) so that a translation unit that launches one instantiates its own copy, with a row in its resource
 // report, and one that does not gets nothing.
 // Probed on their own by sp_internal_bbox / sp_internal_morton_keys / sp_internal_sorted_insert (spatial_probes.hip,
@@ -10,8 +12,35 @@
 #include <cfloat>
 
 #include "sp_common.h"
+#include "sp_math.h"
 
 namespace sp {
+
+// The pose an external search is asked at: a query q is searched at T * q, T column-major. `dev` names 16 floats resident on the
+// device, or is null and the matrix travels by value in `m` (the identity when the caller gave none). One kernel argument; a caller
+// that only wants the matrix by value takes the Mat4Arg it begins with.
+struct QueryPose : Mat4Arg {
+    const float* dev;
+};
+inline QueryPose query_pose(const float* transT, int transT_on_device) {
+    QueryPose P;
+    for (int i = 0; i < 16; ++i) P.m[i] = (transT && !transT_on_device) ? transT[i] : (i % 5 == 0 ? 1.0f : 0.0f);
+    P.dev = transT_on_device ? transT : nullptr;
+    return P;
+}
+__device__ __forceinline__ Rigid load_pose(const QueryPose& P) { return load_rigid_colmajor(P.dev ? P.dev : P.m); }
+// Query qi where it is searched: T * queries[qi] by transform_point's fma chain (the reference's, sp_math.h) and no other.
+__device__ __forceinline__ void load_query(const float4* __restrict__ queries, unsigned qi, const Rigid& T, float& x, float& y, float& z) {
+    const float4 q4 = queries[qi];
+    transform_point(T, q4.x, q4.y, q4.z, x, y, z);
+}
+// ... as a float4 whose .w the caller sets
+__device__ __forceinline__ float4 load_query(const float4* __restrict__ queries, unsigned qi, const Rigid& T, float w) {
+    float4 q;
+    load_query(queries, qi, T, q.x, q.y, q.z);
+    q.w = w;
+    return q;
+}
 
 // Order-preserving float -> u32 and back: a < b as floats <=> ordered_bits(a) < ordered_bits(b) as unsigned (-0 below +0).
 __host__ __device__ inline unsigned ordered_bits(float f) {

@@ -13,6 +13,7 @@
 #include "radix_sort.h"
 #include "sp_common.h"
 #include "sp_math.h"
+#include "sp_spatial.h"
 
 void sp_set_error(const char* msg);
 
@@ -126,11 +127,7 @@ __device__ __forceinline__ void decode_cov(const CovSum& s, float inv, float4* _
 // hardware form is valid)
 __device__ __forceinline__ void fadd(float* p, float v) { unsafeAtomicAdd(p, v); }
 
-inline Mat4Arg pose_arg(const float* pose16) {
-    Mat4Arg a;
-    for (int i = 0; i < 16; ++i) a.m[i] = pose16 ? pose16[i] : ((i % 5 == 0) ? 1.0f : 0.0f);
-    return a;
-}
+inline Mat4Arg pose_arg(const float* pose16) { return query_pose(pose16, 0); }  // a host pose by value, the identity for none
 
 constexpr unsigned long long kNoSlot = ~0ull;
 

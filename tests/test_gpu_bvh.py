@@ -194,6 +194,8 @@ def test_bvh_heap_kernel_equals_the_sorted_insertion_kernel(sp, orc):
         u = b.knn_search(big_q, k, T)
         b._set_option("bvh_sort_queries", 1)
         assert torch.equal(r.indices, u.indices) and torch.equal(r.distances, u.distances)
+    rd = b.knn_search(big_q, 10, dev(T.T.reshape(16)))  # the same pose resident on the device, through the ordering kernel too
+    assert torch.equal(rd.indices, r.indices) and torch.equal(rd.distances, r.distances)
     rr = both(lambda: b.radius_search(big_q, 8, 0.25, T))
     rs_small = b.radius_search(Q, 8, 0.25, T)
     assert torch.equal(rr.indices[:len(q)], rs_small.indices) and torch.equal(rr.distances[:len(q)], rs_small.distances)
@@ -236,6 +238,8 @@ def test_gridknn_sorts_many_external_queries_by_cell(sp, orc):
             bi, bd = orc.knn_bruteforce(qT, pts, k)
             for rows in (slice(0, len(q)), slice(-len(q), None)):
                 assert np.array_equal(r.indices[rows].cpu().numpy(), bi) and np.array_equal(r.distances[rows].cpu().numpy(), bd)
+        d = grid.knn_search(big, k, dev(T.T.reshape(16)))  # the same pose resident on the device, through the ordering kernel too
+        assert torch.equal(d.indices, r.indices) and torch.equal(d.distances, r.distances)
         rr = grid.radius_search(big, 6, 0.2, T)
         grid._set_option("grid_sort_queries", 0)
         ru = grid.radius_search(big, 6, 0.2, T)
