@@ -1868,3 +1868,33 @@ extern "C" int sp_internal_source_option(sp_gicp_source* s, int option, int valu
     }
     return SP_ERR_INVALID_ARGUMENT;
 }
+
+// sp_internal_block_reduce (sp_internal.h): one workgroup loads its lanes' values and calls block_reduce_store, nothing more.
+namespace sp {
+namespace {
+template <int NV, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void probe_block_reduce_kernel(const float* __restrict__ values, const uint32_t* __restrict__ counts,
+                                                                   float* __restrict__ row) {
+    float acc[NV];
+#pragma unroll
+    for (int e = 0; e < NV; ++e) acc[e] = values[(size_t)threadIdx.x * NV + e];
+    const unsigned cnt = counts[2 * threadIdx.x], extra = counts[2 * threadIdx.x + 1];
+    if (threadIdx.x >= NV + 2 && threadIdx.x < kPartial) row[threadIdx.x] = 0.0f;  // the words of a partial row no sum goes to
+    block_reduce_store<NV, BLOCK>(acc, cnt, row, false, extra);
+}
+template <int NV>
+int probe_block_reduce(const float* values, const uint32_t* counts, int block, float* row, hipStream_t st) {
+    if (block == 64) probe_block_reduce_kernel<NV, 64><<<1, 64, 0, st>>>(values, counts, row);
+    else if (block == 256) probe_block_reduce_kernel<NV, 256><<<1, 256, 0, st>>>(values, counts, row);
+    else probe_block_reduce_kernel<NV, 1024><<<1, 1024, 0, st>>>(values, counts, row);
+    return launch_status();
+}
+}  // namespace
+}  // namespace sp
+extern "C" int sp_internal_block_reduce(const float* lane_values, const uint32_t* lane_counts, int block, int nv, float* row_out,
+                                        void* stream) {
+    if (!lane_values || !lane_counts || !row_out || (block != 64 && block != 256 && block != 1024) || (nv != sp::kAcc - 1 && nv != 1))
+        return SP_ERR_INVALID_ARGUMENT;
+    return nv == 1 ? sp::probe_block_reduce<1>(lane_values, lane_counts, block, row_out, sp::as_stream(stream))
+                   : sp::probe_block_reduce<sp::kAcc - 1>(lane_values, lane_counts, block, row_out, sp::as_stream(stream));
+}

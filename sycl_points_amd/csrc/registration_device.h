@@ -39,21 +39,41 @@ template <bool SC1>
 __device__ __forceinline__ float load_row_word(const float* p) {
     return SC1 ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
+constexpr bool lanes_hold_row(int nv) {  // after wave_reduce_transposed: value l in lane l, the two integers in lanes nv, nv + 1
+    for (int l = 0; l < nv; ++l)
+        if (wave_transposed_value(nv, (unsigned)l) != l) return false;
+    return wave_transposed_value(2, (unsigned)nv) == 0 && wave_transposed_value(2, (unsigned)nv + 1) == 1;
+}
+// First stage of both block reductions: the wave's NV sums and its two integers into row[0 .. NV + 1] (the integers as bit
+// patterns). One value: the ladder to lane 63. More: wave_reduce_transposed (sp_common.h: the ladder's tree, the same bits),
+// after which lane l < NV holds the total of value l and lanes NV, NV + 1, which only repeat sums, take the two integers; each
+// of these lanes writes its one word.
+template <int NV>
+__device__ __forceinline__ void wave_sums_to_row(float (&acc)[NV], unsigned cnt, unsigned extra, unsigned lane, float* __restrict__ row) {
+    if constexpr (NV == 1) {
+        acc[0] = wave_sum_to_lane63(acc[0]);
+        cnt = wave_sum_u32_to_lane63(cnt);
+        extra = wave_sum_u32_to_lane63(extra);
+        if (lane == kWave - 1) {
+            row[0] = acc[0];
+            row[1] = __uint_as_float(cnt);
+            row[2] = __uint_as_float(extra);
+        }
+    } else {
+        static_assert(NV + 2 <= kPartial && lanes_hold_row(NV), "lane l < NV must hold value l, lanes NV and NV + 1 the integers 0 and 1");
+        unsigned c[2] = {cnt, extra};
+        const float s = wave_reduce_transposed(acc, lane);
+        const unsigned k = wave_reduce_transposed(c, lane);
+        if (lane < NV + 2) row[lane] = lane < NV ? s : __uint_as_float(k);
+    }
+}
+
 template <int NV, int BLOCK = kBlock, bool SC1 = false>
 __device__ __forceinline__ void block_reduce_store(float (&acc)[NV], unsigned cnt, float* __restrict__ partial,
                                                    bool count_as_float = false, unsigned extra = 0) {
     __shared__ float red[BLOCK / kWave][kPartial];
     const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) acc[e] = wave_sum_to_lane63(acc[e]);
-    cnt = wave_sum_u32_to_lane63(cnt);
-    extra = wave_sum_u32_to_lane63(extra);
-    if (lane == kWave - 1) {
-#pragma unroll
-        for (int e = 0; e < NV; ++e) red[wave][e] = acc[e];
-        red[wave][NV] = __uint_as_float(cnt);
-        red[wave][NV + 1] = __uint_as_float(extra);
-    }
+    wave_sums_to_row<NV>(acc, cnt, extra, lane, red[wave]);
     __syncthreads();
     if (threadIdx.x < NV) {
         float s = 0.0f;
@@ -641,16 +661,7 @@ template <int NV, int BLOCK>
 __device__ __forceinline__ void block_reduce_lds(float (&acc)[NV], unsigned cnt, unsigned extra, float* __restrict__ tot) {
     __shared__ float red[BLOCK / kWave][kPartial];
     const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) acc[e] = wave_sum_to_lane63(acc[e]);
-    cnt = wave_sum_u32_to_lane63(cnt);
-    extra = wave_sum_u32_to_lane63(extra);
-    if (lane == kWave - 1) {
-#pragma unroll
-        for (int e = 0; e < NV; ++e) red[wave][e] = acc[e];
-        red[wave][NV] = __uint_as_float(cnt);
-        red[wave][NV + 1] = __uint_as_float(extra);
-    }
+    wave_sums_to_row<NV>(acc, cnt, extra, lane, red[wave]);
     __syncthreads();
     if (threadIdx.x < NV) {
         float s = 0.0f;

@@ -115,6 +115,11 @@ int sp_internal_morton_keys(const float* points, size_t n, const float* lo3, con
  * 100); 1: (distance, index) lexicographic (kcap 1, 10, 32). */
 int sp_internal_sorted_insert(int order, int kcap, int k, const float* d, const int32_t* idx, size_t rows, size_t m, float* d_out,
                               int32_t* idx_out, void* stream);
+/* block_reduce_store (csrc/registration_device.h), the workgroup reduction that ends every launch of the registration kernels, on
+ * its own: one workgroup of `block` lanes (64, 256 or 1024); lane l brings the nv floats lane_values[l * nv ..] (nv: 28, the sums
+ * of a linearisation, or 1) and the two integers lane_counts[2 l], lane_counts[2 l + 1]. row_out: the partial row, 32 words: nv
+ * sums, the first integer's sum as a uint32 bit pattern, the second's as a float value, zeros. All device pointers. */
+int sp_internal_block_reduce(const float* lane_values, const uint32_t* lane_counts, int block, int nv, float* row_out, void* stream);
 
 #ifdef __cplusplus
 }
