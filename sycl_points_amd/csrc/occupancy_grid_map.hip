@@ -271,7 +271,9 @@ __global__ __launch_bounds__(kBlock) void ogm_prune_kernel(OgmTable t, uint32_t 
 }
 
 // rehash (:652-782): every live slot re-enters the new table through free slots only: claimed once, then copied.
-// Not VoxelHashMap's rehash kernel, on purpose: that one merges entries with atomic adds, which a table with tombstones never needs.
+// Not VoxelHashMap's rehash kernel, on purpose: that one merges entries of one key with atomic adds; this one, as the reference's,
+// keeps them apart. A table can hold a key twice: find_or_claim takes the first `deleted` slot of the key's sequence before it reaches
+// the key's own slot further along. Both entries move, the one that claims the earlier slot of the new sequence answers the lookups.
 __global__ __launch_bounds__(kBlock) void ogm_rehash_kernel(OgmTable old_t, OgmTable new_t, bool has_cov, bool has_rgb,
                                                             bool has_intensity, unsigned* __restrict__ voxel_num) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;

@@ -66,8 +66,9 @@ __global__ __launch_bounds__(kBlock) void vhm_add_kernel(Table t, const float4* 
 }
 
 // rehash (:845-931): every live slot of the old table re-enters the new one with its own time stamp.
-// Not OccupancyGridMap's rehash kernel, on purpose: a table whose probe chains vhm_remove_kernel has cut can hold one key twice, and
-// re-entering through insert() merges the two entries with its atomic adds.
+// Not OccupancyGridMap's rehash kernel, on purpose: a table whose probe chains vhm_remove_kernel has cut can hold one key twice (the
+// next insert of a key that sits behind a slot reset to `invalid` claims that slot, short of its own), and re-entering through
+// insert() merges the two entries with its atomic adds.
 __global__ __launch_bounds__(kBlock) void vhm_rehash_kernel(Table old_t, Table new_t, bool has_cov, bool has_rgb,
                                                             bool has_intensity, unsigned* __restrict__ voxel_num) {
     const unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
