@@ -410,6 +410,7 @@ INTERNAL_SIGNATURES = {
     "sp_internal_source_option": (_i, [_vp, _i, _i]),
     "sp_internal_grid_option": (_i, [_vp, _i, _i]),
     "sp_internal_bvh_option": (_i, [_vp, _i, _i]),
+    "sp_internal_bvh_walk_counts": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sp_internal_grid_small_build": (_i, [_i]),
     "sp_internal_align_searched_log": (_vp, [_vp, _vp]),
     "sp_internal_source_tile_floats": (_sz, [_vp]),
@@ -434,7 +435,8 @@ VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOX
 COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA
 FPS_FORM = {"auto": 0, "one_workgroup": 1, "per_sample": 2, "persistent": 3}  # sp_internal_fps's form
 INTERNAL_OPTION = {"stage_mask": 0, "reuse": 1, "fast_nn": 2, "self_knn_mode": 3, "persistent": 4, "persistent_from": 5,
-                   "bvh_self_heap": 6, "bvh_sort_queries": 7, "grid_sort_queries": 8, "opt_wave_query": 9, "opt_fuse_trials": 10}
+                   "bvh_self_heap": 6, "bvh_sort_queries": 7, "grid_sort_queries": 8, "opt_wave_query": 9, "opt_fuse_trials": 10,
+                   "bvh_walk_counts": 11}
 
 
 def build(force=False):

@@ -313,6 +313,13 @@ class BVH(KNNBase):
         """csrc/sp_internal.h switches of this handle (tests, comparisons)."""
         check(_lib.lib().sp_internal_bvh_option(self._h, _lib.INTERNAL_OPTION[name], int(value)))
 
+    def _walk_counts(self):
+        """(queries handed on to the sorted-insertion kernel, arena slots asked for) of the last search, which ran with
+        _set_option("bvh_walk_counts", 1): sp_internal_bvh_walk_counts (waits for that search)."""
+        handed, claims = C.c_uint32(), C.c_uint32()
+        check(_lib.lib().sp_internal_bvh_walk_counts(self._h, C.byref(handed), C.byref(claims)))
+        return int(handed.value), int(claims.value)
+
     def self_knn(self, k):
         """The cloud's own points as queries, in tree order (row i = neighbours of point i)."""
         res = KNNResult()

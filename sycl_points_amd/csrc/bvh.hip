@@ -38,6 +38,10 @@ struct sp_bvh {
     mutable sp::StreamSet streams;
     int sort_queries = 1;     // external queries (>= 400 k of them) searched in the order of the tree's curve (0: as given)
     int self_heap = 1;        // searches by bvh_heap_kernel (0: the sorted-insertion kernel alone; tests, comparisons)
+    int walk_counts = 0;      // 1: every search leaves its two walk counters in `counts` (tests; 0: nothing is copied)
+    mutable unsigned* counts = nullptr;          // 2 device words, allocated by the first search that keeps them
+    mutable hipStream_t counts_stream = nullptr; // the stream of that search's copy
+    mutable bool counts_valid = false;
 };
 
 namespace sp {
@@ -662,6 +666,16 @@ void launch_heap(const sp_bvh* b, const float4* q, unsigned nq, int k, const Que
         bvh_search_kernel<OLDK><<<g, kBlock, 0, st>>>(b->node, b->obox, b->pts, n, q, nq, k, pose, idx, d2, 0.0f, todo, todo_count);
 }
 
+// SP_INTERNAL_BVH_WALK_COUNTS: the search's two counters (`src`: the words behind todo_count; null: a search without the heap
+// kernel, zeros) into the handle's own two words, behind the search on its stream.
+int bvh_keep_walk_counts(const sp_bvh* b, const unsigned* src, hipStream_t st) {
+    if (!b->counts && pooled_alloc(&b->counts, 2 * sizeof(unsigned), st) != hipSuccess) return SP_ERR_HIP;
+    b->counts_stream = st;
+    b->counts_valid = true;
+    if (!src) return zero_async(b->counts, 2 * sizeof(unsigned), st);
+    return hipMemcpyAsync(b->counts, src, 2 * sizeof(unsigned), hipMemcpyDeviceToDevice, st) == hipSuccess ? SP_OK : SP_ERR_HIP;
+}
+
 // radius_sq < 0: plain kNN
 int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const float* transT, int transT_on_device,
                  int32_t* idx_out, float* d2_out, hipStream_t st, float radius_sq = -1.0f) {
@@ -705,6 +719,7 @@ int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const 
                                 : k == 21 ? launch_heap<21, 32> : launch_heap<32, 32>;
             launch(b, q, nq, kk, pose, radius_sq, idx_out, d2_out, todo, todo_count, order, deep, arena_slots, st);
             rc = launch_status();
+            if (rc == SP_OK && b->walk_counts) rc = bvh_keep_walk_counts(b, todo_count, st);
         }
         StreamSet used;
         used.note(st);
@@ -716,7 +731,8 @@ int bvh_dispatch(const sp_bvh* b, const float4* q, unsigned nq, size_t k, const 
     else if (k <= 10) launch_bvh<10>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
     else if (k <= 20) launch_bvh<20>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
     else launch_bvh<32>(b, q, nq, kk, pose, idx_out, d2_out, st, radius_sq);
-    return launch_status();
+    const int rc = launch_status();
+    return rc == SP_OK && b->walk_counts ? bvh_keep_walk_counts(b, nullptr, st) : rc;
 }
 
 }  // namespace
@@ -728,6 +744,7 @@ extern "C" void sp_bvh_destroy(sp_bvh* b) {
     sp::pooled_free_after(b->node, b->streams);
     sp::pooled_free_after(b->obox, b->streams);
     sp::pooled_free_after(b->bbox, b->streams);
+    sp::pooled_free_after(b->counts, b->streams);
     delete b;
 }
 
@@ -795,7 +812,23 @@ extern "C" int sp_internal_bvh_option(sp_bvh* b, int option, int value) {
     if (!b) return SP_ERR_INVALID_ARGUMENT;
     if (option == SP_INTERNAL_BVH_SELF_HEAP) b->self_heap = value;
     else if (option == SP_INTERNAL_BVH_SORT_QUERIES) b->sort_queries = value;
+    else if (option == SP_INTERNAL_BVH_WALK_COUNTS) { b->walk_counts = value; b->counts_valid = false; }
     else return SP_ERR_INVALID_ARGUMENT;
+    return SP_OK;
+}
+
+extern "C" int sp_internal_bvh_walk_counts(const sp_bvh* b, uint32_t* handed_on_out, uint32_t* arena_claims_out) {
+    if (!b || !handed_on_out || !arena_claims_out) return SP_ERR_INVALID_ARGUMENT;
+    if (!b->counts_valid) {
+        sp_set_error("[BVH] no search has kept its walk counters (SP_INTERNAL_BVH_WALK_COUNTS)");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
+    unsigned host[2] = {0u, 0u};
+    if (hipStreamSynchronize(b->counts_stream) != hipSuccess ||
+        hipMemcpy(host, b->counts, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
+        return SP_ERR_HIP;
+    *handed_on_out = host[0];
+    *arena_claims_out = host[1];
     return SP_OK;
 }
 

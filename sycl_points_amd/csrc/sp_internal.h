@@ -48,12 +48,20 @@ enum {
     /* sp_gicp_source: sp_gicp_align_optimize, wave-per-point launches of up to 2048 points: an LM / dog-leg trial step also
      * linearises at the trial pose (1, default: an accepted trial's next linearisation is then already there) or not (0). The
      * same sequence of optimiser decisions either way. */
-    SP_INTERNAL_OPT_FUSE_TRIALS = 10
+    SP_INTERNAL_OPT_FUSE_TRIALS = 10,
+    /* sp_bvh: every search also leaves its two walk counters — queries the heap kernel handed on to the sorted-insertion kernel,
+     * slots of the deep-stack arena claimed — in two words the handle owns, copied behind the search on its stream (1), or
+     * nothing is copied (0, default). Read with sp_internal_bvh_walk_counts. Same launches, same lists either way. */
+    SP_INTERNAL_BVH_WALK_COUNTS = 11
 };
 
 int sp_internal_source_option(sp_gicp_source* source, int option, int value);
 int sp_internal_grid_option(sp_grid* grid, int option, int value);
 int sp_internal_bvh_option(sp_bvh* bvh, int option, int value);
+/* The walk counters of the handle's last search under SP_INTERNAL_BVH_WALK_COUNTS (waits for that search's stream): zeros for a
+ * search that did not go through the heap kernel; SP_ERR_INVALID_ARGUMENT when no search has kept any. An arena claim is counted
+ * for every lane that asked for a slot, served or not. */
+int sp_internal_bvh_walk_counts(const sp_bvh* bvh, uint32_t* handed_on_out, uint32_t* arena_claims_out);
 /* Process-wide: grids of up to 8192 points and fewer than 32768 cells are built by one launch of one workgroup (1, default) or by the
  * general chain of launches (0); < 0 only asks. Returns the previous setting. Same structure bit for bit. */
 int sp_internal_grid_small_build(int enable);
