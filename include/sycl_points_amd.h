@@ -917,6 +917,35 @@ int sp_gicp_source_set_persistent(sp_gicp_source* source, int enable);
  * target whose cells are crowded (sp_grid_max_cell_points in the hundreds or thousands: a raw LiDAR scan), where a lane's walk
  * through its block of cells is thousands of candidates long. Same correspondences in every mode. */
 int sp_gicp_source_set_wave_per_point(sp_gicp_source* source, int mode);
+/* MI355X extension: the same alignment (registration.hpp:201-276 with pipeline/robust.hpp:78-111 around it, every
+ * OptimizationMethod, as sp_gicp_align_optimize runs it) of ONE prepared source against ONE prepared target from `batch` initial
+ * guesses in ONE launch — relocalisation, start-up without a pose, a yaw sweep, loop-closure checks. The reference has no such
+ * call: it would run align() once per guess, `batch` times the round trips of one alignment. Here workgroup b of a plain grid of
+ * `batch` workgroups (256 lanes up to 256 source points, 1024 beyond) runs the whole alignment of hypothesis b: linearise and
+ * trial steps over the source, the step's totals summed in LDS, one lane running the optimiser's state machine. A hypothesis
+ * keeps its correspondence-cache rows (3 x float4 per point) in the caller's workspace, so the workgroups share nothing they
+ * write and none waits for another: the launch needs no residency, works for any batch on any stream (a capturing one too, and
+ * beside another stream's persistent launch), ignores sp_gicp_source_set_persistent / sp_gicp_source_set_wave_per_point, and
+ * neither reads nor writes the source's own correspondence cache — an alignment of the same source before or after behaves as if
+ * the batch had never run. The first linearisation of every hypothesis searches every point; later ones reuse the hypothesis's
+ * own rows under the target's certificates.
+ *   T_init_device   batch x 16 floats, column-major poses            T_out_device  the final poses (may alias T_init_device)
+ *   results_device  batch blocks, each as sp_gicp_align_optimize writes its one (status always 0, pad[0] = SP_ALIGN_RESULT_DONE last)
+ *   workspace       sp_gicp_align_batch_workspace_bytes(n, batch) bytes, at least batch * 48 * n; that function returns 0 for
+ *                   n == 0, n > SP_ALIGN_BATCH_MAX_POINTS, batch == 0 or batch > SP_ALIGN_BATCH_MAX
+ * Only enqueues. Arguments as for sp_gicp_align_optimize (n_levels, method, max_iterations in 1..65535, reg_type as the target
+ * was prepared, no rotation constraint); SP_ERR_INVALID_ARGUMENT with a message, and nothing enqueued, also when batch or the
+ * source's point count is outside the ranges above, the workspace is too small, or the target has no certificates
+ * (sp_gicp_target_create_plain without sp_gicp_target_certify: there are no rows to freeze trials on).
+ * sp_align_best_host (host memory only): the block with the most inliers among those with status 0, a finite pose, a finite
+ * error and inlier > 0; ties to the smaller error, then to the lower index. *best_out = batch when no block qualifies (SP_OK). */
+enum { SP_ALIGN_BATCH_MAX_POINTS = 16384, SP_ALIGN_BATCH_MAX = 65535 };
+size_t sp_gicp_align_batch_workspace_bytes(size_t n, size_t batch);
+int sp_gicp_align_batch(const sp_gicp_target* target, const sp_gicp_source* source, const float* T_init_device,
+                        float* T_out_device, size_t batch, const sp_factor_params* params, const sp_opt_params* opt,
+                        const float* robust_scales, int n_levels, sp_align_result* results_device, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int sp_align_best_host(const sp_align_result* results_host, size_t batch, size_t* best_out);
 /* The same optimiser for a HOST-driven loop (registration.hpp:201-276 around optimize_gauss_newton :803-828,
  * optimize_levenberg_marquardt :830-895, optimize_powell_dogleg :897-964, and pipeline/robust.hpp:100-111 for n_levels > 1): the
  * state machine one lane of sp_gicp_align_optimize's launch runs (csrc/sp_optimizer.h), compiled for the host from the same

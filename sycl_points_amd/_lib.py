@@ -304,6 +304,10 @@ SIGNATURES = {
                                     _sz, _vp]),
     "sp_gicp_source_set_persistent": (_i, [_vp, _i]),
     "sp_gicp_source_set_wave_per_point": (_i, [_vp, _i]),
+    "sp_gicp_align_batch_workspace_bytes": (_sz, [_sz, _sz]),
+    "sp_gicp_align_batch": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(FactorParams), C.POINTER(OptParams), C.POINTER(C.c_float), _i, _vp,
+                                 _vp, _sz, _vp]),
+    "sp_align_best_host": (_i, [_vp, _sz, C.POINTER(_sz)]),
     "sp_opt_stepper_create": (_i, [C.POINTER(OptParams), _vp, C.POINTER(C.c_float), _i, C.POINTER(_vp)]),
     "sp_opt_stepper_destroy": (None, [_vp]),
     "sp_opt_stepper_next": (_i, [_vp, C.POINTER(OptRequest)]),

@@ -1976,6 +1976,64 @@ class Registration:
             return None
         return self._result_from_align_result(r)
 
+    def align_batch(self, source, prepared_target, initial_guesses, robust_scales=None, sort_by_cell=True, prepare=True):
+        """MI355X extension: Registration::align of `source` against `prepared_target` from every pose of `initial_guesses`
+        (a sequence of 4x4 matrices) in ONE launch, one workgroup per guess, and ONE read-back (sp_gicp_align_batch; the
+        reference would call align() once per guess). The source is prepared once, at initial_guesses[0] (the order only
+        decides which lane handles which point); prepare=False takes the prepared source as it is. The source's own
+        correspondence cache is left alone. Returns one result per guess, each as align_optimize returns it (`log`,
+        `linearizations`, `trials`, `searched`); Registration.best_of picks among them."""
+        L = _lib.lib()
+        p = self.params
+        guesses = [np.asarray(T, np.float32) for T in initial_guesses]
+        B, n = len(guesses), source.size()
+        dev = source.points.device
+        rsz = C.sizeof(_lib.AlignResult)
+        need = L.sp_gicp_align_batch_workspace_bytes(n, B)
+        bufs = getattr(self, "_batch_bufs", None)
+        if bufs is None or bufs[0].device != dev or bufs[0].numel() < 16 * max(B, 1) or bufs[3].numel() < need:
+            # (sized for this call, kept for the next one that fits)
+            bufs = (torch.zeros(16 * max(B, 1), dtype=torch.float32, device=dev),
+                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8, device=dev),
+                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8).pin_memory(),
+                    torch.empty(max(need, 16), dtype=torch.uint8, device=dev))
+            self._batch_bufs = bufs
+        T_dev, res_dev, res_host, ws = bufs
+        if B:
+            poses = np.stack([_T16(T).reshape(-1) for T in guesses])  # one copy up
+            T_dev[:16 * B].copy_(torch.from_numpy(poses.reshape(-1).copy()), non_blocking=True)
+        psrc, _ = self._prepared_source(n)
+        if prepare:
+            psrc.prepare(prepared_target, source, guesses[0] if B else None, sort_by_cell)
+        scales = list(robust_scales) if robust_scales else [p.robust_default_scale]
+        fp = self._factor_params(scales[0])
+        op = self.opt_params()
+        sc = (C.c_float * len(scales))(*scales)
+        check(L.sp_gicp_align_batch(prepared_target._h, psrc._h, _ptr(T_dev), _ptr(T_dev), B, C.byref(fp), C.byref(op), sc, len(scales),
+                                    _ptr(res_dev), _ptr(ws), ws.numel(), _stream()))
+        res_host[:rsz * B].copy_(res_dev[:rsz * B], non_blocking=True)  # one copy down
+        torch.cuda.current_stream().synchronize()
+        raw = res_host[:rsz * B].numpy().tobytes()
+        out = []
+        for b in range(B):
+            res = self._result_from_align_result(_lib.AlignResult.from_buffer_copy(raw, rsz * b))
+            res.block = raw[rsz * b:rsz * (b + 1)]  # the sp_align_result as the launch wrote it
+            out.append(res)
+        return out
+
+    @staticmethod
+    def best_of(results):
+        """Index of the best hypothesis of align_batch (sp_align_best_host): the most inliers among results with a finite pose, a
+        finite error and at least one inlier; ties to the smaller error, then to the lower index. len(results) when none
+        qualifies."""
+        blocks = (_lib.AlignResult * max(len(results), 1))()
+        for blk, r in zip(blocks, results):
+            blk.T[:] = [float(v) for v in _T16(np.asarray(r.T, np.float32)).reshape(-1)]
+            blk.error, blk.inlier, blk.status = float(r.error), int(r.inlier), 0
+        best = C.c_size_t(len(results))
+        check(_lib.lib().sp_align_best_host(C.byref(blocks), len(results), C.byref(best)))
+        return int(best.value)
+
     @staticmethod
     def _result_from_align_result(r):
         res = RegistrationResult()
