@@ -434,6 +434,7 @@ INTERNAL_SIGNATURES = {
     "sp_internal_morton_keys": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp]),
     "sp_internal_sorted_insert": (_i, [_i, _i, _i, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "sp_internal_block_reduce": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "sp_internal_finish_wave": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOXEL_BOX_SHARD_STRIDE
 COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA

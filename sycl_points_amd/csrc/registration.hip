@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "registration_device.h"
+#include "sp_wave_solve.h"
 #include "sp_cov_normal.h"
 
 namespace sp {
@@ -391,6 +392,32 @@ __global__ void gn_update_kernel(sp_linearized* lin, float* T, float lambda, flo
     if (threadIdx.x == 0 && blockIdx.x == 0) gn_update_impl(lin, T, lambda, crit_rot, crit_trans, delta_out8, true, ldlt_ws);
 }
 
+// sp_internal_finish_wave (sp_internal.h): one wave per case runs the wave form of the iteration finish (sp_wave_solve.h) on that
+// case's totals, as wave 0 of the alignment kernels does: totals and pose in LDS, the pose updated in place.
+__global__ __launch_bounds__(kWave) void finish_wave_kernel(const float* __restrict__ totals, const float* __restrict__ params,
+                                                            float* T, float* __restrict__ delta8, float* __restrict__ x) {
+    __shared__ float tot[32];
+    __shared__ float sT[16];
+    __shared__ float sdelta[8];
+    const size_t c = blockIdx.x;
+    const unsigned lane = threadIdx.x;
+    if (lane < 30) tot[lane] = totals[c * 30 + lane];
+    if (lane < 16) sT[lane] = T[c * 16 + lane];
+    __syncthreads();
+    WaveLanesDevice w(lane);
+    float d[6];
+    wave_gn_update(w, tot, sT, params[c * 3], params[c * 3 + 1], params[c * 3 + 2], sdelta, d);
+    __syncthreads();
+    if (lane < 16) T[c * 16 + lane] = sT[lane];
+    if (lane < 8) delta8[c * 8 + lane] = sdelta[lane];
+    if (lane < 6) {
+        float v = d[0];
+#pragma unroll
+        for (unsigned e = 1; e < 6; ++e) v = lane == e ? d[e] : v;
+        x[c * 6 + lane] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Fused GICP iteration on a prepared target (GridKNN + plane-regularised covariances stored in grid order).
 //
@@ -634,31 +661,46 @@ __device__ __forceinline__ bool align_begin(const float* T_init, const AlignStat
 // from the point loop's. The step alone changes nothing; the whole prologue brings the POINT_TO_DISTRIBUTION instantiations from
 // 1-5 spilled registers to 1-2 but gives every instantiation a 184-byte stack frame per lane. Inlined, the GICP instantiations
 // have no spill except Tukey's one register.)
-// One lane finishes an iteration: its totals (red0: 28 sums, the uint32 count, the searched count as a float value) at the pose
-// in sT -> solve_linear_system + pose update + is_converged (registration.hpp:791-828, 407-410). The step is applied to sT IN
-// PLACE (no copy, no second barrier on the path every workgroup waits on: sdelta[6] > 0.5 says converged). `publish`: this
-// workgroup also writes the state after the iteration to *so, its searched-point count to log[k] and the system to *lin_out.
+// Wave 0 finishes an iteration (every lane of it calls this): its totals (red0: 28 sums, the uint32 count, the searched count as a
+// float value) at the pose in sT -> solve_linear_system + pose update + is_converged (registration.hpp:791-828, 407-410), in the
+// wave form of sp_wave_solve.h: the lanes read their rows of H and b straight from the totals, no sp_linearized in between. The
+// step is applied to sT IN PLACE (no copy, no second barrier on the path every workgroup waits on: sdelta[6] > 0.5 says
+// converged). `publish`: this workgroup also writes the state after the iteration to *so, its searched-point count to log[k] and
+// the system to *lin_out — a lane per word, out of registers and the totals, after the pose is in sT.
 __device__ __forceinline__ void finish_iteration(const float* red0, float* sT, float lambda, float crit_rot, float crit_trans,
-                                                 unsigned prev_iterations, sp_linearized* slin, float* sdelta, LdltScratch* ws,
-                                                 bool publish, AlignState* so, unsigned* log, int k, sp_linearized* lin_out) {
-    if (publish) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) so->T_lin[i] = sT[i];
-    }
-    unpack_totals(red0, kAcc - 1, slin);
-    gn_update_impl(slin, sT, lambda, crit_rot, crit_trans, sdelta, false, *ws);
+                                                 unsigned prev_iterations, float* sdelta, bool publish, AlignState* so,
+                                                 unsigned* log, int k, sp_linearized* lin_out) {
+    const unsigned lane = threadIdx.x;  // < kWave
+    float t_lin = 0.0f;
+    if (publish && lane < 16) t_lin = sT[lane];
+    WaveLanesDevice w(lane);
+    float delta[6];
+    wave_gn_update(w, red0, sT, lambda, crit_rot, crit_trans, sdelta, delta);
     if (publish) {
         const unsigned searched = (unsigned)red0[kAcc];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) so->T[i] = sT[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) so->delta[i] = sdelta[i];
-        so->converged = sdelta[6] > 0.5f ? 1u : 0u;
-        so->iterations = prev_iterations + 1;
-        so->searched = searched;
-        so->pad = 0;
-        if (log && k < kSearchedLog) log[k] = searched;
-        if (lin_out) *lin_out = *slin;
+        if (lane < 16) {
+            so->T[lane] = w.s.out;
+            so->T_lin[lane] = t_lin;
+            if (lane < 8) so->delta[lane] = w.s.d8;
+            if (lane == 6) so->converged = w.s.d8 > 0.5f ? 1u : 0u;
+            if (lane == 8) so->iterations = prev_iterations + 1;
+            if (lane == 9) {
+                so->searched = searched;
+                if (log && k < kSearchedLog) log[k] = searched;
+            }
+            if (lane == 10) so->pad = 0;
+        }
+        if (lin_out && lane < sizeof(sp_linearized) / 4) {  // unpack_totals, word by word
+            const unsigned cnt = __float_as_uint(red0[kAcc - 1]);
+            const unsigned a = lane / 6, c = lane % 6;
+            unsigned v = 0;  // pad
+            if (lane < 36) v = __float_as_uint(red0[a <= c ? tri6(a, c) : tri6(c, a)]);
+            else if (lane < 43) v = __float_as_uint(red0[21 + (lane - 36)]);  // b, error
+            else if (lane == 43) v = cnt;
+            else if (lane == 44) v = __float_as_uint((float)(cnt & 4095u));
+            else if (lane == 45) v = __float_as_uint((float)(cnt >> 12));
+            reinterpret_cast<unsigned*>(lin_out)[lane] = v;
+        }
     }
 }
 
@@ -787,9 +829,7 @@ __device__ __forceinline__ void align_store_late_state(const AlignArgs& A) {
 template <bool SHARDED>
 __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, unsigned* sflag) {
     __shared__ float red[kFinalThreads / 32][kPartial];
-    __shared__ sp_linearized slin;
     __shared__ float sdelta[8];
-    __shared__ LdltScratch ldlt_ws;
     if (A.first) {
         state_store(state_load(false, nullptr, A.T_init), sT, sflag);
         // (a new alignment: the searched-point log starts empty — entry j is written when iteration j is finished; the sharded
@@ -819,10 +859,9 @@ __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, un
         zero_row();
         return false;
     }
-    if (threadIdx.x == 0)
-        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], &slin, sdelta, &ldlt_ws, blockIdx.x == 0, A.state_out,
-                         A.searched_log,
-                         A.k, A.lin_out);
+    if (threadIdx.x < kWave)
+        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], sdelta, blockIdx.x == 0, A.state_out,
+                         A.searched_log, A.k, A.lin_out);
     __syncthreads();
     if (sdelta[6] > 0.5f) {  // converged with this step: no further linearisation (registration.hpp:266-268)
         zero_row();
@@ -899,9 +938,10 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
     const unsigned stride = gridDim.x * kAlignBlock;
     const unsigned tile = xcd_tile();
     __shared__ unsigned s_prev[2];  // converged, iterations of the state this launch starts from
-    // (state_load / state_store and, below, finish_iteration written out. This kernel's instantiations spill 6-47 registers and
-    // the count moves with the text: through the helpers five of the twenty spill between 5 fewer and 4 more, so both stay as
-    // they were written for this kernel)
+    // (state_load / state_store and, below, the finish of an iteration written out, by ONE lane — the form finish_iteration had
+    // before it became a wave function (sp_wave_solve.h). This kernel's instantiations spill up to 32 registers and the count
+    // moves with the text: through the helpers five of the twenty spilled between 5 fewer and 4 more, so both stay as they
+    // were written for this kernel; the wave form has not been tried here)
     if (A.k_begin >= 2) {  // the state after iteration k_begin - 2: the pose launch k_begin - 1 ran at, the flags
         if (threadIdx.x < 18) {
             const unsigned v = reinterpret_cast<const unsigned*>(&A.ws.state[A.k_begin & 1])[threadIdx.x < 16 ? threadIdx.x : kStateFlagWord + threadIdx.x - 16];
@@ -940,7 +980,7 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_persistent_kernel(Fuse
                 return;
             }
             reduce_rows_1024<true>(A.ws.part[(k - 1) & 1], gridDim.x, kAcc - 1, red, false, [] {});
-            if (threadIdx.x == 0) {  // (finish_iteration, written out: see the note at the top of the kernel)
+            if (threadIdx.x == 0) {  // (the one-lane finish, written out: see the note at the top of the kernel)
                 const bool publish = blockIdx.x == 0;
                 AlignState* const so = &A.ws.state[(k - 1) & 1];
                 if (publish) {
@@ -1026,9 +1066,7 @@ __global__ __launch_bounds__(kFinalThreads) void align_solve_kernel(AlignArgs A,
     __shared__ float red[kFinalThreads / 32][kPartial];
     __shared__ float sT[16];
     __shared__ unsigned sflag[2];
-    __shared__ sp_linearized slin;
     __shared__ float sdelta[8];
-    __shared__ LdltScratch ldlt_ws;
     if (!align_begin(A.T_init, A.state_in, A.state_out, A.has_prev, sT, sflag)) {
         align_publish(A.state_out, Pb);
         return;
@@ -1038,8 +1076,8 @@ __global__ __launch_bounds__(kFinalThreads) void align_solve_kernel(AlignArgs A,
         align_publish(A.state_out, Pb);
         return;
     }
-    if (threadIdx.x == 0)  // (ALIGN_FANIN / ALIGN_DIRECT: the streaming launch's last arriver has written the log entry, align_tail)
-        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], &slin, sdelta, &ldlt_ws, true, A.state_out,
+    if (threadIdx.x < kWave)  // (ALIGN_FANIN / ALIGN_DIRECT: the streaming launch's last arriver has written the log entry, align_tail)
+        finish_iteration(red[0], sT, A.lambda, A.crit_rot, A.crit_trans, sflag[1], sdelta, true, A.state_out,
                          (A.mode == ALIGN_ROWS || A.mode == ALIGN_PROLOGUE) ? A.searched_log : nullptr, A.k, A.lin_out);
     align_publish(A.state_out, Pb);
 }
@@ -1204,6 +1242,16 @@ extern "C" int sp_gn_update(sp_linearized* lin, float* T_dev, float lambda, floa
                             float* delta_out8, void* stream) {
     sp::gn_update_kernel<<<1, 64, 0, sp::as_stream(stream)>>>(lin, T_dev, lambda, crit_rotation, crit_translation,
                                                               delta_out8);
+    return sp::launch_status();
+}
+extern "C" int sp_internal_finish_wave(const float* totals, const float* params, float* T, float* delta8_out, float* x_out, size_t n,
+                                       void* stream) {
+    if (n == 0) return SP_OK;
+    if (!totals || !params || !T || !delta8_out || !x_out || n > 0x7fffffffu) {
+        sp_set_error("sp_internal_finish_wave: null pointer or too many cases");
+        return SP_ERR_INVALID_ARGUMENT;
+    }
+    sp::finish_wave_kernel<<<(unsigned)n, sp::kWave, 0, sp::as_stream(stream)>>>(totals, params, T, delta8_out, x_out);
     return sp::launch_status();
 }
 extern "C" int sp_gn_update_host(const sp_linearized* lin_host, float* T_host, float lambda, float crit_rotation,

@@ -128,6 +128,13 @@ int sp_internal_sorted_insert(int order, int kcap, int k, const float* d, const 
  * of a linearisation, or 1) and the two integers lane_counts[2 l], lane_counts[2 l + 1]. row_out: the partial row, 32 words: nv
  * sums, the first integer's sum as a uint32 bit pattern, the second's as a float value, zeros. All device pointers. */
 int sp_internal_block_reduce(const float* lane_values, const uint32_t* lane_counts, int block, int nv, float* row_out, void* stream);
+/* The wave form of the iteration finish (csrc/sp_wave_solve.h: the 6x6 LDL^T solve and the pose update on the lanes of one wave) on
+ * its own: one launch, n independent cases, one wave each. Per case: totals, 30 floats (the 21 sums of H's upper triangle row-major,
+ * the 6 of b, 3 that are not read); params, 3 floats (lambda, criteria_rotation, criteria_translation); T, 16 floats, the pose, updated
+ * in place. Out per case: delta8_out, 8 floats (delta, converged, ok, as sp_gn_update gives them); x_out, 6 floats, the raw solution of
+ * (H + lambda I) x = -b. All device pointers. */
+int sp_internal_finish_wave(const float* totals, const float* params, float* T, float* delta8_out, float* x_out, size_t n,
+                            void* stream);
 
 #ifdef __cplusplus
 }
