@@ -99,6 +99,12 @@ public:
 
     void remove_old_data() { throw_on_error(sp_vhm_remove_old_data(h_, queue_.stream())); }
 
+    /// MI355X extension: the rows Registration::align(source, map) reads (sp_vhm_prepare_registration), for the map as it is
+    /// now; reg_type SP_REG_GICP or SP_REG_POINT_TO_DISTRIBUTION. align() calls it when registration_ready() says no.
+    void prepare_registration(const int reg_type) { throw_on_error(sp_vhm_prepare_registration(h_, reg_type, queue_.stream())); }
+    bool registration_ready(const int reg_type) const { return sp_vhm_registration_ready(h_, reg_type) != 0; }
+    const sp_voxel_hash_map* handle() const { return h_; }
+
 private:
     sycl_utils::DeviceQueue queue_;
     sp_voxel_hash_map* h_ = nullptr;

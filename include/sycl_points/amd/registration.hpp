@@ -20,6 +20,7 @@
 #include <tuple>
 
 #include "features.hpp"
+#include "mapping.hpp"
 
 namespace sycl_points {
 namespace algorithms {
@@ -215,6 +216,7 @@ public:
         if (map_host_) (void)hipHostFree(map_host_);
         if (batch_dev_) (void)hipFree(batch_dev_);
         if (batch_pin_) (void)hipHostFree(batch_pin_);
+        if (vws_) (void)hipFree(vws_);
     }
     Registration(const Registration&) = delete;
     Registration& operator=(const Registration&) = delete;
@@ -320,43 +322,74 @@ public:
             throw std::runtime_error("[Registration::align] a communicator is set: only the device-resident Gauss-Newton loop "
                                      "(GICP / POINT_TO_DISTRIBUTION on a GridKNN, no host-side pose terms) is sharded");
 
-        // The host-driven loop: every decision of the optimiser (:803-964) is the library's stepper's — the state machine the
-        // device-resident launch runs (csrc/sp_optimizer.h); this loop linearises and evaluates trials where it asks for them.
-        const sp_opt_params op = opt_params();
-        sp_opt_stepper* st = nullptr;
-        throw_on_error(sp_opt_stepper_create(&op, initial_guess.data(), &robust_scale, 1, &st));
-        const std::unique_ptr<sp_opt_stepper, void (*)(sp_opt_stepper*)> owner(st, sp_opt_stepper_destroy);
-        for (;;) {
-            sp_opt_request req;
-            throw_on_error(sp_opt_stepper_next(st, &req));
-            if (req.want == SP_OPT_WANT_DONE) break;
-            TransformMatrix T;
-            std::memcpy(T.data(), req.T, sizeof req.T);
-            if (req.want == SP_OPT_WANT_LINEARIZE) {
-                LinearizedResult lin = fused ? linearize_fused(source.size(), T, robust_scale)
-                                             : linearize_generic(source, target, nn, T, robust_scale);
-                result.H_raw = lin.H; result.b_raw = lin.b; result.error_raw = lin.error;
-                if (pose_terms) apply_pose_terms(lin, T, initial_guess);  // registration.hpp:249-253
-                const sp_linearized h = to_linearized(lin);
-                throw_on_error(sp_opt_stepper_linearized(st, &h));
-                if (params_.verbose && params_.optimization_method == OptimizationMethod::GAUSS_NEWTON)
-                    std::cout << "iter [" << req.iteration << "] error: " << lin.error << ", inlier: " << lin.inlier << std::endl;
-            } else {
-                const auto [icp_error, inlier] = compute_error(source, target, T, robust_scale);
-                const float new_error = icp_error + prior_error(T);  // registration.hpp:854, :933
-                float rho = 0.0f;
-                throw_on_error(sp_opt_stepper_trial(st, new_error, inlier, &rho));
-                if (params_.verbose && params_.optimization_method == OptimizationMethod::POWELL_DOGLEG)
-                    std::cout << "iter [" << req.iteration << "] radius: " << req.damping << ", rho: " << rho
-                              << ", error: " << new_error << ", inlier: " << inlier << std::endl;
-            }
-        }
-        sp_align_result r;
-        throw_on_error(sp_opt_stepper_result(st, &r));
-        RegistrationResult out = to_registration_result(r);
-        out.H_raw = result.H_raw; out.b_raw = result.b_raw; out.error_raw = result.error_raw;
-        return out;
+        return host_loop(initial_guess, robust_scale, pose_terms,
+                         [&](const TransformMatrix& T) {
+                             return fused ? linearize_fused(source.size(), T, robust_scale) : linearize_generic(source, target, nn, T, robust_scale);
+                         },
+                         [&](const TransformMatrix& T) { return compute_error(source, target, T, robust_scale); });
     }
+
+    /// MI355X extension: align() against the VoxelHashMap itself — voxelised GICP. The target of a source point is the Gaussian
+    /// of the voxel T p falls into (set_voxel_neighbors(7) / (27): of the nearest voxel mean among that cell and its 6 face /
+    /// all 26 neighbours); the correspondence is a hash lookup, so there is no export, no tree and no covariance estimation
+    /// per keyframe (what Submap::build_submap pays to hand the other overload a target). GICP and POINT_TO_DISTRIBUTION, no
+    /// rotation constraint. The map's registration rows are refreshed here when the map has changed since they were made.
+    /// The optimiser loop is the host-driven one of the other overload: every OptimizationMethod, degenerate regularisation, the
+    /// MAP prior, verbose.
+    RegistrationResult align(const PointCloudShared& source, mapping::VoxelHashMap& target_map,
+                             const TransformMatrix& initial_guess = TransformMatrix::Identity(),
+                             const ExecutionOptions& options = ExecutionOptions()) {
+        RegistrationResult result;
+        result.T.matrix() = initial_guess;
+        const size_t N = source.size();
+        if (N == 0) return result;
+        if ((params_.reg_type != RegType::GICP && params_.reg_type != RegType::POINT_TO_DISTRIBUTION) || params_.rotation_constraint.enable)
+            throw std::invalid_argument("[Registration::align] a VoxelHashMap target: GICP or POINT_TO_DISTRIBUTION without the "
+                                        "rotation constraint");
+        if (params_.reg_type == RegType::GICP && !source.has_cov())
+            throw std::runtime_error("[Registration::validate_params] Covariance matrices of source and target must be "
+                                     "pre-computed before performing GICP matching.");
+        if (comm_ != nullptr || xchg_ != nullptr)
+            throw std::runtime_error("[Registration::align] a communicator is set: only the device-resident Gauss-Newton loop "
+                                     "(GICP / POINT_TO_DISTRIBUTION on a GridKNN, no host-side pose terms) is sharded");
+        if (params_.robust.type != robust::RobustLossType::NONE && params_.robust.default_scale <= 0.0f) {
+            std::cout << "[Caution] `robust.default_scale` must be greater than zero. Disable robust loss." << std::endl;
+            params_.robust.type = robust::RobustLossType::NONE;
+        }
+        const float robust_scale = options.robust_scale > 0.0f ? options.robust_scale : params_.robust.default_scale;
+        const bool pose_terms = params_.degenerate_reg.type != DegenerateRegularizationType::none || prior_active();
+        const int reg = int(params_.reg_type);
+        if (!target_map.registration_ready(reg)) target_map.prepare_registration(reg);
+        const size_t need = sp_vhm_registration_workspace_bytes(N);
+        if (vws_bytes_ < need) {
+            if (vws_) hip_check(hipFree(vws_), "hipFree");
+            vws_ = nullptr; vws_bytes_ = 0;
+            hip_check(hipMalloc(&vws_, need), "hipMalloc");
+            vws_bytes_ = need;
+        }
+        throw_on_error(sp_vhm_prepare_source(source.covs_device(), N, reg, vws_, vws_bytes_, queue_.stream()));
+        fused_loop_active_ = last_lin_fused_ = false;  // (compute_error_frozen: nothing of this alignment lies in neighbors_ or the cache)
+        const sp_factor_params fp = factor_params(robust_scale);
+        return host_loop(initial_guess, robust_scale, pose_terms,
+                         [&](const TransformMatrix& T) {
+                             throw_on_error(sp_vhm_linearize(target_map.handle(), source.points_device(), N, T.data(), 0, &fp, voxel_neighbors_,
+                                                             lin_dev_, nullptr, vws_, vws_bytes_, queue_.stream()));
+                             return to_result(read_lin());
+                         },
+                         [&](const TransformMatrix& T) {
+                             throw_on_error(sp_vhm_error(target_map.handle(), source.points_device(), N, T.data(), 0, &fp, lin_dev_, vws_,
+                                                         vws_bytes_, queue_.stream()));
+                             const sp_linearized h = read_lin();
+                             return std::tuple<float, uint32_t>{h.error, h.inlier};
+                         });
+    }
+    /// The cells a source point probes in align(source, map): 1 (default) its own, 7 with the face neighbours, 27 all of 3x3x3.
+    void set_voxel_neighbors(int neighbor_voxels) {
+        if (neighbor_voxels != 1 && neighbor_voxels != 7 && neighbor_voxels != 27)
+            throw std::invalid_argument("[Registration::set_voxel_neighbors] 1, 7 or 27");
+        voxel_neighbors_ = neighbor_voxels;
+    }
+    int voxel_neighbors() const { return voxel_neighbors_; }
 
     /// MI355X extension: pipeline::RobustAligner's annealing loop (pipeline/robust.hpp:100-111) — one align() per robust scale,
     /// each starting from the pose the previous one ended on — with all levels in ONE launch and ONE read-back when align()
@@ -568,6 +601,47 @@ public:
     std::pair<uint32_t, uint32_t> last_optimizer_steps() const { return {last_opt_linearizations_, last_opt_trials_}; }
 
 private:
+    /// The host-driven loop of align(): every decision of the optimiser (registration.hpp:803-964) is the library's stepper's — the
+    /// state machine the device-resident launch runs (csrc/sp_optimizer.h); this loop linearises (linearize(T) -> LinearizedResult)
+    /// and evaluates trials (trial_error(T) -> {error, inlier} over the correspondences of the last linearisation) where it asks.
+    template <class Linearize, class TrialError>
+    RegistrationResult host_loop(const TransformMatrix& initial_guess, float robust_scale, bool pose_terms, Linearize&& linearize,
+                                 TrialError&& trial_error) {
+        RegistrationResult result;
+        const sp_opt_params op = opt_params();
+        sp_opt_stepper* st = nullptr;
+        throw_on_error(sp_opt_stepper_create(&op, initial_guess.data(), &robust_scale, 1, &st));
+        const std::unique_ptr<sp_opt_stepper, void (*)(sp_opt_stepper*)> owner(st, sp_opt_stepper_destroy);
+        for (;;) {
+            sp_opt_request req;
+            throw_on_error(sp_opt_stepper_next(st, &req));
+            if (req.want == SP_OPT_WANT_DONE) break;
+            TransformMatrix T;
+            std::memcpy(T.data(), req.T, sizeof req.T);
+            if (req.want == SP_OPT_WANT_LINEARIZE) {
+                LinearizedResult lin = linearize(T);
+                result.H_raw = lin.H; result.b_raw = lin.b; result.error_raw = lin.error;
+                if (pose_terms) apply_pose_terms(lin, T, initial_guess);  // registration.hpp:249-253
+                const sp_linearized h = to_linearized(lin);
+                throw_on_error(sp_opt_stepper_linearized(st, &h));
+                if (params_.verbose && params_.optimization_method == OptimizationMethod::GAUSS_NEWTON)
+                    std::cout << "iter [" << req.iteration << "] error: " << lin.error << ", inlier: " << lin.inlier << std::endl;
+            } else {
+                const auto [icp_error, inlier] = trial_error(T);
+                const float new_error = icp_error + prior_error(T);  // registration.hpp:854, :933
+                float rho = 0.0f;
+                throw_on_error(sp_opt_stepper_trial(st, new_error, inlier, &rho));
+                if (params_.verbose && params_.optimization_method == OptimizationMethod::POWELL_DOGLEG)
+                    std::cout << "iter [" << req.iteration << "] radius: " << req.damping << ", rho: " << rho
+                              << ", error: " << new_error << ", inlier: " << inlier << std::endl;
+            }
+        }
+        sp_align_result r;
+        throw_on_error(sp_opt_stepper_result(st, &r));
+        RegistrationResult out = to_registration_result(r);
+        out.H_raw = result.H_raw; out.b_raw = result.b_raw; out.error_raw = result.error_raw;
+        return out;
+    }
     sp_factor_params factor_params(float robust_scale) const {
         return sp_factor_params{int(params_.reg_type), int(params_.robust.type), params_.max_correspondence_distance,
                                 robust_scale, genz_alpha_, params_.genz.planarity_threshold,
@@ -900,6 +974,9 @@ private:
     size_t batch_dev_bytes_ = 0;
     char* batch_pin_ = nullptr;  // ... and pinned host memory for the poses going up and the blocks coming back
     size_t batch_pin_bytes_ = 0;
+    void* vws_ = nullptr;  // align(source, map): partial rows | frozen slots | prepared source rows (sp_vhm_registration_workspace_bytes)
+    size_t vws_bytes_ = 0;
+    int voxel_neighbors_ = 1;
     knn::GridKNN::Ptr kd_grid_;        // GridKNN standing in for the caller's KDTree (grid_for)
     uint64_t kd_grid_tree_id_ = 0;
 };

@@ -1351,6 +1351,50 @@ int sp_vhm_overlap_ratio(const sp_voxel_hash_map* map, const float* points, size
                          float* ratio_out_host, void* stream);
 int sp_vhm_remove_old_data(sp_voxel_hash_map* map, void* stream);
 
+/* Voxelised GICP: a scan aligned against the map itself (MI355X extension; the reference exports the voxel means, builds a
+ * KD-tree on them, estimates covariances and searches a neighbour per point per iteration, submapping.hpp). The target of a
+ * source point is the Gaussian of a voxel (its mean, the exp of its mean log-covariance); the correspondence is a hash lookup.
+ *   sp_vhm_prepare_registration  three float4 per table slot, indexed as the table's keys are, in an array the map owns
+ *                        (allocated at the first call, again after a grow): row 0 = mean xyz, w = 1 when the voxel counts
+ *                        (count >= min_num_point, count != 0) else 0; rows 1-2 = (xx, xy, xz, yy | yz, zz, 0, 0) of
+ *                        SP_REG_GICP: V diag(1e-3, 1, 1) V^T of the voxel covariance; SP_REG_POINT_TO_DISTRIBUTION: its inverse
+ *                        (zero when |det| < 1e-6). One launch, one lane per slot; enqueue only. The rows are valid for the map's
+ *                        GENERATION, a counter that add_point_cloud, a rehash, remove_old_data, clear and setting voxel_size or
+ *                        min_num_point advance. Any other reg_type, or a map without covariances: SP_ERR_INVALID_ARGUMENT,
+ *                        nothing enqueued.
+ *   sp_vhm_registration_ready    1 when the rows are those of the map's current generation and of reg_type, else 0.
+ *   sp_vhm_registration_workspace_bytes / sp_vhm_prepare_source  the workspace of an alignment of n source points: partial rows
+ *                        of the reduction | the frozen slot of every point (uint32, 0xFFFFFFFF: none) | two float4 per point,
+ *                        the packed V diag(1e-3, 1, 1) V^T of its covariance, which prepare_source fills once per alignment
+ *                        (SP_REG_POINT_TO_DISTRIBUTION reads no source covariance: nothing is enqueued, src_covs may be null).
+ *   sp_vhm_neighbor_offsets_host  the cells a source point probes, in order, as neighbor_voxels int32 triples (dx, dy, dz):
+ *                        1 = its own cell; 7 = that, then the six face neighbours; 27 = those seven, then the twelve edge and the
+ *                        eight corner neighbours. HOST only. Any other count: SP_ERR_INVALID_ARGUMENT.
+ *   sp_vhm_linearize     per source point q = T p -> the key of every probed cell (an invalid key is skipped) -> its slot (100
+ *                        probes) -> among the slots whose row has w = 1 the one whose mean is nearest to q, an exact tie to the
+ *                        earlier cell of the probing order -> rejected when |q - mean|^2 > max_correspondence_distance^2 -> else
+ *                        linearised against the voxel's row (sp_gicp_iteration_fused's algebra) and summed into *out by the fixed
+ *                        tree of sp_gicp_linearize: two runs give the same bits. The winner's slot is kept in the workspace (the
+ *                        frozen correspondence); corr_keys_out_opt (device, n entries) receives its voxel key, or ~0.
+ *   sp_vhm_error         the error of the factor at transT_trial over the slots the last sp_vhm_linearize of this map left in
+ *                        this workspace (out->error, out->inlier; the inlier gate is that linearisation's, M uses the trial
+ *                        pose's R): what an LM / dog-leg trial step asks for. SP_ERR_RUNTIME when that workspace holds no
+ *                        linearisation of this map and n; SP_ERR_INVALID_ARGUMENT when the map's generation has moved since.
+ * linearize and error only enqueue; both need sp_vhm_registration_ready(map, params->reg_type) (SP_ERR_INVALID_ARGUMENT
+ * otherwise, as for an enabled rotation constraint, a reg_type other than the two above and a workspace that is too small), and
+ * write nothing when they fail. n == 0: *out zeroed, SP_OK. All array pointers are device memory; transT as for sp_gicp_linearize. */
+int sp_vhm_prepare_registration(sp_voxel_hash_map* map, int reg_type, void* stream);
+int sp_vhm_registration_ready(const sp_voxel_hash_map* map, int reg_type);
+size_t sp_vhm_registration_workspace_bytes(size_t n);
+int sp_vhm_prepare_source(const float* src_covs, size_t n, int reg_type, void* workspace, size_t workspace_bytes, void* stream);
+int sp_vhm_neighbor_offsets_host(int neighbor_voxels, int32_t* out);
+int sp_vhm_linearize(const sp_voxel_hash_map* map, const float* src_points, size_t n, const float* transT,
+                     int transT_on_device, const sp_factor_params* params, int neighbor_voxels, sp_linearized* out,
+                     uint64_t* corr_keys_out_opt, void* workspace, size_t workspace_bytes, void* stream);
+int sp_vhm_error(const sp_voxel_hash_map* map, const float* src_points, size_t n, const float* transT_trial,
+                 int trial_on_device, const sp_factor_params* params, sp_linearized* out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- OccupancyGridMap (mapping/occupancy_grid_map.hpp:27-472)
  * The other submap of Submap::build_submap: the VoxelHashMap table (same key, same double hashing, same capacity ladder; 128
  * probes; removed slots keep a `deleted` key) whose voxels also carry a log-odds occupancy. Per voxel: sums of the map-frame hit

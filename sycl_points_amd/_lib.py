@@ -384,6 +384,13 @@ SIGNATURES = {
     "sp_vhm_downsampling": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "sp_vhm_overlap_ratio": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_f), _vp]),
     "sp_vhm_remove_old_data": (_i, [_vp, _vp]),
+    "sp_vhm_prepare_registration": (_i, [_vp, _i, _vp]),
+    "sp_vhm_registration_ready": (_i, [_vp, _i]),
+    "sp_vhm_registration_workspace_bytes": (_sz, [_sz]),
+    "sp_vhm_prepare_source": (_i, [_vp, _sz, _i, _vp, _sz, _vp]),
+    "sp_vhm_neighbor_offsets_host": (_i, [_i, _vp]),
+    "sp_vhm_linearize": (_i, [_vp, _vp, _sz, _vp, _i, C.POINTER(FactorParams), _i, _vp, _vp, _vp, _sz, _vp]),
+    "sp_vhm_error": (_i, [_vp, _vp, _sz, _vp, _i, C.POINTER(FactorParams), _vp, _vp, _sz, _vp]),
     "sp_ogm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
     "sp_ogm_destroy": (None, [_vp]),
     "sp_ogm_set": (_i, [_vp, _i, _f]),

@@ -1536,6 +1536,13 @@ class VoxelHashMap(_HashedVoxelMap):
     def remove_old_data(self):
         check(_lib.lib().sp_vhm_remove_old_data(self._h, _stream()))
 
+    def prepare_registration(self, reg_type="GICP"):
+        """sp_vhm_prepare_registration: the rows Registration.align_voxel_map reads, for the map as it is now (one launch)."""
+        check(_lib.lib().sp_vhm_prepare_registration(self._h, REG[reg_type], _stream()))
+
+    def registration_ready(self, reg_type="GICP"):
+        return bool(_lib.lib().sp_vhm_registration_ready(self._h, REG[reg_type]))
+
 
 class OccupancyGridMap(_HashedVoxelMap):
     """algorithms/mapping/occupancy_grid_map.hpp:27-190, 417 over the sp_ogm_* entry points: the log-odds submap in HBM, with
@@ -2094,6 +2101,89 @@ class Registration:
                                            _stream()))
             r = self._read_lin(lin)
             return float(r.error), int(r.inlier)
+
+        return self._host_loop(T, linearize_at, error_at, scale)
+
+    # -- voxelised GICP: the target is a VoxelHashMap (sp_vhm_linearize / sp_vhm_error)
+    def _voxel_workspace(self, n, device):
+        need = _lib.lib().sp_vhm_registration_workspace_bytes(n)
+        ws = getattr(self, "_vws", None)
+        if ws is None or ws.device != device or ws.numel() < need:
+            ws = self._vws = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def prepare_voxel_source(self, source):
+        """sp_vhm_prepare_source: the packed regularised source covariances of an alignment, into this object's workspace."""
+        n = source.size()
+        ws = self._voxel_workspace(n, source.points.device)
+        check(_lib.lib().sp_vhm_prepare_source(_ptr(source.covs if source.has_cov() else None), n, REG[self.params.reg_type], _ptr(ws),
+                                               ws.numel(), _stream()))
+
+    def linearize_voxel_map(self, source, voxel_map, pose, robust_scale=-1.0, neighbor_voxels=1, prepare_source=True,
+                            want_keys=False, lin=None, workspace_bytes=None):
+        """sp_vhm_linearize at `pose` (a 4x4 host matrix or 16 floats on the device): {"H", "b", "error", "inlier"} and, with
+        want_keys, "keys": every source point's voxel key (int64 tensor, -1 for none). lin / workspace_bytes: the output buffer
+        (48 floats on the device) and the workspace size handed to the library, for the tests of the argument checks."""
+        scale = robust_scale if robust_scale > 0 else self.params.robust_default_scale
+        n, dev = source.size(), source.points.device
+        ws = self._voxel_workspace(n, dev)
+        lin = self._buffers(dev)[1] if lin is None else lin
+        if prepare_source:
+            self.prepare_voxel_source(source)
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if want_keys else None
+        fp = self._factor_params(scale)
+        tp, on_dev, keep = _trans_arg(pose)
+        check(_lib.lib().sp_vhm_linearize(voxel_map._h, _ptr(source.points) if n else None, n, tp, on_dev, C.byref(fp),
+                                          int(neighbor_voxels), _ptr(lin), _ptr(keys), _ptr(ws),
+                                          ws.numel() if workspace_bytes is None else workspace_bytes, _stream()))
+        r = self._read_lin(lin)
+        out = {"H": np.array(r.H, np.float32).reshape(6, 6), "b": np.array(r.b, np.float32), "error": float(r.error),
+               "inlier": int(r.inlier), "lin": r}
+        if want_keys:
+            out["keys"] = keys[:n]
+        return out
+
+    def error_voxel_map(self, source, voxel_map, pose, robust_scale=-1.0, lin=None, workspace_bytes=None):
+        """sp_vhm_error at the trial `pose` over the correspondences the last linearize_voxel_map froze: (error, inlier)."""
+        scale = robust_scale if robust_scale > 0 else self.params.robust_default_scale
+        n, dev = source.size(), source.points.device
+        ws = self._voxel_workspace(n, dev)
+        lin = self._buffers(dev)[1] if lin is None else lin
+        fp = self._factor_params(scale)
+        tp, on_dev, keep = _trans_arg(pose)
+        check(_lib.lib().sp_vhm_error(voxel_map._h, _ptr(source.points) if n else None, n, tp, on_dev, C.byref(fp), _ptr(lin),
+                                      _ptr(ws), ws.numel() if workspace_bytes is None else workspace_bytes, _stream()))
+        r = self._read_lin(lin)
+        return float(r.error), int(r.inlier)
+
+    def align_voxel_map(self, source, voxel_map, initial_guess=None, robust_scale=-1.0, neighbor_voxels=1):
+        """Registration::align against a VoxelHashMap (MI355X extension): distribution-to-distribution against the Gaussian of
+        the voxel each source point falls into (or of the nearest mean among 7 / 27 cells), the correspondence by hash lookup
+        and no tree. The host-driven optimiser loop of align(): every optimisation method, degenerate regularisation, the MAP
+        prior. The map's registration rows are refreshed here when they are not those of the map as it is now."""
+        p = self.params
+        result = RegistrationResult()
+        result.T = identity() if initial_guess is None else np.array(initial_guess, np.float32)
+        if source.size() == 0:
+            return result
+        if p.reg_type not in ("GICP", "POINT_TO_DISTRIBUTION") or p.rotation_constraint_enable:
+            raise SpError(1, "align_voxel_map: GICP / POINT_TO_DISTRIBUTION without the rotation constraint")
+        if p.reg_type == "GICP" and not source.has_cov():
+            raise SpError(2, "[Registration::validate_params] Covariance matrices of source and target must be "
+                             "pre-computed before performing GICP matching.")
+        if p.robust_type != "NONE" and p.robust_default_scale <= 0.0:
+            p.robust_type = "NONE"
+        scale = robust_scale if robust_scale > 0 else p.robust_default_scale
+        if not voxel_map.registration_ready(p.reg_type):
+            voxel_map.prepare_registration(p.reg_type)
+        self.prepare_voxel_source(source)
+        T = _T16(result.T).copy().reshape(-1)
+
+        def linearize_at(Tcol):
+            return self.linearize_voxel_map(source, voxel_map, Tcol.reshape(4, 4).T, scale, neighbor_voxels, prepare_source=False)["lin"]
+
+        def error_at(Tcol, Tlin_col):
+            return self.error_voxel_map(source, voxel_map, Tcol.reshape(4, 4).T, scale)
 
         return self._host_loop(T, linearize_at, error_at, scale)
 

@@ -12,14 +12,14 @@
 // Host-side control flow (rehash schedule, staleness counter, has_* flags) follows :117-141 line by line; like the
 // reference, add_point_cloud waits for its kernel and reads the voxel count back.
 
-#include "sp_voxel_table.h"
+#include "voxel_hash_map.h"
 
 namespace sp {
 namespace {
 
-constexpr unsigned kMaxProbe = 100;      // voxel_hash_map.hpp:505
+constexpr unsigned kMaxProbe = kVhmMaxProbe;
 
-using Table = VoxelTable<float4>;  // core: sum_x, sum_y, sum_z, count (uint32 bits)
+using Table = VhmTable;
 
 // global_reduction (:549-585): claim the first free slot or find the key's slot within kMaxProbe probes, then add.
 // An entry that finds neither is dropped, as in the reference.
@@ -132,10 +132,6 @@ struct EnoughPoints {
 }  // namespace
 }  // namespace sp
 
-struct sp_voxel_hash_map : sp::VoxelMapState<float4> {
-    uint32_t max_staleness = 100, remove_old_data_cycle = 10, min_num_point = 1, staleness_counter = 0;
-};
-
 namespace sp {
 namespace {
 
@@ -154,6 +150,7 @@ int remove_old(sp_voxel_hash_map* m, hipStream_t st) {
     if (m->staleness_counter <= m->max_staleness) return SP_OK;
     int rc = m->write_counter(st, 0);
     if (rc != SP_OK) return rc;
+    m->touch();
     vhm_remove_kernel<<<div_up(m->t.capacity, kBlock), kBlock, 0, st>>>(m->t, m->staleness_counter - m->max_staleness,
                                                                       m->counter);
     if ((rc = m->read_voxel_num(st)) == SP_OK) drop_flags_when_empty(m);
@@ -166,10 +163,14 @@ int remove_old(sp_voxel_hash_map* m, hipStream_t st) {
 extern "C" int sp_vhm_create(float voxel_size, void* stream, sp_voxel_hash_map** out) {
     return sp::create_map(voxel_size, stream, out);
 }
-extern "C" void sp_vhm_destroy(sp_voxel_hash_map* m) { sp::destroy_map(m); }
+extern "C" void sp_vhm_destroy(sp_voxel_hash_map* m) {
+    if (m) (void)hipFree(m->reg_rows);
+    sp::destroy_map(m);
+}
 
 extern "C" int sp_vhm_clear(sp_voxel_hash_map* m, void* stream) {  // :83-113
     if (!m) return SP_ERR_INVALID_ARGUMENT;
+    m->touch();
     const int rc = m->reset_to_first_capacity(sp::as_stream(stream));
     if (rc == SP_OK) m->staleness_counter = 0;
     return rc;
@@ -182,11 +183,12 @@ extern "C" int sp_vhm_set(sp_voxel_hash_map* m, int param, float value) {
             if (!(value > 0.0f)) { sp_set_error("voxel_size must be positive."); return SP_ERR_INVALID_ARGUMENT; }
             m->voxel_size = value;
             m->voxel_size_inv = 1.0f / value;
+            m->touch();
             return SP_OK;
         case SP_VHM_MAX_STALENESS: m->max_staleness = (uint32_t)value; return SP_OK;
         case SP_VHM_REMOVE_OLD_DATA_CYCLE: m->remove_old_data_cycle = (uint32_t)value; return SP_OK;
         case SP_VHM_REHASH_THRESHOLD: m->rehash_threshold = value; return SP_OK;
-        case SP_VHM_MIN_NUM_POINT: m->min_num_point = (uint32_t)value; return SP_OK;
+        case SP_VHM_MIN_NUM_POINT: m->min_num_point = (uint32_t)value; m->touch(); return SP_OK;
     }
     return SP_ERR_INVALID_ARGUMENT;
 }
@@ -227,6 +229,7 @@ extern "C" int sp_vhm_add_point_cloud(sp_voxel_hash_map* m, const float* points,
     if (n >= (1ull << 32)) { sp_set_error("[VoxelHashMap] more than 2^32 points"); return SP_ERR_INVALID_ARGUMENT; }
     hipStream_t st = as_stream(stream);
     const unsigned long long cap = m->t.capacity;
+    m->touch();  // (before anything is enqueued: a call that fails half way leaves rows nobody may trust either)
     int rc = m->ensure_rehash(st, rehash_launch(m, st));
     if (rc != SP_OK) return rc;
     if (m->t.capacity != cap) drop_flags_when_empty(m);
