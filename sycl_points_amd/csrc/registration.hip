@@ -762,11 +762,11 @@ template <bool SHARDED, typename Hook>
 __device__ __forceinline__ bool align_totals(const AlignArgs& A, const float* __restrict__ rows, unsigned nrows,
                                              float (*red)[kPartial], Hook after_loads, const unsigned* converged = nullptr) {
     if constexpr (!SHARDED) {
-        reduce_rows_1024(rows, nrows, kAcc - 1, red, false, after_loads);
+        reduce_rows_1024<false, true>(rows, nrows, kAcc - 1, red, false, after_loads);
         return true;
     } else {
         if (A.mode == ALIGN_ROWS || A.mode == ALIGN_PROLOGUE) {
-            reduce_rows_1024(rows, nrows, kAcc - 1, red, A.mode == ALIGN_ROWS, after_loads);
+            reduce_rows_1024<false, true>(rows, nrows, kAcc - 1, red, A.mode == ALIGN_ROWS, after_loads);
             return true;
         }
         if (A.mode == ALIGN_DIRECT) {
@@ -826,8 +826,10 @@ __device__ __forceinline__ void align_store_late_state(const AlignArgs& A) {
     }
 }
 
-template <bool SHARDED>
-__device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, unsigned* sflag) {
+// `prefetch` (not run by launch 0, which finishes nothing) is called by every lane once the state words and the rows are
+// requested and before anything waits for them: what it loads is in flight while the rows are summed and wave 0 solves.
+template <bool SHARDED, typename Prefetch>
+__device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, unsigned* sflag, Prefetch prefetch) {
     __shared__ float red[kFinalThreads / 32][kPartial];
     __shared__ float sdelta[8];
     if (A.first) {
@@ -843,7 +845,7 @@ __device__ __forceinline__ bool align_prologue(const AlignArgs& A, float* sT, un
     // memory round trip for both
     const unsigned sv = state_load(A.has_prev, A.state_in, A.T_init);
     const unsigned nrows = (SHARDED && A.mode == ALIGN_ROWS) ? (unsigned)kAlignMaxBlocks : gridDim.x;
-    const bool arrived = align_totals<SHARDED>(A, A.prev_rows, nrows, red, [=] { state_store(sv, sT, sflag); }, sflag);
+    const bool arrived = align_totals<SHARDED>(A, A.prev_rows, nrows, red, [&] { prefetch(); state_store(sv, sT, sflag); }, sflag);
     if (!arrived) {  // (uniform per workgroup; every workgroup of every rank runs into the same bound)
         if (blockIdx.x == 0) align_store_late_state(A);
         return false;
@@ -878,16 +880,33 @@ __global__ __launch_bounds__(kAlignBlock) void gicp_align_kernel(FusedParams P, 
     __shared__ float sT[16];
     __shared__ unsigned sflag[2];
     // (converged: every rank holds the same state and stops at the same launch — nobody waits for a row)
-    if (!align_prologue<SHARDED>(A, sT, sflag)) return;
+    // The first trip's loads that do not depend on the pose (PointHead: the coordinates and the correspondence row, written by an
+    // earlier launch, addresses from i alone) are requested inside the prologue, behind its row loads: they travel while the
+    // rows are summed and wave 0 solves, a time in which the workgroup otherwise asks memory for nothing. Every wave does this,
+    // wave 0 too (its solve reads LDS). A launch that ends in its prologue (converged, a late peer row) leaves them outstanding:
+    // valid addresses of this launch's own buffers. Launch 0 has no prologue to hide them behind and loads in the loop.
+    // Issued from the hook and not after align_totals: the compiler waits for the rows with a counted vmcnt there
+    // (profiles/prologue_prefetch_resources.txt) — as long as no branch stands around the loads, see point_head_load. This is
+    // the form that was measured (0.45-0.72 us per steady launch, profiles/prologue_prefetch_same_box.txt); with the counted
+    // wait in the listing the later issue point, which overlaps the solve alone, was not built.
+    const unsigned tile = xcd_tile();
+    const unsigned i0 = tile * kAlignBlock + threadIdx.x;
+    PointHead head;
+    if (!align_prologue<SHARDED>(A, sT, sflag, [&] { point_head_load(P, i0, head); })) return;
     const Rigid T = uniform_pose(sT);
     float acc[kAcc - 1];
     unsigned cnt = 0, searched = 0;
     const unsigned stride = gridDim.x * kAlignBlock;
 #pragma unroll
     for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
-    const unsigned tile = xcd_tile();
-    for (unsigned i = tile * kAlignBlock + threadIdx.x; i < P.n; i += stride)
-        fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert>(P, T, i, acc, cnt, searched);
+    bool use_head = !A.first;  // (uniform: the first trip of a launch that had a prologue)
+    for (unsigned i = i0; i < P.n; i += stride) {
+        fused_point<LOSS, FAST_NN, P2D, kSeedSearches, kNegCert, true>(P, T, i, acc, cnt, searched, &head, use_head);
+        // (the 15 words are dead from here on: said so, or they would hold registers across every later trip's search)
+        use_head = false;
+        head.x = head.y = head.z = 0.0f;
+        head.r0 = head.r1 = head.r2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
     if constexpr (!SHARDED) {
         block_reduce_store<kAcc - 1, kAlignBlock>(acc, cnt, partials + (size_t)blockIdx.x * kPartial, false, searched);
     } else if (A.mode == ALIGN_ROWS) {

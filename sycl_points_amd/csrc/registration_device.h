@@ -107,7 +107,9 @@ __host__ __device__ inline void gn_update_impl(sp_linearized* lin, float* T, flo
 // On return (after a barrier) red[0][e] holds the totals; slot nv is the uint32 count.
 // `after_loads` runs once the row loads have been issued (and before the first barrier): the per-iteration kernel stores
 // the previous state there, which it loaded BEFORE the rows, so that both arrive in the same memory round trip.
-template <bool SC1 = false, typename Hook>
+// AT_MOST_256: the caller's rows never exceed 256 (the per-iteration kernel's grid), so only the first form is compiled — with
+// both, loads that `after_loads` issues in one form count as pending in the other and the compiler drains them there.
+template <bool SC1 = false, bool AT_MOST_256 = false, typename Hook>
 __device__ __forceinline__ void reduce_rows_1024(const float* __restrict__ partials, unsigned rows, int nv,
                                                  float (*red)[kPartial], bool count_is_float, Hook after_loads) {
     constexpr unsigned kParts = kFinalThreads / 32;
@@ -117,7 +119,7 @@ __device__ __forceinline__ void reduce_rows_1024(const float* __restrict__ parti
     float s = 0.0f;
     unsigned c = 0;
     const bool is_count = ((int)e == nv);
-    if (per <= 8) {  // at most 256 rows (the per-iteration kernel): all loads of a lane in flight at once
+    if (AT_MOST_256 || per <= 8) {  // at most 256 rows (the per-iteration kernel): all loads of a lane in flight at once
         float v[8];
 #pragma unroll
         for (unsigned j = 0; j < 8; ++j)
@@ -369,6 +371,26 @@ __device__ __forceinline__ float search_bound2_margin(const FusedParams& P, floa
     return wide;
 }
 
+// What a lane loads first of point i, whatever the pose: its three coordinate words and, when the cache is valid, its
+// correspondence row — 15 words whose addresses depend on i alone. gicp_align_kernel requests them for the workgroup's first
+// trip while the previous iteration is still being finished (align_prologue) and hands them to fused_point.
+struct PointHead {
+    float x, y, z;
+    float4 r0, r1, r2;
+};
+// The six loads stand on EVERY path, with no branch around them: a load that is issued on one path only counts as pending on
+// all of them, and the compiler then drains every load (s_waitcnt vmcnt(0)) where it could have counted the older ones in.
+// So a lane without a point (i >= n) asks for point n - 1 again, and while the cache holds nothing every lane asks for row 0:
+// addresses inside the n points and the n rows of this source (a source of no points still owns one tile and one row,
+// sp_gicp_source_create), values nobody reads.
+__device__ __forceinline__ void point_head_load(const FusedParams& P, unsigned i, PointHead& h) {
+    const unsigned ic = min(i, max(P.n, 1u) - 1u);
+    const float* const sw = src_words(P, ic);
+    h.x = sw[0]; h.y = sw[kWave]; h.z = sw[2 * kWave];
+    const float4* const row = P.ccache + 3 * (size_t)(P.cache_valid ? ic : 0u);
+    h.r0 = row[0]; h.r1 = row[1]; h.r2 = row[2];
+}
+
 // One source point of the fused iteration: q = T p -> correspondence (cache row by certificate, else exact NN on the target
 // grid) -> linearise -> accumulate.
 // P.cache_valid: 0 the cache holds nothing (every point is searched), 1 a row is used when its certificate holds: while
@@ -376,12 +398,28 @@ __device__ __forceinline__ float search_bound2_margin(const FusedParams& P, floa
 // cache row) with no search and no gather, and a wave whose lanes all pass never enters the search code.
 // SEED: a point whose certificate fails starts its search from the previous winner (grid_nn1_fast's `seed`).
 // NEG: a search that finds nothing is made with the widened bound and recorded as a negative certificate (store_correspondence).
-template <int LOSS, bool FAST_NN, bool P2D = false, bool SEED = true, bool NEG = true>
+// PRE (gicp_align_kernel): `head` holds the point's first loads already (point_head_load, issued behind the prologue's row
+// loads) and `use_head`, uniform over the workgroup, says whether this trip takes them — the workgroup's first trip — or
+// loads as every other caller does. From the certificate on, one text for both.
+template <int LOSS, bool FAST_NN, bool P2D = false, bool SEED = true, bool NEG = true, bool PRE = false>
 __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T, unsigned i, float (&acc)[kAcc - 1],
-                                            unsigned& cnt, unsigned& searched) {
+                                            unsigned& cnt, unsigned& searched, const PointHead* head = nullptr,
+                                            bool use_head = false) {
     const float* const sw = src_words(P, i);
-    const float4 s = src_point(sw);
     float4* const row = P.ccache + 3 * (size_t)i;  // (a prepared source always has its cache rows)
+    float4 s;
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;  // (read only where P.cache_valid has filled them)
+    if constexpr (PRE) {
+        if (use_head) {  // (a scalar branch)
+            s = make_float4(head->x, head->y, head->z, 1.0f);
+            r0 = head->r0; r1 = head->r1; r2 = head->r2;
+        } else {
+            s = src_point(sw);
+            if (P.cache_valid) { r0 = row[0]; r1 = row[1]; r2 = row[2]; }
+        }
+    } else {
+        s = src_point(sw);
+    }
     float qx, qy, qz;
     transform_point(T, s.x, s.y, s.z, qx, qy, qz);
     Nearest nn;
@@ -391,7 +429,7 @@ __device__ __forceinline__ void fused_point(const FusedParams& P, const Rigid& T
     Nearest seed;
     seed.d2 = FLT_MAX; seed.idx = -1; seed.pos = 0; seed.x = seed.y = seed.z = 0.0f;
     if (P.cache_valid) {
-        const float4 r0 = row[0], r1 = row[1], r2 = row[2];
+        if constexpr (!PRE) { r0 = row[0]; r1 = row[1]; r2 = row[2]; }
         const float d = dist2(qx, qy, qz, r0.x, r0.y, r0.z);
         const unsigned pos = __float_as_uint(r2.w);
         if (certified(P, d, r0.w, qx, qy, qz, pos)) {
