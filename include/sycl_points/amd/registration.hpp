@@ -509,6 +509,85 @@ public:
     /// every further guess adds about 0.02 ms to the batch: from 5 guesses on the batch is ahead (at 4: 0.95 of the sequential
     /// time); on a cloud of even density already from 2.
     static constexpr size_t kAlignBatchMinGuesses = 5;
+
+    /// MI355X extension: align(source, map) from every pose of `initial_guesses` — relocalisation against the one target that
+    /// persists across frames. With at least kVoxelAlignBatchMinGuesses guesses (and at most SP_ALIGN_BATCH_MAX), a source of up
+    /// to SP_VHM_ALIGN_BATCH_MAX_POINTS points, not verbose, max_iterations in 1..65535, no degenerate regularisation, no active MAP
+    /// prior: ONE optimiser launch with a workgroup per guess (sp_vhm_align_batch), the poses up in one copy, the result
+    /// blocks back in one read-back. Otherwise align(source, map, guess) once per guess, so the call is always usable.
+    /// Validation and messages are align(source, map)'s; voxel_neighbors() cells are probed; the map's registration rows are
+    /// refreshed when they are stale. result[i] belongs to initial_guesses[i]; best_of picks among them. After a batch on the
+    /// device nothing is frozen for compute_error_frozen, as after the other overload.
+    std::vector<RegistrationResult> align_batch(const PointCloudShared& source, mapping::VoxelHashMap& target_map,
+                                                const std::vector<TransformMatrix>& initial_guesses,
+                                                const ExecutionOptions& options = ExecutionOptions()) {
+        std::vector<RegistrationResult> out;
+        out.reserve(initial_guesses.size());
+        const size_t B = initial_guesses.size(), N = source.size();
+        const bool pose_terms = params_.degenerate_reg.type != DegenerateRegularizationType::none || prior_active();
+        if (!(B >= kVoxelAlignBatchMinGuesses && B <= size_t(SP_ALIGN_BATCH_MAX) && N > 0 && N <= size_t(SP_VHM_ALIGN_BATCH_MAX_POINTS) &&
+              !params_.verbose && params_.max_iterations > 0 && params_.max_iterations <= 65535 && !pose_terms && comm_ == nullptr &&
+              xchg_ == nullptr)) {  // (the launch logs the iteration in 16 bits: more iterations go guess by guess)
+            for (const TransformMatrix& T0 : initial_guesses) out.push_back(align(source, target_map, T0, options));
+            return out;
+        }
+        if ((params_.reg_type != RegType::GICP && params_.reg_type != RegType::POINT_TO_DISTRIBUTION) || params_.rotation_constraint.enable)
+            throw std::invalid_argument("[Registration::align] a VoxelHashMap target: GICP or POINT_TO_DISTRIBUTION without the "
+                                        "rotation constraint");
+        if (params_.reg_type == RegType::GICP && !source.has_cov())
+            throw std::runtime_error("[Registration::validate_params] Covariance matrices of source and target must be "
+                                     "pre-computed before performing GICP matching.");
+        if (params_.robust.type != robust::RobustLossType::NONE && params_.robust.default_scale <= 0.0f) {
+            std::cout << "[Caution] `robust.default_scale` must be greater than zero. Disable robust loss." << std::endl;
+            params_.robust.type = robust::RobustLossType::NONE;
+        }
+        const float robust_scale = options.robust_scale > 0.0f ? options.robust_scale : params_.robust.default_scale;
+        const int reg = int(params_.reg_type);
+        if (!target_map.registration_ready(reg)) target_map.prepare_registration(reg);
+        // device: poses | result blocks | source rows and the hypotheses' slots; pinned host: poses | result blocks
+        const size_t poses_bytes = (B * 16 * sizeof(float) + 255) / 256 * 256, res_bytes = (B * sizeof(sp_align_result) + 255) / 256 * 256;
+        const size_t ws_bytes = sp_vhm_align_batch_workspace_bytes(N, B);
+        if (batch_dev_bytes_ < poses_bytes + res_bytes + ws_bytes) {
+            if (batch_dev_) hip_check(hipFree(batch_dev_), "hipFree");
+            batch_dev_ = nullptr; batch_dev_bytes_ = 0;
+            hip_check(hipMalloc(&batch_dev_, poses_bytes + res_bytes + ws_bytes), "hipMalloc");
+            batch_dev_bytes_ = poses_bytes + res_bytes + ws_bytes;
+        }
+        if (batch_pin_bytes_ < poses_bytes + res_bytes) {
+            if (batch_pin_) hip_check(hipHostFree(batch_pin_), "hipHostFree");
+            batch_pin_ = nullptr; batch_pin_bytes_ = 0;
+            hip_check(hipHostMalloc(&batch_pin_, poses_bytes + res_bytes), "hipHostMalloc");
+            batch_pin_bytes_ = poses_bytes + res_bytes;
+        }
+        float* const T_dev = reinterpret_cast<float*>(batch_dev_);
+        sp_align_result* const res_dev = reinterpret_cast<sp_align_result*>(batch_dev_ + poses_bytes);
+        float* const T_host = reinterpret_cast<float*>(batch_pin_);
+        const sp_align_result* const res_host = reinterpret_cast<const sp_align_result*>(batch_pin_ + poses_bytes);
+        for (size_t b = 0; b < B; ++b) std::memcpy(T_host + 16 * b, initial_guesses[b].data(), 16 * sizeof(float));
+        hip_check(hipMemcpyAsync(T_dev, T_host, B * 16 * sizeof(float), hipMemcpyHostToDevice, queue_.stream()), "H2D");
+        const sp_factor_params fp = factor_params(robust_scale);
+        const sp_opt_params op = opt_params();
+        throw_on_error(sp_vhm_align_batch(target_map.handle(), source.points_device(), source.has_cov() ? source.covs_device() : nullptr, N,
+                                          T_dev, T_dev, B, &fp, &op, &robust_scale, 1, voxel_neighbors_, res_dev, nullptr,
+                                          batch_dev_ + poses_bytes + res_bytes, ws_bytes, queue_.stream()));
+        hip_check(hipMemcpyAsync(batch_pin_ + poses_bytes, res_dev, B * sizeof(sp_align_result), hipMemcpyDeviceToHost, queue_.stream()), "D2H");
+        hip_check(hipStreamSynchronize(queue_.stream()), "sync");
+        for (size_t b = 0; b < B; ++b) out.push_back(to_registration_result(res_host[b]));
+        last_opt_linearizations_ = res_host[B - 1].linearizations;
+        last_opt_trials_ = res_host[B - 1].trials;
+        // nothing is frozen for compute_error_frozen: neither the source's cache nor neighbors_ describes this batch
+        last_lin_fused_ = false;
+        fused_loop_active_ = false;
+        if (neighbors_.indices != nullptr) neighbors_.resize(0, 1);  // (never allocated when only maps have been aligned against)
+        return out;
+    }
+    /// Where the voxel-map batch starts to win over align(source, map) per guess. Measured: already a single
+    /// guess is ahead, 125 us against 341 us on 1000 points of the three planes and 319 us against 506 us on the bundled pair
+    /// (one launch and one read-back against two launches and a read-back per step); at 256 guesses 31 and 43 times. Measured
+    /// against the Python mirror's per-guess loop (its ctypes calls included) on sources of up to 6 124 points. A guess is one
+    /// workgroup of 512 lanes: near SP_VHM_ALIGN_BATCH_MAX_POINTS a step is 32 passes on one compute unit, and one or two
+    /// guesses of such a source have not been measured against the loop, which spreads a step over the device.
+    static constexpr size_t kVoxelAlignBatchMinGuesses = 1;
     /// The best of align_batch's results by the rule of sp_align_best_host: the most inliers among results with a finite pose, a
     /// finite error and at least one inlier; ties to the smaller error, then to the lower index; results.size() when none qualifies.
     static size_t best_of(const std::vector<RegistrationResult>& results) {

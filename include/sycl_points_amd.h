@@ -1394,6 +1394,37 @@ int sp_vhm_linearize(const sp_voxel_hash_map* map, const float* src_points, size
 int sp_vhm_error(const sp_voxel_hash_map* map, const float* src_points, size_t n, const float* transT_trial,
                  int trial_on_device, const sp_factor_params* params, sp_linearized* out, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* The same alignment from `batch` initial guesses in ONE launch (relocalisation against the map: start-up without a pose, a yaw
+ * sweep, a loop-closure check): sp_gicp_align_batch's launch shape around sp_vhm_linearize's and sp_vhm_error's per-point work.
+ * Workgroup b of a plain grid of `batch` workgroups runs the whole alignment of hypothesis b (every OptimizationMethod, n_levels
+ * robust scales): a step is a pass of its lanes over the source, the totals are summed in LDS, one lane runs the optimiser's
+ * state machine. 256 lanes up to 256 source points, 512 beyond (no form of the kernel uses scratch memory). The workgroups
+ * share nothing they write and none waits for another: no residency requirement, any batch on any stream (a capturing one too,
+ * and beside another stream's persistent launch). The map is only read: its generation, its rows and what sp_vhm_linearize noted
+ * for sp_vhm_error stay as they are — an sp_vhm_error after a batch behaves as if the batch had not run.
+ *   src_covs        n x 16 floats; may be null for SP_REG_POINT_TO_DISTRIBUTION. SP_REG_GICP: the packed source rows are filled
+ *                   on the same stream ahead of the optimiser (two launches; point-to-distribution one)
+ *   T_init_device   batch x 16 floats, column-major poses            T_out_device  the final poses (may alias T_init_device)
+ *   results_device  batch blocks, each as sp_gicp_align_batch writes its one (status 0, pad[0] = SP_ALIGN_RESULT_DONE last).
+ *                   searched = n x linearizations: every linearisation looks every point up. T_lin: the pose of the last
+ *                   linearisation, whose system H, b, error_raw are
+ *   corr_keys_out_opt  device, batch x n, may be null: each point's voxel key of that last linearisation, or ~0
+ *   workspace       sp_vhm_align_batch_workspace_bytes(n, batch) bytes: two float4 per source point | batch arrays of n uint32
+ *                   slots, each 16-byte aligned; at least 32 n + 4 n batch. That function returns 0 for n == 0,
+ *                   n > SP_VHM_ALIGN_BATCH_MAX_POINTS, batch == 0 or batch > SP_ALIGN_BATCH_MAX
+ * Only enqueues. SP_ERR_INVALID_ARGUMENT with a message for a null argument, n_levels outside 1..SP_OPT_MAX_LEVELS, an unknown
+ * method, max_iterations outside 1..65535, a reg_type other than the two above, an enabled rotation constraint, a map without
+ * covariances, rows that are not sp_vhm_registration_ready for params->reg_type, neighbor_voxels not 1 / 7 / 27, n or batch
+ * outside the ranges above and a workspace that is too small; SP_ERR_RUNTIME with the reference's message for SP_REG_GICP
+ * without src_covs. On any failure nothing is enqueued and nothing is written. */
+enum { SP_VHM_ALIGN_BATCH_MAX_POINTS = 16384 };   /* batch limit: SP_ALIGN_BATCH_MAX */
+size_t sp_vhm_align_batch_workspace_bytes(size_t n, size_t batch);
+int sp_vhm_align_batch(const sp_voxel_hash_map* map, const float* src_points, const float* src_covs, size_t n,
+                       const float* T_init_device, float* T_out_device, size_t batch,
+                       const sp_factor_params* params, const sp_opt_params* opt,
+                       const float* robust_scales, int n_levels, int neighbor_voxels,
+                       sp_align_result* results_device, uint64_t* corr_keys_out_opt,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- OccupancyGridMap (mapping/occupancy_grid_map.hpp:27-472)
  * The other submap of Submap::build_submap: the VoxelHashMap table (same key, same double hashing, same capacity ladder; 128

@@ -391,6 +391,9 @@ SIGNATURES = {
     "sp_vhm_neighbor_offsets_host": (_i, [_i, _vp]),
     "sp_vhm_linearize": (_i, [_vp, _vp, _sz, _vp, _i, C.POINTER(FactorParams), _i, _vp, _vp, _vp, _sz, _vp]),
     "sp_vhm_error": (_i, [_vp, _vp, _sz, _vp, _i, C.POINTER(FactorParams), _vp, _vp, _sz, _vp]),
+    "sp_vhm_align_batch_workspace_bytes": (_sz, [_sz, _sz]),
+    "sp_vhm_align_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(FactorParams), C.POINTER(OptParams), C.POINTER(C.c_float),
+                                _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sp_ogm_create": (_i, [_f, _vp, C.POINTER(_vp)]),
     "sp_ogm_destroy": (None, [_vp]),
     "sp_ogm_set": (_i, [_vp, _i, _f]),

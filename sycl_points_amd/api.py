@@ -2187,6 +2187,64 @@ class Registration:
 
         return self._host_loop(T, linearize_at, error_at, scale)
 
+    def align_voxel_map_batch(self, source, voxel_map, initial_guesses, robust_scales=None, neighbor_voxels=1, want_keys=False):
+        """MI355X extension: align_voxel_map from every pose of `initial_guesses` (a sequence of 4x4 matrices) in ONE launch, one
+        workgroup per guess, and ONE read-back (sp_vhm_align_batch) — relocalisation against the map. The explicit call: no
+        threshold, no host-side pose terms (degenerate regularisation, the MAP prior). The map's registration rows are refreshed
+        here when they are not those of the map as it is now; the map itself is only read. Returns one result per guess as
+        align_batch does (`log`, `linearizations`, `trials`, `searched`, `T_lin`, `block`); with want_keys each also has `keys`,
+        every source point's voxel key at the last linearisation (int64 tensor, -1 for none)."""
+        return self._align_voxel_map_batch(source, voxel_map, initial_guesses, robust_scales, neighbor_voxels, want_keys)
+
+    def _align_voxel_map_batch(self, source, voxel_map, initial_guesses, robust_scales=None, neighbor_voxels=1, want_keys=False,
+                               prepare=True, T_out=None, results=None, workspace_bytes=None):
+        """align_voxel_map_batch with what the tests of the library's contract hand in: prepare=False takes the map's rows as they
+        are; T_out / results: the output buffers; workspace_bytes: the workspace size told to the library."""
+        L = _lib.lib()
+        p = self.params
+        guesses = [np.asarray(T, np.float32) for T in initial_guesses]
+        B, n = len(guesses), source.size()
+        dev = source.points.device
+        rsz = C.sizeof(_lib.AlignResult)
+        if p.robust_type != "NONE" and p.robust_default_scale <= 0.0:
+            p.robust_type = "NONE"
+        if prepare and p.reg_type in ("GICP", "POINT_TO_DISTRIBUTION") and not voxel_map.registration_ready(p.reg_type):
+            voxel_map.prepare_registration(p.reg_type)
+        need = L.sp_vhm_align_batch_workspace_bytes(n, B)
+        bufs = getattr(self, "_vbatch_bufs", None)
+        if bufs is None or bufs[0].device != dev or bufs[0].numel() < 16 * max(B, 1) or bufs[3].numel() < need:
+            # (sized for this call, kept for the next one that fits)
+            bufs = (torch.zeros(16 * max(B, 1), dtype=torch.float32, device=dev),
+                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8, device=dev),
+                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8).pin_memory(),
+                    torch.empty(max(need, 16), dtype=torch.uint8, device=dev))
+            self._vbatch_bufs = bufs
+        T_dev, res_dev, res_host, ws = bufs
+        res_dev = res_dev if results is None else results
+        if B:
+            poses = np.stack([_T16(T).reshape(-1) for T in guesses])  # one copy up
+            T_dev[:16 * B].copy_(torch.from_numpy(poses.reshape(-1).copy()), non_blocking=True)
+        keys = torch.empty(max(B * n, 1), dtype=torch.int64, device=dev) if want_keys else None
+        scales = list(robust_scales) if robust_scales else [p.robust_default_scale]
+        fp = self._factor_params(scales[0])
+        op = self.opt_params()
+        sc = (C.c_float * len(scales))(*scales)
+        check(L.sp_vhm_align_batch(voxel_map._h, _ptr(source.points) if n else None, _ptr(source.covs if source.has_cov() else None), n,
+                                   _ptr(T_dev), _ptr(T_dev if T_out is None else T_out), B, C.byref(fp), C.byref(op), sc, len(scales),
+                                   int(neighbor_voxels), _ptr(res_dev), _ptr(keys), _ptr(ws),
+                                   ws.numel() if workspace_bytes is None else workspace_bytes, _stream()))
+        res_host[:rsz * B].copy_(res_dev[:rsz * B], non_blocking=True)  # one copy down
+        torch.cuda.current_stream().synchronize()
+        raw = res_host[:rsz * B].numpy().tobytes()
+        out = []
+        for b in range(B):
+            res = self._result_from_align_result(_lib.AlignResult.from_buffer_copy(raw, rsz * b))
+            res.block = raw[rsz * b:rsz * (b + 1)]  # the sp_align_result as the launch wrote it
+            if want_keys:
+                res.keys = keys[b * n:(b + 1) * n]
+            out.append(res)
+        return out
+
     def _host_loop(self, T, linearize_at, error_at, scale):
         """The optimiser loop of Registration::align shared by the generic and the prepared path, from pose T (column-major 16
         floats): the library's stepper (sp_opt_stepper_*: the state machine of the device-resident launch) says what it wants

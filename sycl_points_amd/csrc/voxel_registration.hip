@@ -15,51 +15,10 @@
 //   * the trial error over the slots the linearisation froze (the contract of sp_gicp_error_prepared).
 // The per-point algebra is sp_linearize.h's (this unit is compiled with -fno-slp-vectorize like its other users), the sums are
 // block_reduce_store and reduce_rows_1024 (registration_device.h): a fixed tree, no float atomics, the same bits run after run.
-#include "voxel_hash_map.h"
-#include "registration_device.h"
-#include "sp_cov_normal.h"
+#include "sp_voxel_registration.h"
 
 namespace sp {
 namespace {
-
-constexpr unsigned kNoFrozenSlot = 0xFFFFFFFFu;
-
-// The probing order: the point's own cell, the six face neighbours, the twelve edge neighbours, the eight corner neighbours.
-// The first 1 / 7 / 27 entries are the three modes.
-struct CellOffsets {
-    int8_t d[27][3];
-};
-constexpr CellOffsets make_cell_offsets() {
-    CellOffsets o{};
-    int k = 0;
-    for (int nz = 0; nz <= 3; ++nz)
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dx = -1; dx <= 1; ++dx)
-                    if ((dx != 0) + (dy != 0) + (dz != 0) == nz) {
-                        o.d[k][0] = (int8_t)dx; o.d[k][1] = (int8_t)dy; o.d[k][2] = (int8_t)dz;
-                        ++k;
-                    }
-    return o;
-}
-constexpr CellOffsets kCellOffsets = make_cell_offsets();
-
-constexpr int64_t kCellMask = (1 << 21) - 1;
-constexpr int64_t kCellOffset = 1 << 20;
-
-// voxel_key3 in two steps: the offset cell coordinates of a finite point (the same arithmetic), then the key of a cell
-// next to it, kInvalidKey when that cell lies outside the 21 bits of an axis.
-__device__ __forceinline__ uint64_t cell_key(int64_t c0, int64_t c1, int64_t c2) {
-    if (c0 < 0 || kCellMask < c0 || c1 < 0 || kCellMask < c1 || c2 < 0 || kCellMask < c2) return kInvalidKey;
-    return ((uint64_t)(c0 & kCellMask)) | ((uint64_t)(c1 & kCellMask) << 21) | ((uint64_t)(c2 & kCellMask) << 42);
-}
-
-__device__ __forceinline__ float4 pack_sym_lo(const Mat3& P) {
-    return make_float4(P.m[0][0], (P.m[0][1] + P.m[1][0]) * 0.5f, (P.m[0][2] + P.m[2][0]) * 0.5f, P.m[1][1]);
-}
-__device__ __forceinline__ float4 pack_sym_hi(const Mat3& P) {
-    return make_float4((P.m[1][2] + P.m[2][1]) * 0.5f, P.m[2][2], 0.0f, 0.0f);
-}
 
 // The rows of every used slot. The mean is write_mean_row's, the covariance decode_cov's: what downsampling() exports.
 template <bool P2D>
@@ -84,27 +43,7 @@ __global__ __launch_bounds__(kBlock) void vhm_registration_rows_kernel(VhmTable 
     row[2] = pack_sym_hi(P);
 }
 
-__global__ __launch_bounds__(kBlock) void vhm_source_rows_kernel(const float4* __restrict__ covs, unsigned n, float4* __restrict__ rows) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const Mat3 P = plane_regularize(load_cov(covs + 4 * (size_t)i));
-    rows[2 * (size_t)i] = pack_sym_lo(P);
-    rows[2 * (size_t)i + 1] = pack_sym_hi(P);
-}
-
-struct VhmRegArgs {
-    const uint64_t* keys;
-    const float4* rows;     // three per slot
-    unsigned long long capacity;
-    const float4* src;      // source points, rows of four floats
-    const float4* src_rows; // two per source point (GICP), in the workspace
-    unsigned* slots;        // the frozen correspondence of every source point
-    uint64_t* corr_keys;    // optional
-    unsigned n;
-    float inv, max_d2, scale;
-    QueryPose pose;
-};
-
+// (the point's statements in place, not through vhm_linearize_point: sp_voxel_linearize_body.h says why)
 template <int LOSS, bool P2D, int NV>
 __global__ __launch_bounds__(kBlock) void vhm_linearize_kernel(VhmRegArgs A, float* __restrict__ partials) {
     const Rigid T = load_pose(A.pose);
@@ -113,62 +52,9 @@ __global__ __launch_bounds__(kBlock) void vhm_linearize_kernel(VhmRegArgs A, flo
     for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
     unsigned cnt = 0;
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < A.n; i += gridDim.x * kBlock) {
-        const float4 p = A.src[i];
-        float qx, qy, qz;
-        transform_point(T, p.x, p.y, p.z, qx, qy, qz);
-        unsigned best = kNoFrozenSlot;
-        uint64_t best_key = kInvalidKey;
-        float best_d2 = INFINITY, tx = 0.0f, ty = 0.0f, tz = 0.0f;
-        if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-            const int64_t c0 = (int64_t)floorf(qx * A.inv) + kCellOffset;
-            const int64_t c1 = (int64_t)floorf(qy * A.inv) + kCellOffset;
-            const int64_t c2 = (int64_t)floorf(qz * A.inv) + kCellOffset;
-            // every cell's first probe: the loads leave together, nothing is compared before the last one has been issued
-            unsigned s0[NV];
-            uint64_t k0[NV];
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const uint64_t h = cell_key(c0 + kCellOffsets.d[j][0], c1 + kCellOffsets.d[j][1], c2 + kCellOffsets.d[j][2]);
-                s0[j] = h == kInvalidKey ? kNoFrozenSlot : (unsigned)slot_id(h, 0, A.capacity);
-                k0[j] = h == kInvalidKey ? kInvalidKey : A.keys[s0[j]];
-            }
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                if (s0[j] == kNoFrozenSlot) continue;  // a cell outside the key's range
-                const uint64_t h = cell_key(c0 + kCellOffsets.d[j][0], c1 + kCellOffsets.d[j][1], c2 + kCellOffsets.d[j][2]);
-                unsigned long long s = s0[j];
-                if (k0[j] != h) {  // find_slot<100> from its second probe on
-                    s = kNoSlot;
-                    if (k0[j] != kInvalidKey)
-                        for (unsigned pr = 1; pr < kVhmMaxProbe; ++pr) {
-                            const unsigned long long sp = slot_id(h, pr, A.capacity);
-                            const uint64_t k = A.keys[sp];
-                            if (k == h) { s = sp; break; }
-                            if (k == kInvalidKey) break;
-                        }
-                }
-                if (s == kNoSlot) continue;
-                const float4 m = A.rows[3 * (size_t)s];
-                if (m.w != 1.0f) continue;
-                const float d2 = dist2(qx, qy, qz, m.x, m.y, m.z);
-                if (d2 < best_d2) {  // strict: an exact tie stays with the earlier cell
-                    best_d2 = d2; best = (unsigned)s; best_key = h;
-                    tx = m.x; ty = m.y; tz = m.z;
-                }
-            }
-        }
-        if (best != kNoFrozenSlot && best_d2 > A.max_d2) { best = kNoFrozenSlot; best_key = kInvalidKey; }
-        A.slots[i] = best;
-        if (A.corr_keys) A.corr_keys[i] = best_key;
-        if (best == kNoFrozenSlot) continue;
-        const Sym3 Ct = load_sym(A.rows + 3 * (size_t)best + 1);
-        Sym3 Cs{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (!P2D) Cs = load_sym(A.src_rows + 2 * (size_t)i);
-        float t[kLinTerms];
-        linearize_terms<LOSS, P2D, false, kLinTerms>(T, p.x, p.y, p.z, qx, qy, qz, tx, ty, tz, Cs, Ct, A.scale, t);
-#pragma unroll
-        for (int e = 0; e < kLinTerms; ++e) acc[e] += t[e];
-        ++cnt;
+#define VHM_POINT_DONE continue
+#include "sp_voxel_linearize_body.h"
+#undef VHM_POINT_DONE
     }
     block_reduce_store<kAcc - 1>(acc, cnt, partials + (size_t)blockIdx.x * kPartial);
 }
@@ -179,21 +65,7 @@ __global__ __launch_bounds__(kBlock) void vhm_error_kernel(VhmRegArgs A, float* 
     const Rigid T = load_pose(A.pose);
     float acc[1] = {0.0f};
     unsigned cnt = 0;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < A.n; i += gridDim.x * kBlock) {
-        const unsigned s = A.slots[i];
-        if (s >= A.capacity) continue;  // kNoFrozenSlot, and nothing outside the table is ever read
-        const float4 p = A.src[i];
-        const float4 m = A.rows[3 * (size_t)s];
-        const Sym3 Ct = load_sym(A.rows + 3 * (size_t)s + 1);
-        Sym3 Cs{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (!P2D) Cs = load_sym(A.src_rows + 2 * (size_t)i);
-        float qx, qy, qz;
-        transform_point(T, p.x, p.y, p.z, qx, qy, qz);
-        float t[1];
-        linearize_terms<LOSS, P2D, true, 1>(T, p.x, p.y, p.z, qx, qy, qz, m.x, m.y, m.z, Cs, Ct, A.scale, t);
-        acc[0] += t[0];
-        ++cnt;
-    }
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < A.n; i += gridDim.x * kBlock) vhm_error_point<LOSS, P2D>(A, T, i, acc, cnt);
     block_reduce_store<1>(acc, cnt, partials + (size_t)blockIdx.x * kPartial);
 }
 
@@ -218,18 +90,6 @@ unsigned vhm_reduce_grid(size_t n) {
     return g ? g : 1;
 }
 
-int invalid(const char* msg) {
-    sp_set_error(msg);
-    return SP_ERR_INVALID_ARGUMENT;
-}
-int check_reg_type(int reg_type) {
-    if (reg_type == SP_REG_GICP || reg_type == SP_REG_POINT_TO_DISTRIBUTION) return SP_OK;
-    return invalid("[VoxelHashMap registration] reg_type must be GICP or POINT_TO_DISTRIBUTION");
-}
-bool rows_ready(const sp_voxel_hash_map* m, int reg_type) {
-    return m->reg_rows != nullptr && m->reg_rows_cap >= (size_t)m->t.capacity && m->reg_generation == m->generation &&
-           m->reg_type == reg_type;
-}
 // what sp_vhm_linearize and sp_vhm_error check alike, in this order
 int check_call(const char* not_ready, const sp_voxel_hash_map* m, const float* src, size_t n, const sp_factor_params* fp,
                const sp_linearized* out) {
