@@ -12,6 +12,7 @@
 //   algorithms/filter/outlier_removal_filter.hpp : filter::OutlierRemoval (statistical, radius)
 //   algorithms/common/filter_by_flags.hpp        : filter::FilterByFlags
 //   algorithms/common/transform.hpp              : transform::transform, transform_copy
+//   (no header of the reference)                 : feature::FPFHFeatures, feature::compute_fpfh(_async) — MI355X extension
 #pragma once
 #include <exception>
 #include <mutex>
@@ -415,6 +416,41 @@ inline void extract_normals(const PointCloudShared& points, const std::vector<sy
 }
 
 }  // namespace covariance
+
+// ================================================================================================ feature (MI355X extension)
+namespace feature {
+/// FPFH descriptors of a cloud: size() rows of SP_FPFH_STRIDE floats on the device, 33 bins and 3 zeros each.
+struct FPFHFeatures {
+    shared_vector_ptr<float> rows = nullptr;
+    size_t count = 0;
+    size_t size() const { return count; }
+    const float* device_data() const { return count ? rows->device_data() : nullptr; }
+};
+/// sp_fpfh_compute on the cloud's stream: `neighbors` is a kNN result of the cloud on itself (k <= SP_FPFH_MAX_K, the point
+/// itself may or may not be in its list). The cloud's normals must be of unit length and CONSISTENTLY ORIENTED — what
+/// covariance::estimate_normals_async gives a scan whose sensor sits at the origin; the features are signed, a flipped normal is
+/// another descriptor. Enqueue only.
+inline FPFHFeatures compute_fpfh_async(const knn::KNNResult& neighbors, const PointCloudShared& cloud) {
+    FPFHFeatures out;
+    out.rows = std::make_shared<shared_vector<float>>(cloud.queue);
+    out.count = cloud.size();
+    if (out.count == 0) return out;
+    if (!cloud.has_normal()) throw std::runtime_error("[feature::compute_fpfh_async] normals not computed");
+    if (neighbors.query_size != out.count) throw std::invalid_argument("[feature::compute_fpfh_async] the neighbour lists are not this cloud's");
+    hipStream_t st = cloud.queue.stream();
+    detail::DeviceScratch ws(sp_fpfh_workspace_bytes(out.count), st);
+    ws.stream_ordered = true;
+    throw_on_error(sp_fpfh_compute(cloud.points_device(), cloud.normals_device(), out.count, neighbors.indices->device_data(),
+                                   neighbors.distances->device_data(), neighbors.k,
+                                   out.rows->device_data_for_write(out.count * SP_FPFH_STRIDE), nullptr, nullptr, ws.p, ws.bytes, st));
+    return out;
+}
+inline FPFHFeatures compute_fpfh(const knn::KNNResult& neighbors, const PointCloudShared& cloud) {
+    FPFHFeatures out = compute_fpfh_async(neighbors, cloud);
+    hip_check(hipStreamSynchronize(cloud.queue.stream()), "sync");
+    return out;
+}
+}  // namespace feature
 
 // ================================================================================================ filters
 namespace filter {

@@ -7,6 +7,8 @@
 //                                                          compute_error_frozen, compute_icp_robust_weights)
 //   algorithms/deskew/relative_pose_deskew.hpp           : deskew::deskew_point_cloud_constant_velocity
 //   algorithms/registration/pipeline/{aligner,velocity_update,robust}.hpp, registration_pipeline(_params).hpp
+//   global_registration.hpp (no header of the reference) : match_features, GlobalRegistrationParams, global_guesses, behind
+//                                                          Registration::align_global — MI355X extension
 // Host control flow follows the reference; every per-point kernel is a C-ABI call. When the KNNBase handed to align()
 // is a GridKNN and the factor is GICP, the iteration uses the prepared / fused kernel (sp_gicp_iteration_fused).
 #pragma once
@@ -20,6 +22,7 @@
 #include <tuple>
 
 #include "features.hpp"
+#include "global_registration.hpp"
 #include "mapping.hpp"
 
 namespace sycl_points {
@@ -604,6 +607,31 @@ public:
         return best;
     }
 
+    /// MI355X extension: align() without an initial guess (relocalisation when more than a yaw angle is unknown). The mutual
+    /// nearest neighbours of the two clouds' FPFH rows (feature::compute_fpfh_async; consistently oriented normals) are the
+    /// matches, params.hypotheses poses of matched triplets are scored by the matches they explain, the params.guesses best become
+    /// the initial guesses of align_batch, and best_of picks the winner (global_registration.hpp: global_guesses). Fewer than three
+    /// matches, no hypothesis that passes its gates, or no alignment best_of accepts: converged == false and the identity;
+    /// nothing throws for want of matches. all_results / guesses_out receive every alignment and its initial guess.
+    RegistrationResult align_global(const PointCloudShared& source, const feature::FPFHFeatures& source_features,
+                                    const PointCloudShared& target, const feature::FPFHFeatures& target_features,
+                                    const knn::KNNBase& target_knn, const GlobalRegistrationParams& global_params = GlobalRegistrationParams(),
+                                    std::vector<RegistrationResult>* all_results = nullptr, std::vector<TransformMatrix>* guesses_out = nullptr,
+                                    const ExecutionOptions& options = ExecutionOptions()) {
+        return pick_global(global_guesses(source, source_features, target, target_features, global_params), all_results, guesses_out,
+                           [&](const std::vector<TransformMatrix>& g) { return align_batch(source, target, target_knn, g, options); });
+    }
+    /// The same against a VoxelHashMap: `target` and its descriptors are the cloud the matches are drawn from (the scan or submap
+    /// the map was built from), the alignment runs against the map (align_batch(source, map, guesses)).
+    RegistrationResult align_global(const PointCloudShared& source, const feature::FPFHFeatures& source_features,
+                                    const PointCloudShared& target, const feature::FPFHFeatures& target_features,
+                                    mapping::VoxelHashMap& target_map, const GlobalRegistrationParams& global_params = GlobalRegistrationParams(),
+                                    std::vector<RegistrationResult>* all_results = nullptr, std::vector<TransformMatrix>* guesses_out = nullptr,
+                                    const ExecutionOptions& options = ExecutionOptions()) {
+        return pick_global(global_guesses(source, source_features, target, target_features, global_params), all_results, guesses_out,
+                           [&](const std::vector<TransformMatrix>& g) { return align_batch(source, target_map, g, options); });
+    }
+
     /// MI355X extension: with a communicator set, `source` is THIS rank's shard of the source cloud (target, its
     /// covariances and its KNN structure are replicated on every rank) and align() runs the Gauss-Newton loop through
     /// sp_gicp_align_sharded: one launch and one 128-byte RCCL all-reduce per iteration, the identical pose on every rank.
@@ -1049,6 +1077,17 @@ private:
     const float* last_src_covs_ = nullptr;
     bool retried_without_persistent_ = false;
     uint32_t last_opt_linearizations_ = 0, last_opt_trials_ = 0;  // steps of the latest device-resident optimiser run
+    template <class BatchFn>
+    static RegistrationResult pick_global(std::vector<TransformMatrix> guesses, std::vector<RegistrationResult>* all_results,
+                                          std::vector<TransformMatrix>* guesses_out, BatchFn&& batch) {
+        std::vector<RegistrationResult> results;
+        if (!guesses.empty()) results = batch(guesses);
+        const size_t best = results.empty() ? 0 : best_of(results);
+        RegistrationResult out = best < results.size() ? results[best] : RegistrationResult();
+        if (all_results) *all_results = std::move(results);
+        if (guesses_out) *guesses_out = std::move(guesses);
+        return out;
+    }
     char* batch_dev_ = nullptr;  // align_batch: poses | result blocks | per-hypothesis cache rows, grown to the largest batch so far
     size_t batch_dev_bytes_ = 0;
     char* batch_pin_ = nullptr;  // ... and pinned host memory for the poses going up and the blocks coming back

@@ -1569,6 +1569,76 @@ int sp_enhanced_reflectivity(const float* points, float* intensities_inout, size
                              int32_t ring_offset, int ring_is_u8, int32_t ambient_offset, void* state_dev, float ema_alpha,
                              float clip_max, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- global registration (MI355X extension)
+ * Initial guesses for sp_gicp_align_batch / sp_vhm_align_batch from the data: FPFH descriptors, nearest neighbours in descriptor
+ * space, and poses of matched triplets scored by how many matches they explain. The reference has nothing of the kind; the
+ * definitions below are the specification. No float atomics anywhere: two calls on the same input give the same bits.
+ *
+ * sp_fpfh_compute: one descriptor row of SP_FPFH_STRIDE floats per point (33 bins, then 3 zeros: 144 bytes, 16-byte aligned).
+ *   points, normals  n x float4. The normals must be of unit length and CONSISTENTLY ORIENTED (what sp_normals_from_knn gives a
+ *                    scan whose sensor sits at the origin): the features are signed, a flipped normal is another descriptor.
+ *   knn_idx, knn_d2  a kNN result of the cloud on itself, n x k, padding -1 / FLT_MAX, k <= SP_FPFH_MAX_K; a list may or may
+ *                    not hold the point itself. Entries outside [0, n) are treated as padding.
+ *   SPFH of point i  its neighbours are the entries j >= 0, j != i in list order, m of them. A pair (i, j) with d = p_j - p_i,
+ *                    dist = |d| is skipped when dist == 0 or a value is not finite. The frame sits at the query point (no swap
+ *                    of the two points): f3 = n_i.d / dist; v = d x n_i, skipped when |v| == 0, v /= |v|; w = n_i x v;
+ *                    f2 = v.n_j; f1 = atan2(w.n_j, n_i.n_j). b1 = floor(11 (f1 + pi) / 2 pi), b2 = floor(11 (f2 + 1) / 2),
+ *                    b3 = floor(11 (f3 + 1) / 2), each clamped to 0..10; the pair adds 1 to count[b1], count[11 + b2],
+ *                    count[22 + b3]. SPFH_i[b] = float(count[b]) * (100.0f / float(m)); all zero for m == 0.
+ *   FPFH of point i  F[b] = sum over the same neighbours, in ascending list position as an fmaf chain from 0, of
+ *                    (1 / d2_ij) * SPFH_j[b] with the list's own d2 (entries with d2 == 0 skipped); then each of the three
+ *                    groups of 11 bins is scaled to sum 100 (a group that sums to 0 stays 0).
+ *   spfh_counts_out_opt / spfh_m_out_opt  n x 33 and n uint16, may be null: the counts and m, for tests and diagnosis.
+ *   workspace        sp_fpfh_workspace_bytes(n) bytes (the SPFH rows, 144 n), 16-byte aligned.
+ * Two launches (SPFH: a wave per point, a lane per neighbour, the histogram by ballots; FPFH: a wave per point, a lane per bin).
+ * n == 0: SP_OK. k == 0 or > SP_FPFH_MAX_K, a null pointer, n >= 2^31, a workspace that is too small -> SP_ERR_INVALID_ARGUMENT.
+ *
+ * sp_feature_match: for every row of `a` (na x SP_FPFH_STRIDE) the row of `b` with the smallest squared L2 distance over the 33
+ * bins, computed as |a|^2 + |b|^2 - 2 a.b (the norms summed in double and rounded once, the product on v_mfma_f32_32x32x2_f32:
+ * exact f32, an fmaf chain), clamped at 0; ties in the computed distance go to the lowest index. idx_out na int32, d2_out_opt
+ * na floats (may be null); nb == 0 gives -1 / FLT_MAX. na, nb <= SP_FEATURE_MATCH_MAX. The targets are split into chunks over
+ * the grid and combined by a 64-bit integer atomicMin on (bits of d2) << 32 | index: order-independent.
+ * workspace: sp_feature_match_workspace_bytes(na, nb), which is 0 beyond the limits.
+ *
+ * sp_feature_match_mutual: both directions, then the source rows i with match_t->s(match_s->t(i)) == i, as (i, j) int32 pairs in
+ * ascending i (flags -> scan -> compaction: sp_compact_by_flags). corr_out: room for min(ns, nt) pairs. *count_out_host receives
+ * the number of pairs by one read-back (the call synchronises the stream). workspace: sp_feature_match_mutual_workspace_bytes.
+ *
+ * sp_correspondence_points: cs_out[m] = src_points[corr[m][0]], ct_out[m] = tgt_points[corr[m][1]] (float4 rows). Enqueue only.
+ *
+ * sp_ransac_score: score_out[h] (uint32, device) for hypotheses h in [0, H), H <= SP_RANSAC_MAX_HYPOTHESES, from the matched
+ * points cs, ct (M x float4, device). Hypothesis h draws r_j = splitmix64(seed + 3 h + j), index_j = ((r_j >> 32) * M) >> 32,
+ * j = 0, 1, 2 (sp_ransac_triplets_host computes the same on the host), with splitmix64(z): z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31. It scores 0 unless the three
+ * indices are distinct, every source edge is longer than min_edge, min(l_s, l_t) >= edge_ratio * max(l_s, l_t) for each of the
+ * three edges, and both triangles satisfy |e x f|^2 >= 0.04 |e|^2 |f|^2 (e = p1 - p0, f = p2 - p0). Its pose aligns the triangle
+ * frames e1 = e / |e|, e3 = (e1 x f) / |e1 x f|, e2 = e3 x e1: R = [e1 e2 e3]_t [e1 e2 e3]_s^T, t = centroid_t - R centroid_s;
+ * its score is the number of m with |R cs_m + t - ct_m|^2 < inlier_distance^2. One lane per hypothesis, the matches pass through
+ * LDS in tiles. M < 3: every score 0. Enqueue only.
+ *
+ * sp_ransac_select_host (host memory only): the `guesses` hypotheses with the highest nonzero scores, ties to the lower h, their
+ * poses recomputed in double from the same triplets of host copies of cs, ct: poses_out[g] 16 doubles, column-major;
+ * hyp_out_opt[g] the hypothesis. *count_out <= guesses poses are written (fewer when fewer scores are nonzero). */
+enum { SP_FPFH_BINS = 33, SP_FPFH_STRIDE = 36, SP_FPFH_MAX_K = 64, SP_FEATURE_MATCH_MAX = 1 << 20,
+       SP_RANSAC_MAX_HYPOTHESES = 1 << 20 };
+size_t sp_fpfh_workspace_bytes(size_t n);
+int sp_fpfh_compute(const float* points, const float* normals, size_t n, const int32_t* knn_idx, const float* knn_d2, size_t k,
+                    float* fpfh_out, uint16_t* spfh_counts_out_opt, uint16_t* spfh_m_out_opt, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t sp_feature_match_workspace_bytes(size_t na, size_t nb);
+int sp_feature_match(const float* a, size_t na, const float* b, size_t nb, int32_t* idx_out, float* d2_out_opt, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t sp_feature_match_mutual_workspace_bytes(size_t ns, size_t nt);
+int sp_feature_match_mutual(const float* src, size_t ns, const float* tgt, size_t nt, int32_t* corr_out,
+                            uint32_t* count_out_host, void* workspace, size_t workspace_bytes, void* stream);
+int sp_correspondence_points(const float* src_points, size_t ns, const float* tgt_points, size_t nt, const int32_t* corr, size_t m,
+                             float* cs_out, float* ct_out, void* stream);
+int sp_ransac_score(const float* cs, const float* ct, size_t m, size_t hypotheses, uint64_t seed, float inlier_distance,
+                    float min_edge, float edge_ratio, uint32_t* score_out, void* stream);
+int sp_ransac_triplets_host(uint64_t seed, size_t first_hypothesis, size_t count, size_t m, uint32_t* triplets_out);
+int sp_ransac_select_host(const uint32_t* scores_host, size_t hypotheses, const float* cs_host, const float* ct_host, size_t m,
+                          uint64_t seed, size_t guesses, double* poses_out, uint32_t* hyp_out_opt, size_t* count_out);
+
 #ifdef __cplusplus
 }
 #endif

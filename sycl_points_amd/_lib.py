@@ -415,7 +415,18 @@ SIGNATURES = {
     "sp_pc2_pack": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_double, _vp, _vp]),
     "sp_enhanced_reflectivity_workspace_bytes": (_sz, [_sz]),
     "sp_enhanced_reflectivity": (_i, [_vp, _vp, _sz, _vp, C.c_uint32, C.c_int32, _i, C.c_int32, _vp, _f, _f, _vp, _vp]),
+    "sp_fpfh_workspace_bytes": (_sz, [_sz]),
+    "sp_fpfh_compute": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_feature_match_workspace_bytes": (_sz, [_sz, _sz]),
+    "sp_feature_match": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "sp_feature_match_mutual_workspace_bytes": (_sz, [_sz, _sz]),
+    "sp_feature_match_mutual": (_i, [_vp, _sz, _vp, _sz, _vp, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
+    "sp_correspondence_points": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "sp_ransac_score": (_i, [_vp, _vp, _sz, _sz, C.c_uint64, _f, _f, _f, _vp, _vp]),
+    "sp_ransac_triplets_host": (_i, [C.c_uint64, _sz, _sz, _sz, _vp]),
+    "sp_ransac_select_host": (_i, [_vp, _sz, _vp, _vp, _sz, C.c_uint64, _sz, _vp, _vp, C.POINTER(_sz)]),
 }
+FPFH_BINS, FPFH_STRIDE, FPFH_MAX_K, FEATURE_MATCH_MAX, RANSAC_MAX_HYPOTHESES = 33, 36, 64, 1 << 20, 1 << 20  # SP_FPFH_*, ...
 
 
 # csrc/sp_internal.h: per-handle measurement / tuning switches, exported for tests/, bench.py and scratch/ — not part of the

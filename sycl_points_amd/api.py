@@ -615,6 +615,123 @@ class covariance:
         return out
 
 
+# ------------------------------------------------------------------ global registration (MI355X extension)
+def _ws_bytes(nbytes, device):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def fpfh(neighbors, cloud, want_counts=False):
+    """feature::compute_fpfh_async (MI355X extension; sp_fpfh_compute): one FPFH row of 36 floats (33 bins, 3 zeros) per point of
+    `cloud` from a kNN result of the cloud on itself (k <= 64). The cloud's normals must be of unit length and consistently
+    oriented (covariance.estimate_normals on a sensor-centred scan). want_counts: also the SPFH counts (n, 33) and m (n,) as
+    int32 tensors."""
+    p = _dev_f32(cloud.points, 4)
+    if not cloud.has_normal():
+        raise SpError(2, "[feature::compute_fpfh_async] normals not computed")
+    nrm = _dev_f32(cloud.normals, 4)
+    idx, d2 = neighbors.indices, neighbors.distances
+    n, k = p.shape[0], int(idx.shape[1]) if idx.dim() == 2 else 0
+    L = _lib.lib()
+    out = torch.empty((n, _lib.FPFH_STRIDE), dtype=torch.float32, device=p.device)
+    counts = torch.zeros((n, _lib.FPFH_BINS), dtype=torch.int16, device=p.device) if want_counts else None
+    m = torch.zeros(n, dtype=torch.int16, device=p.device) if want_counts else None
+    nbytes = L.sp_fpfh_workspace_bytes(n)
+    ws = _ws_bytes(nbytes, p.device)
+    check(L.sp_fpfh_compute(_ptr(p), _ptr(nrm), n, _ptr(idx), _ptr(d2), k, _ptr(out), _ptr(counts), _ptr(m), _ptr(ws), ws.numel(),
+                            _stream()))
+    if want_counts:  # (uint16 on the device)
+        return out, counts.to(torch.int32) & 0xFFFF, m.to(torch.int32) & 0xFFFF
+    return out
+
+
+def _feature_rows(t):
+    t = _dev_f32(t)
+    if t.dim() != 2 or t.shape[1] != _lib.FPFH_STRIDE:
+        raise SpError(1, f"expected descriptor rows of shape (N, {_lib.FPFH_STRIDE}), got {tuple(t.shape)}")
+    return t
+
+
+def match_features(a, b):
+    """registration::match_features (sp_feature_match): for every row of `a` the nearest row of `b` over the 33 bins ->
+    (indices int32, squared distances); -1 / FLT_MAX for an empty b; ties to the lowest index."""
+    a, b = _feature_rows(a), _feature_rows(b)
+    L = _lib.lib()
+    na, nb = a.shape[0], b.shape[0]
+    idx = torch.empty(na, dtype=torch.int32, device=a.device)
+    d2 = torch.empty(na, dtype=torch.float32, device=a.device)
+    ws = _ws_bytes(L.sp_feature_match_workspace_bytes(na, nb), a.device)
+    check(L.sp_feature_match(_ptr(a), na, _ptr(b), nb, _ptr(idx), _ptr(d2), _ptr(ws), ws.numel(), _stream()))
+    return idx, d2
+
+
+def match_features_mutual(src, tgt):
+    """sp_feature_match_mutual: the (i, j) pairs with j the nearest row of `tgt` to src[i] and i the nearest row of `src` to
+    tgt[j], ascending in i -> (M, 2) int32 tensor. One read-back (the count)."""
+    src, tgt = _feature_rows(src), _feature_rows(tgt)
+    L = _lib.lib()
+    ns, nt = src.shape[0], tgt.shape[0]
+    corr = torch.empty((max(min(ns, nt), 1), 2), dtype=torch.int32, device=src.device)
+    ws = _ws_bytes(L.sp_feature_match_mutual_workspace_bytes(ns, nt), src.device)
+    count = C.c_uint32(0)
+    check(L.sp_feature_match_mutual(_ptr(src), ns, _ptr(tgt), nt, _ptr(corr), C.byref(count), _ptr(ws), ws.numel(), _stream()))
+    return corr[:int(count.value)]
+
+
+def correspondence_points(source_points, target_points, corr):
+    """sp_correspondence_points: the matched points (M, 4) of both clouds, in the order of `corr`."""
+    s, t = _dev_f32(_points_of(source_points), 4), _dev_f32(_points_of(target_points), 4)
+    m = int(corr.shape[0])
+    cs = torch.empty((m, 4), dtype=torch.float32, device=s.device)
+    ct = torch.empty((m, 4), dtype=torch.float32, device=s.device)
+    check(_lib.lib().sp_correspondence_points(_ptr(s), s.shape[0], _ptr(t), t.shape[0], _ptr(corr.contiguous()), m, _ptr(cs), _ptr(ct),
+                                              _stream()))
+    return cs, ct
+
+
+def ransac_scores(cs, ct, hypotheses, inlier_distance, min_edge=0.0, edge_ratio=0.9, seed=0):
+    """sp_ransac_score: the number of matches each of `hypotheses` triplet poses explains (0 for a triplet that fails a gate) ->
+    int32 tensor on the device."""
+    cs, ct = _dev_f32(cs, 4), _dev_f32(ct, 4)
+    score = torch.empty(max(int(hypotheses), 1), dtype=torch.int32, device=cs.device)
+    check(_lib.lib().sp_ransac_score(_ptr(cs), _ptr(ct), cs.shape[0], int(hypotheses), int(seed), inlier_distance, min_edge, edge_ratio,
+                                     _ptr(score), _stream()))
+    return score[:int(hypotheses)]
+
+
+def ransac_triplets(seed, hypotheses, m, first=0):
+    """sp_ransac_triplets_host: the matches hypotheses first .. first + hypotheses - 1 draw -> (hypotheses, 3) uint32 numpy"""
+    out = np.zeros((int(hypotheses), 3), np.uint32)
+    check(_lib.lib().sp_ransac_triplets_host(int(seed), int(first), int(hypotheses), int(m), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def ransac_select(scores, cs, ct, guesses, seed=0):
+    """sp_ransac_select_host: the `guesses` best hypotheses (ties to the lower index) and their poses in double, from host copies
+    of the scores and the matched points (tensors are copied down) -> (poses (B', 4, 4) float64, hypotheses (B',) uint32)."""
+    host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dt)  # noqa: E731
+    sc, csh, cth = host(scores, np.int32).view(np.uint32), host(cs, np.float32), host(ct, np.float32)
+    B = int(guesses)
+    poses = np.zeros((max(B, 1), 16), np.float64)
+    hyp = np.zeros(max(B, 1), np.uint32)
+    count = C.c_size_t(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(_lib.lib().sp_ransac_select_host(vp(sc), sc.shape[0], vp(csh), vp(cth), csh.shape[0], int(seed), B, vp(poses), vp(hyp),
+                                           C.byref(count)))
+    v = int(count.value)
+    return poses[:v].reshape(v, 4, 4).transpose(0, 2, 1).copy(), hyp[:v].copy()
+
+
+@dataclass
+class GlobalRegistrationParams:
+    """registration::GlobalRegistrationParams (MI355X extension)"""
+    hypotheses: int = 50000
+    guesses: int = 64
+    inlier_distance: float = 1.0   # tau: a match counts for a hypothesis when its residual is below this
+    min_edge: float = 0.0          # every source edge of a triplet must be longer
+    edge_ratio: float = 0.9        # the shorter of two matching edges against the longer
+    seed: int = 0
+
+
 # ------------------------------------------------------------------ voxel grid
 class VoxelGrid:
     """algorithms/filter/voxel_downsampling.hpp:14-289"""
@@ -2040,6 +2157,41 @@ class Registration:
         best = C.c_size_t(len(results))
         check(_lib.lib().sp_align_best_host(C.byref(blocks), len(results), C.byref(best)))
         return int(best.value)
+
+    def align_global(self, source, source_features, target, target_features, prepared_target, params=None, return_all=False,
+                     robust_scales=None, sort_by_cell=True):
+        """MI355X extension: Registration::align without an initial guess. The mutual nearest neighbours of the two clouds' FPFH
+        rows (fpfh()) are the matches; params.hypotheses poses of matched triplets are scored by the matches they explain
+        (sp_ransac_score), the params.guesses best become the initial guesses of align_batch against `prepared_target` (a
+        PreparedTarget, or a VoxelHashMap: align_voxel_map_batch), and best_of picks the winner. Fewer than three matches, no
+        hypothesis that passes its gates, or no alignment that best_of accepts: a result with converged == False and the
+        identity; nothing throws. return_all: (winner, every alignment's result, the guesses as 4x4 float32). sort_by_cell: how
+        align_batch prepares the source ("presorted" is what the C++ facade takes for sources of up to 4096 points). Two
+        read-backs before the alignment (the match count; the scores and the matched points), one after."""
+        gp = params or GlobalRegistrationParams()
+        none = RegistrationResult()
+        done = lambda res, results=(), guesses=(): (res, list(results), list(guesses)) if return_all else res  # noqa: E731
+        if source.size() == 0 or target.size() == 0 or gp.hypotheses <= 0 or gp.guesses <= 0:
+            return done(none)
+        corr = match_features_mutual(source_features, target_features)
+        if corr.shape[0] < 3:
+            return done(none)
+        cs, ct = correspondence_points(source, target, corr)
+        score = ransac_scores(cs, ct, gp.hypotheses, gp.inlier_distance, gp.min_edge, gp.edge_ratio, gp.seed)
+        poses, hyp = ransac_select(score, cs, ct, gp.guesses, gp.seed)
+        if len(poses) == 0:
+            return done(none)
+        guesses = [np.ascontiguousarray(T, np.float32) for T in poses]
+        if isinstance(prepared_target, VoxelHashMap):
+            results = self.align_voxel_map_batch(source, prepared_target, guesses, robust_scales)
+        else:
+            results = self.align_batch(source, prepared_target, guesses, robust_scales, sort_by_cell)
+        best = self.best_of(results)
+        if best >= len(results):
+            return done(none, results, guesses)
+        res = results[best]
+        res.hypothesis, res.matches = int(hyp[best]), int(corr.shape[0])
+        return done(res, results, guesses)
 
     @staticmethod
     def _result_from_align_result(r):
