@@ -471,41 +471,13 @@ public:
             ptgt_covs_ = target.covs.get();
             ptgt_covs_gen_ = target.covs->generation();
         }
-        // device: poses | result blocks | the hypotheses' cache rows; pinned host: poses | result blocks
-        const size_t poses_bytes = (B * 16 * sizeof(float) + 255) / 256 * 256, res_bytes = (B * sizeof(sp_align_result) + 255) / 256 * 256;
-        const size_t rows_bytes = sp_gicp_align_batch_workspace_bytes(N, B);
-        if (batch_dev_bytes_ < poses_bytes + res_bytes + rows_bytes) {
-            if (batch_dev_) hip_check(hipFree(batch_dev_), "hipFree");
-            batch_dev_ = nullptr; batch_dev_bytes_ = 0;
-            hip_check(hipMalloc(&batch_dev_, poses_bytes + res_bytes + rows_bytes), "hipMalloc");
-            batch_dev_bytes_ = poses_bytes + res_bytes + rows_bytes;
-        }
-        if (batch_pin_bytes_ < poses_bytes + res_bytes) {
-            if (batch_pin_) hip_check(hipHostFree(batch_pin_), "hipHostFree");
-            batch_pin_ = nullptr; batch_pin_bytes_ = 0;
-            hip_check(hipHostMalloc(&batch_pin_, poses_bytes + res_bytes), "hipHostMalloc");
-            batch_pin_bytes_ = poses_bytes + res_bytes;
-        }
-        float* const T_dev = reinterpret_cast<float*>(batch_dev_);
-        sp_align_result* const res_dev = reinterpret_cast<sp_align_result*>(batch_dev_ + poses_bytes);
-        float* const T_host = reinterpret_cast<float*>(batch_pin_);
-        const sp_align_result* const res_host = reinterpret_cast<const sp_align_result*>(batch_pin_ + poses_bytes);
-        for (size_t b = 0; b < B; ++b) std::memcpy(T_host + 16 * b, initial_guesses[b].data(), 16 * sizeof(float));
-        hip_check(hipMemcpyAsync(T_dev, T_host, B * 16 * sizeof(float), hipMemcpyHostToDevice, queue_.stream()), "H2D");
-        const sp_factor_params fp = factor_params(robust_scale);
-        const sp_opt_params op = opt_params();
-        throw_on_error(sp_gicp_align_batch(ptgt_, psrc_, T_dev, T_dev, B, &fp, &op, &robust_scale, 1, res_dev,
-                                           batch_dev_ + poses_bytes + res_bytes, rows_bytes, queue_.stream()));
-        hip_check(hipMemcpyAsync(batch_pin_ + poses_bytes, res_dev, B * sizeof(sp_align_result), hipMemcpyDeviceToHost, queue_.stream()), "D2H");
-        hip_check(hipStreamSynchronize(queue_.stream()), "sync");
-        for (size_t b = 0; b < B; ++b) out.push_back(to_registration_result(res_host[b]));
-        last_opt_linearizations_ = res_host[B - 1].linearizations;
-        last_opt_trials_ = res_host[B - 1].trials;
-        // nothing is frozen for compute_error_frozen (see above): neither the source's cache nor neighbors_ describes this batch
-        last_lin_fused_ = false;
-        fused_loop_active_ = false;
-        neighbors_.resize(0, 1);
-        return out;
+        const size_t rows_bytes = sp_gicp_align_batch_workspace_bytes(N, B);  // the hypotheses' cache rows
+        return run_batch(initial_guesses, rows_bytes, [&](float* T_dev, sp_align_result* res_dev, char* workspace, size_t workspace_bytes) {
+            const sp_factor_params fp = factor_params(robust_scale);
+            const sp_opt_params op = opt_params();
+            throw_on_error(sp_gicp_align_batch(ptgt_, psrc_, T_dev, T_dev, B, &fp, &op, &robust_scale, 1, res_dev, workspace,
+                                               workspace_bytes, queue_.stream()));
+        });
     }
     /// Where align_batch's one launch starts to win over align() per guess. Measured: a workgroup alone walks a
     /// 1000-point sample of a voxel-downsampled scan in 0.71 ms where the single launch, spread over the device, takes 0.2 ms, and
@@ -547,42 +519,14 @@ public:
         const float robust_scale = options.robust_scale > 0.0f ? options.robust_scale : params_.robust.default_scale;
         const int reg = int(params_.reg_type);
         if (!target_map.registration_ready(reg)) target_map.prepare_registration(reg);
-        // device: poses | result blocks | source rows and the hypotheses' slots; pinned host: poses | result blocks
-        const size_t poses_bytes = (B * 16 * sizeof(float) + 255) / 256 * 256, res_bytes = (B * sizeof(sp_align_result) + 255) / 256 * 256;
-        const size_t ws_bytes = sp_vhm_align_batch_workspace_bytes(N, B);
-        if (batch_dev_bytes_ < poses_bytes + res_bytes + ws_bytes) {
-            if (batch_dev_) hip_check(hipFree(batch_dev_), "hipFree");
-            batch_dev_ = nullptr; batch_dev_bytes_ = 0;
-            hip_check(hipMalloc(&batch_dev_, poses_bytes + res_bytes + ws_bytes), "hipMalloc");
-            batch_dev_bytes_ = poses_bytes + res_bytes + ws_bytes;
-        }
-        if (batch_pin_bytes_ < poses_bytes + res_bytes) {
-            if (batch_pin_) hip_check(hipHostFree(batch_pin_), "hipHostFree");
-            batch_pin_ = nullptr; batch_pin_bytes_ = 0;
-            hip_check(hipHostMalloc(&batch_pin_, poses_bytes + res_bytes), "hipHostMalloc");
-            batch_pin_bytes_ = poses_bytes + res_bytes;
-        }
-        float* const T_dev = reinterpret_cast<float*>(batch_dev_);
-        sp_align_result* const res_dev = reinterpret_cast<sp_align_result*>(batch_dev_ + poses_bytes);
-        float* const T_host = reinterpret_cast<float*>(batch_pin_);
-        const sp_align_result* const res_host = reinterpret_cast<const sp_align_result*>(batch_pin_ + poses_bytes);
-        for (size_t b = 0; b < B; ++b) std::memcpy(T_host + 16 * b, initial_guesses[b].data(), 16 * sizeof(float));
-        hip_check(hipMemcpyAsync(T_dev, T_host, B * 16 * sizeof(float), hipMemcpyHostToDevice, queue_.stream()), "H2D");
-        const sp_factor_params fp = factor_params(robust_scale);
-        const sp_opt_params op = opt_params();
-        throw_on_error(sp_vhm_align_batch(target_map.handle(), source.points_device(), source.has_cov() ? source.covs_device() : nullptr, N,
-                                          T_dev, T_dev, B, &fp, &op, &robust_scale, 1, voxel_neighbors_, res_dev, nullptr,
-                                          batch_dev_ + poses_bytes + res_bytes, ws_bytes, queue_.stream()));
-        hip_check(hipMemcpyAsync(batch_pin_ + poses_bytes, res_dev, B * sizeof(sp_align_result), hipMemcpyDeviceToHost, queue_.stream()), "D2H");
-        hip_check(hipStreamSynchronize(queue_.stream()), "sync");
-        for (size_t b = 0; b < B; ++b) out.push_back(to_registration_result(res_host[b]));
-        last_opt_linearizations_ = res_host[B - 1].linearizations;
-        last_opt_trials_ = res_host[B - 1].trials;
-        // nothing is frozen for compute_error_frozen: neither the source's cache nor neighbors_ describes this batch
-        last_lin_fused_ = false;
-        fused_loop_active_ = false;
-        if (neighbors_.indices != nullptr) neighbors_.resize(0, 1);  // (never allocated when only maps have been aligned against)
-        return out;
+        const size_t ws_bytes = sp_vhm_align_batch_workspace_bytes(N, B);  // the source rows and the hypotheses' slots
+        return run_batch(initial_guesses, ws_bytes, [&](float* T_dev, sp_align_result* res_dev, char* workspace, size_t workspace_bytes) {
+            const sp_factor_params fp = factor_params(robust_scale);
+            const sp_opt_params op = opt_params();
+            throw_on_error(sp_vhm_align_batch(target_map.handle(), source.points_device(), source.has_cov() ? source.covs_device() : nullptr,
+                                              N, T_dev, T_dev, B, &fp, &op, &robust_scale, 1, voxel_neighbors_, res_dev, nullptr, workspace,
+                                              workspace_bytes, queue_.stream()));
+        });
     }
     /// Where the voxel-map batch starts to win over align(source, map) per guess. Measured: already a single
     /// guess is ahead, 125 us against 341 us on 1000 points of the three planes and 319 us against 506 us on the bundled pair
@@ -811,6 +755,45 @@ private:
         result.inlier = h.inlier;
         result.H_raw = result.H; result.b_raw = result.b; result.error_raw = h.error_raw;
         return result;
+    }
+    /// The hand-off of both align_batch overloads: the poses up in one copy, `launch(T_dev, res_dev, workspace, workspace_bytes)`
+    /// (the one C call, poses updated in place), the result blocks back in one read-back. Device: poses | result blocks |
+    /// workspace; pinned host: poses | result blocks; both grown to the largest batch so far.
+    template <class Launch>
+    std::vector<RegistrationResult> run_batch(const std::vector<TransformMatrix>& guesses, size_t workspace_bytes, Launch&& launch) {
+        const size_t B = guesses.size();
+        const size_t poses_bytes = (B * 16 * sizeof(float) + 255) / 256 * 256, res_bytes = (B * sizeof(sp_align_result) + 255) / 256 * 256;
+        if (batch_dev_bytes_ < poses_bytes + res_bytes + workspace_bytes) {
+            if (batch_dev_) hip_check(hipFree(batch_dev_), "hipFree");
+            batch_dev_ = nullptr; batch_dev_bytes_ = 0;
+            hip_check(hipMalloc(&batch_dev_, poses_bytes + res_bytes + workspace_bytes), "hipMalloc");
+            batch_dev_bytes_ = poses_bytes + res_bytes + workspace_bytes;
+        }
+        if (batch_pin_bytes_ < poses_bytes + res_bytes) {
+            if (batch_pin_) hip_check(hipHostFree(batch_pin_), "hipHostFree");
+            batch_pin_ = nullptr; batch_pin_bytes_ = 0;
+            hip_check(hipHostMalloc(&batch_pin_, poses_bytes + res_bytes), "hipHostMalloc");
+            batch_pin_bytes_ = poses_bytes + res_bytes;
+        }
+        float* const T_dev = reinterpret_cast<float*>(batch_dev_);
+        sp_align_result* const res_dev = reinterpret_cast<sp_align_result*>(batch_dev_ + poses_bytes);
+        float* const T_host = reinterpret_cast<float*>(batch_pin_);
+        const sp_align_result* const res_host = reinterpret_cast<const sp_align_result*>(batch_pin_ + poses_bytes);
+        for (size_t b = 0; b < B; ++b) std::memcpy(T_host + 16 * b, guesses[b].data(), 16 * sizeof(float));
+        hip_check(hipMemcpyAsync(T_dev, T_host, B * 16 * sizeof(float), hipMemcpyHostToDevice, queue_.stream()), "H2D");
+        launch(T_dev, res_dev, batch_dev_ + poses_bytes + res_bytes, workspace_bytes);
+        hip_check(hipMemcpyAsync(batch_pin_ + poses_bytes, res_dev, B * sizeof(sp_align_result), hipMemcpyDeviceToHost, queue_.stream()), "D2H");
+        hip_check(hipStreamSynchronize(queue_.stream()), "sync");
+        std::vector<RegistrationResult> out;
+        out.reserve(B);
+        for (size_t b = 0; b < B; ++b) out.push_back(to_registration_result(res_host[b]));
+        last_opt_linearizations_ = res_host[B - 1].linearizations;
+        last_opt_trials_ = res_host[B - 1].trials;
+        // nothing is frozen for compute_error_frozen: neither the source's cache nor neighbors_ describes this batch
+        last_lin_fused_ = false;
+        fused_loop_active_ = false;
+        if (neighbors_.indices != nullptr) neighbors_.resize(0, 1);  // (never allocated when only maps have been aligned against)
+        return out;
     }
     sp_linearized read_lin() const {  // the reference's wait_and_throw + toCPU(0) (registration.hpp:674-675)
         sp_linearized* const h = static_cast<sp_linearized*>(pin_);

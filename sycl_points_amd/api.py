@@ -2111,21 +2111,6 @@ class Registration:
         p = self.params
         guesses = [np.asarray(T, np.float32) for T in initial_guesses]
         B, n = len(guesses), source.size()
-        dev = source.points.device
-        rsz = C.sizeof(_lib.AlignResult)
-        need = L.sp_gicp_align_batch_workspace_bytes(n, B)
-        bufs = getattr(self, "_batch_bufs", None)
-        if bufs is None or bufs[0].device != dev or bufs[0].numel() < 16 * max(B, 1) or bufs[3].numel() < need:
-            # (sized for this call, kept for the next one that fits)
-            bufs = (torch.zeros(16 * max(B, 1), dtype=torch.float32, device=dev),
-                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8, device=dev),
-                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8).pin_memory(),
-                    torch.empty(max(need, 16), dtype=torch.uint8, device=dev))
-            self._batch_bufs = bufs
-        T_dev, res_dev, res_host, ws = bufs
-        if B:
-            poses = np.stack([_T16(T).reshape(-1) for T in guesses])  # one copy up
-            T_dev[:16 * B].copy_(torch.from_numpy(poses.reshape(-1).copy()), non_blocking=True)
         psrc, _ = self._prepared_source(n)
         if prepare:
             psrc.prepare(prepared_target, source, guesses[0] if B else None, sort_by_cell)
@@ -2133,8 +2118,36 @@ class Registration:
         fp = self._factor_params(scales[0])
         op = self.opt_params()
         sc = (C.c_float * len(scales))(*scales)
-        check(L.sp_gicp_align_batch(prepared_target._h, psrc._h, _ptr(T_dev), _ptr(T_dev), B, C.byref(fp), C.byref(op), sc, len(scales),
-                                    _ptr(res_dev), _ptr(ws), ws.numel(), _stream()))
+
+        def call(T_dev, res_dev, ws):
+            check(L.sp_gicp_align_batch(prepared_target._h, psrc._h, _ptr(T_dev), _ptr(T_dev), B, C.byref(fp), C.byref(op), sc,
+                                        len(scales), _ptr(res_dev), _ptr(ws), ws.numel(), _stream()))
+
+        return self._run_batch(source.points.device, guesses, L.sp_gicp_align_batch_workspace_bytes(n, B), call)
+
+    def _run_batch(self, dev, guesses, need_bytes, call, results=None):
+        """The hand-off of both batch alignments: the poses up in one copy, `call(T_dev, res_dev, ws)` (the one ctypes call: poses in
+        T_dev, result blocks into res_dev — `results` when given —, a workspace of at least need_bytes), the blocks back in one
+        read-back, one result per guess with its `block`. The buffers (poses | blocks | pinned blocks | workspace) are one tuple,
+        _batch_bufs, grown to the largest need so far."""
+        B = len(guesses)
+        rsz = C.sizeof(_lib.AlignResult)
+        bufs = getattr(self, "_batch_bufs", None)
+        if bufs is not None and bufs[0].device != dev:
+            bufs = None
+        if bufs is None or bufs[0].numel() < 16 * max(B, 1) or bufs[3].numel() < need_bytes:
+            slots = max(B, 1, bufs[0].numel() // 16 if bufs else 0)
+            bufs = (torch.zeros(16 * slots, dtype=torch.float32, device=dev),
+                    torch.zeros(rsz * slots, dtype=torch.uint8, device=dev),
+                    torch.zeros(rsz * slots, dtype=torch.uint8).pin_memory(),
+                    torch.empty(max(need_bytes, 16, bufs[3].numel() if bufs else 0), dtype=torch.uint8, device=dev))
+            self._batch_bufs = bufs
+        T_dev, res_dev, res_host, ws = bufs
+        res_dev = res_dev if results is None else results
+        if B:
+            poses = np.stack([_T16(T).reshape(-1) for T in guesses])  # one copy up
+            T_dev[:16 * B].copy_(torch.from_numpy(poses.reshape(-1).copy()), non_blocking=True)
+        call(T_dev, res_dev, ws)
         res_host[:rsz * B].copy_(res_dev[:rsz * B], non_blocking=True)  # one copy down
         torch.cuda.current_stream().synchronize()
         raw = res_host[:rsz * B].numpy().tobytes()
@@ -2357,44 +2370,26 @@ class Registration:
         guesses = [np.asarray(T, np.float32) for T in initial_guesses]
         B, n = len(guesses), source.size()
         dev = source.points.device
-        rsz = C.sizeof(_lib.AlignResult)
         if p.robust_type != "NONE" and p.robust_default_scale <= 0.0:
             p.robust_type = "NONE"
         if prepare and p.reg_type in ("GICP", "POINT_TO_DISTRIBUTION") and not voxel_map.registration_ready(p.reg_type):
             voxel_map.prepare_registration(p.reg_type)
-        need = L.sp_vhm_align_batch_workspace_bytes(n, B)
-        bufs = getattr(self, "_vbatch_bufs", None)
-        if bufs is None or bufs[0].device != dev or bufs[0].numel() < 16 * max(B, 1) or bufs[3].numel() < need:
-            # (sized for this call, kept for the next one that fits)
-            bufs = (torch.zeros(16 * max(B, 1), dtype=torch.float32, device=dev),
-                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8, device=dev),
-                    torch.zeros(rsz * max(B, 1), dtype=torch.uint8).pin_memory(),
-                    torch.empty(max(need, 16), dtype=torch.uint8, device=dev))
-            self._vbatch_bufs = bufs
-        T_dev, res_dev, res_host, ws = bufs
-        res_dev = res_dev if results is None else results
-        if B:
-            poses = np.stack([_T16(T).reshape(-1) for T in guesses])  # one copy up
-            T_dev[:16 * B].copy_(torch.from_numpy(poses.reshape(-1).copy()), non_blocking=True)
         keys = torch.empty(max(B * n, 1), dtype=torch.int64, device=dev) if want_keys else None
         scales = list(robust_scales) if robust_scales else [p.robust_default_scale]
         fp = self._factor_params(scales[0])
         op = self.opt_params()
         sc = (C.c_float * len(scales))(*scales)
-        check(L.sp_vhm_align_batch(voxel_map._h, _ptr(source.points) if n else None, _ptr(source.covs if source.has_cov() else None), n,
-                                   _ptr(T_dev), _ptr(T_dev if T_out is None else T_out), B, C.byref(fp), C.byref(op), sc, len(scales),
-                                   int(neighbor_voxels), _ptr(res_dev), _ptr(keys), _ptr(ws),
-                                   ws.numel() if workspace_bytes is None else workspace_bytes, _stream()))
-        res_host[:rsz * B].copy_(res_dev[:rsz * B], non_blocking=True)  # one copy down
-        torch.cuda.current_stream().synchronize()
-        raw = res_host[:rsz * B].numpy().tobytes()
-        out = []
-        for b in range(B):
-            res = self._result_from_align_result(_lib.AlignResult.from_buffer_copy(raw, rsz * b))
-            res.block = raw[rsz * b:rsz * (b + 1)]  # the sp_align_result as the launch wrote it
-            if want_keys:
+
+        def call(T_dev, res_dev, ws):
+            check(L.sp_vhm_align_batch(voxel_map._h, _ptr(source.points) if n else None, _ptr(source.covs if source.has_cov() else None),
+                                       n, _ptr(T_dev), _ptr(T_dev if T_out is None else T_out), B, C.byref(fp), C.byref(op), sc,
+                                       len(scales), int(neighbor_voxels), _ptr(res_dev), _ptr(keys), _ptr(ws),
+                                       ws.numel() if workspace_bytes is None else workspace_bytes, _stream()))
+
+        out = self._run_batch(dev, guesses, L.sp_vhm_align_batch_workspace_bytes(n, B), call, results)
+        if want_keys:
+            for b, res in enumerate(out):
                 res.keys = keys[b * n:(b + 1) * n]
-            out.append(res)
         return out
 
     def _host_loop(self, T, linearize_at, error_at, scale):

@@ -20,7 +20,7 @@
 // of step s, i.e. after every workgroup has finished reading the rows of step s - 1 that it overwrites.
 #include <algorithm>
 
-#include "sp_optimizer.h"
+#include "sp_optimize_batch.h"
 
 namespace sp {
 namespace {
@@ -44,10 +44,8 @@ struct OptArgs {
     unsigned long long budget;    // wall_clock64 ticks a wait may take
 };
 
-using OptShared = OptState;  // sp_optimizer.h: the state machine's state, in LDS, identical in every workgroup
-
 // After a linearisation step: tot = 28 sums, the uint32 count, the searched count as a float value.
-__device__ __forceinline__ void opt_after_linearize_impl(OptShared& S, const float* tot, bool publish) {
+__device__ __forceinline__ void opt_after_linearize_impl(OptState& S, const float* tot, bool publish) {
     unpack_totals(tot, kAcc - 1, &S.slin);
     ++S.ctl.n_lin;
     S.ctl.searched += (unsigned)tot[kAcc];
@@ -55,7 +53,7 @@ __device__ __forceinline__ void opt_after_linearize_impl(OptShared& S, const flo
 }
 
 // After a trial step: tot[0] = the robust error at the trial pose, tot[1] = the uint32 inlier count.
-__device__ __forceinline__ void opt_after_trial_impl(OptShared& S, const float* tot, bool publish) {
+__device__ __forceinline__ void opt_after_trial_impl(OptState& S, const float* tot, bool publish) {
     opt_after_trial(S, tot[0], __float_as_uint(tot[1]), publish);
 }
 
@@ -65,7 +63,7 @@ __device__ __forceinline__ void opt_after_trial_impl(OptShared& S, const float* 
 // robust error / inlier count. The trial is decided exactly as a plain trial step decides it; when its pose was taken and what
 // follows is the linearisation that was speculated on (same pose, the level whose scale it used), that linearisation is adopted
 // as if its step had just run: the same sequence of state-machine calls as the unfused loop, one hand-off less.
-__device__ __forceinline__ void opt_after_fused_impl(OptShared& S, const float* tot, bool publish) {
+__device__ __forceinline__ void opt_after_fused_impl(OptState& S, const float* tot, bool publish) {
     OptCtl& c = S.ctl;
     const float trial[2] = {tot[30], tot[31]};
     opt_after_trial_impl(S, trial, publish);
@@ -76,25 +74,14 @@ __device__ __forceinline__ void opt_after_fused_impl(OptShared& S, const float* 
 }
 // A trial is due: make it a fused step when there is a linearisation to speculate on (an accepted trial that ends the last level
 // is followed by nothing).
-__device__ __forceinline__ void opt_upgrade_trial(OptShared& S, int fuse) {
+__device__ __forceinline__ void opt_upgrade_trial(OptState& S, int fuse) {
     OptCtl& c = S.ctl;
     if (!fuse || c.done || c.phase != PHASE_TRIAL) return;
     const int next = (c.conv_any || c.iter + 1 >= S.opt.max_iterations) ? c.level + 1 : c.level;
     if (next < S.n_levels) { c.phase = PHASE_FUSED; c.spec_level = next; }
 }
-__device__ __noinline__ void opt_after_linearize_call(OptShared& S, const float* tot, bool publish) { opt_after_linearize_impl(S, tot, publish); }
-__device__ __noinline__ void opt_after_trial_call(OptShared& S, const float* tot, bool publish) { opt_after_trial_impl(S, tot, publish); }
-
-// The results (workgroup 0): RegistrationResult of the last level + the linearisation pose + counters.
-__device__ __forceinline__ void opt_publish(float* T_out, const OptShared& S) {
-    sp_align_result* const r = S.result;
-    const unsigned t = threadIdx.x;
-    if (t < 16) { r->T[t] = S.sT[t]; T_out[t] = S.sT[t]; }
-    else if (t < 32) r->T_lin[t - 16] = S.sTlin[t - 16];
-    else if (t >= 64 && t < 100) r->H[t - 64] = S.slin.H[t - 64];
-    else if (t >= 128 && t < 134) r->b[t - 128] = S.slin.b[t - 128];
-    else if (t == 192) opt_result_scalars(S, r);  // (pad[0]: the done flag, stored last by the caller of this function)
-}
+__device__ __noinline__ void opt_after_linearize_call(OptState& S, const float* tot, bool publish) { opt_after_linearize_impl(S, tot, publish); }
+__device__ __noinline__ void opt_after_trial_call(OptState& S, const float* tot, bool publish) { opt_after_trial_impl(S, tot, publish); }
 
 // BLOCK: lanes per workgroup. The search of a linearisation is bound by vector issue (thousands of wave instructions per 64
 // points), so a SMALL source wants its waves on many compute units, each wave alone on its SIMD — workgroups of 256 lanes —
@@ -206,27 +193,14 @@ __device__ __forceinline__ float waveq_row_slot(const float (&acc)[NV], unsigned
 constexpr size_t kWaveQueryMax = 2048, kWaveQueryForcedMax = 131072;
 template <int LOSS, bool FAST_NN, bool P2D, int BLOCK, bool WAVEQ = false>
 __global__ __launch_bounds__(BLOCK) void gicp_optimize_kernel(FusedParams P, OptArgs A) {
-    __shared__ OptShared S;
+    __shared__ OptState S;
     __shared__ float red[BLOCK / 32][kPartial];
     __shared__ unsigned s_wait;
     const unsigned stride = gridDim.x * BLOCK;
     const unsigned tile = xcd_tile();
     const bool single = gridDim.x == 1;
     const bool publish = blockIdx.x == 0;
-    if (threadIdx.x < 16) {
-        S.sT[threadIdx.x] = A.T_init[threadIdx.x];
-        S.sTlin[threadIdx.x] = A.T_init[threadIdx.x];
-    } else if (threadIdx.x == 32) {
-        OptCtl c;
-        opt_start(c, A.opt, P.cache_valid);
-        S.ctl = c;
-        S.opt = A.opt;
-        S.n_levels = A.n_levels;
-        S.reuse = A.reuse;
-        S.result = A.result;
-    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 48) {
-        reinterpret_cast<float*>(&S.slin)[threadIdx.x - 64] = 0.0f;
-    }
+    opt_state_init(S, A.T_init, A.opt, A.n_levels, A.reuse, P.cache_valid, A.result);  // (identical in every workgroup)
     __syncthreads();
 #ifdef SP_OPT_TIMING
     unsigned long long wg_t0 = 0;
@@ -335,11 +309,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_optimize_kernel(FusedParams P, Opt
             if (publish) {
                 if (threadIdx.x < 16) { A.T_out[threadIdx.x] = __int_as_float(0x7fc00000); A.result->T[threadIdx.x] = __int_as_float(0x7fc00000); }
                 if (threadIdx.x == 16) { A.result->status = 2u; A.result->converged = 0u; A.result->log_entries = 0u; }
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    __threadfence_system();
-                    __hip_atomic_store(&A.result->pad[0], (unsigned)SP_ALIGN_RESULT_DONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                opt_publish_done(A.result);
             }
         };
         if constexpr (WAVEQ) {
@@ -381,15 +351,9 @@ __global__ __launch_bounds__(BLOCK) void gicp_optimize_kernel(FusedParams P, Opt
 #ifdef SP_OPT_TIMING
             if (publish) g_sp_step = 0;
 #endif
-            if (publish) {
-                opt_publish(A.T_out, S);
-                // the block is complete: the flag goes last, behind a system-scope release — result_device may be host-mapped memory
-                // whose pad[0] the caller cleared and spins on (no read-back copy, no synchronisation)
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    __threadfence_system();
-                    __hip_atomic_store(&A.result->pad[0], (unsigned)SP_ALIGN_RESULT_DONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+            if (publish) {  // (workgroup 0)
+                opt_publish_block(S, A.result, A.T_out);
+                opt_publish_done(A.result);
             }
             if constexpr (WAVEQ) {
                 if (S.ctl.cur != 0) {  // the launch leaves its correspondences in the source's own rows: every wave copies its points'
@@ -424,18 +388,7 @@ extern "C" int sp_gicp_align_optimize(const sp_gicp_target* target, const sp_gic
     using namespace sp;
     hipStream_t st = as_stream(stream);
     if (!target || !source || !params || !opt || !transT_device || !result_device || !robust_scales) return SP_ERR_INVALID_ARGUMENT;
-    if (n_levels < 1 || n_levels > SP_OPT_MAX_LEVELS) {
-        sp_set_error("[sp_gicp_align_optimize] n_levels must be in 1..SP_OPT_MAX_LEVELS");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
-    if (opt->method != SP_OPT_GAUSS_NEWTON && opt->method != SP_OPT_LEVENBERG_MARQUARDT && opt->method != SP_OPT_POWELL_DOGLEG) {
-        sp_set_error("[sp_gicp_align_optimize] unknown optimization method");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
-    if (opt->max_iterations < 1 || opt->max_iterations > 65535) {
-        sp_set_error("[sp_gicp_align_optimize] max_iterations must be in 1..65535 (0 iterations: the result is the initial guess)");
-        return SP_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_opt_args("sp_gicp_align_optimize", opt, n_levels, "the result is the initial guess"); rc != SP_OK) return rc;
     if (const int rc = check_prepared_reg(target, params); rc != SP_OK) return rc;
     const size_t n = source->n;
     if (n == 0) {
@@ -501,7 +454,7 @@ extern "C" int sp_gicp_align_optimize(const sp_gicp_target* target, const sp_gic
     A.T_init = transT_device;
     A.T_out = transT_device;
     A.opt = *opt;
-    for (int l = 0; l < SP_OPT_MAX_LEVELS; ++l) A.scales[l] = robust_scales[l < n_levels ? l : n_levels - 1];
+    fill_level_scales(A.scales, robust_scales, n_levels);
     A.n_levels = n_levels;
     A.reuse = (source->opt_reuse && P.ccache != nullptr) ? 1 : 0;
     A.result = result_device;

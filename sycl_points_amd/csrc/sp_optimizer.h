@@ -7,6 +7,8 @@
 #ifndef SP_OPTIMIZER_H
 #define SP_OPTIMIZER_H
 
+#include <string>
+
 #include "registration_device.h"
 
 namespace sp {
@@ -223,6 +225,26 @@ SP_HD void opt_result_scalars(const OptState& S, sp_align_result* r) {
     r->damping = S.opt.method == SP_OPT_POWELL_DOGLEG ? c.radius : c.lambda;
     r->log_entries = c.log_n < (unsigned)SP_OPT_LOG_ENTRIES ? c.log_n : (unsigned)SP_OPT_LOG_ENTRIES;
     r->pad[1] = r->pad[2] = 0u;  // (pad[0]: the done flag of the device launch, stored last by its caller)
+}
+
+// ---- host: what every entry point that takes the optimiser's arguments checks, under the caller's own name
+inline int invalid(const char* msg) {
+    sp_set_error(msg);
+    return SP_ERR_INVALID_ARGUMENT;
+}
+// `zero_iterations`: what the caller's result is without an iteration, the tail of the max_iterations message.
+inline int check_opt_args(const char* fn, const sp_opt_params* opt, int n_levels, const char* zero_iterations) {
+    const std::string at = std::string("[") + fn + "] ";
+    if (n_levels < 1 || n_levels > SP_OPT_MAX_LEVELS) return invalid((at + "n_levels must be in 1..SP_OPT_MAX_LEVELS").c_str());
+    if (opt->method != SP_OPT_GAUSS_NEWTON && opt->method != SP_OPT_LEVENBERG_MARQUARDT && opt->method != SP_OPT_POWELL_DOGLEG)
+        return invalid((at + "unknown optimization method").c_str());
+    if (opt->max_iterations < 1 || opt->max_iterations > 65535)
+        return invalid((at + "max_iterations must be in 1..65535 (0 iterations: " + zero_iterations + ")").c_str());
+    return SP_OK;
+}
+// One robust scale per annealing level; the levels past n_levels repeat the last one.
+inline void fill_level_scales(float (&dst)[SP_OPT_MAX_LEVELS], const float* robust_scales, int n_levels) {
+    for (int l = 0; l < SP_OPT_MAX_LEVELS; ++l) dst[l] = robust_scales[l < n_levels ? l : n_levels - 1];
 }
 
 }  // namespace

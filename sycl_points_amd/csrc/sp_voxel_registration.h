@@ -6,7 +6,7 @@
 #define SP_VOXEL_REGISTRATION_H
 
 #include "voxel_hash_map.h"
-#include "registration_device.h"
+#include "sp_optimizer.h"
 #include "sp_cov_normal.h"
 
 namespace sp {
@@ -60,10 +60,6 @@ __global__ __launch_bounds__(kBlock) void vhm_source_rows_kernel(const float4* _
     rows[2 * (size_t)i + 1] = pack_sym_hi(P);
 }
 
-inline int invalid(const char* msg) {
-    sp_set_error(msg);
-    return SP_ERR_INVALID_ARGUMENT;
-}
 inline int check_reg_type(int reg_type) {
     if (reg_type == SP_REG_GICP || reg_type == SP_REG_POINT_TO_DISTRIBUTION) return SP_OK;
     return invalid("[VoxelHashMap registration] reg_type must be GICP or POINT_TO_DISTRIBUTION");

@@ -3,108 +3,52 @@
 // against an old submap. The host-driven loop of voxel_registration.hip costs two launches and a read-back per linearisation and
 // per LM / dog-leg trial, 20 to 60 round trips an alignment, times the number of guesses.
 //
-// vhm_optimize_batch_kernel is gicp_optimize_batch_kernel's launch shape (registration_batch.hip) around the voxel per-point
-// bodies (sp_voxel_registration.h): a plain grid of `batch` workgroups, workgroup b runs the WHOLE alignment of hypothesis b. A
-// step is a pass of the workgroup's lanes over the source (vhm_linearize_point to linearise: every point is looked up again,
-// there is nothing to reuse; vhm_error_point over the frozen slots for a trial), the step's totals are summed in LDS
-// (block_reduce_lds) and one lane runs the optimiser's state machine (sp_optimizer.h) on LDS. Hypotheses share nothing they
-// write: the map's keys and rows and the packed source rows are read-only, the frozen slots of hypothesis b are its own uint32
-// array in the caller's workspace. So no workgroup ever waits for another: no counter, no residency requirement, no bounded
-// wait, any batch on any stream (a capturing one included). Every loop is bounded: max_iterations, lm_max_inner_iterations,
-// SP_OPT_MAX_LEVELS, kVhmMaxProbe. The map is only read; its generation and sp_vhm_linearize's bookkeeping stay as they are.
+// vhm_optimize_batch_kernel is the one-workgroup-per-guess shell of sp_optimize_batch.h (the launch shape and why no workgroup
+// ever waits for another are explained there) around the voxel per-point bodies (sp_voxel_registration.h): vhm_linearize_point to
+// linearise (every point is looked up again, there is nothing to reuse; bounded by kVhmMaxProbe), vhm_error_point over the frozen
+// slots for a trial. What a hypothesis owns is its uint32 array of frozen slots in the caller's workspace (and its row of
+// corr_keys, when asked for); the map's keys and rows and the packed source rows are read-only. The map is only read; its
+// generation and sp_vhm_linearize's bookkeeping stay as they are.
 #include "sp_voxel_registration.h"
-#include "sp_optimizer.h"
+#include "sp_optimize_batch.h"
 
 namespace sp {
 namespace {
 
-struct VhmBatchArgs {
+struct VhmBatchArgs : BatchCommon {  // (reuse = 0: no correspondence survives a linearisation)
     unsigned* slots;       // batch x slot_stride: the hypotheses' frozen correspondences
     size_t slot_stride;
     uint64_t* corr_keys;   // optional: batch x n
-    const float* T_init;   // device: batch x 16, column-major
-    float* T_out;          // device: batch x 16 (may alias T_init: workgroup b reads its pose before it writes anything)
-    sp_opt_params opt;
-    float scales[SP_OPT_MAX_LEVELS];
-    int n_levels;
-    sp_align_result* results;
 };
 
-// The step's totals (block_reduce_lds: sums | uint32 count) into the state machine. Every linearisation looks every point up.
-__device__ __forceinline__ void vhm_after_linearize(OptState& S, const float* tot, unsigned n) {
-    unpack_totals(tot, kAcc - 1, &S.slin);
-    ++S.ctl.n_lin;
-    S.ctl.searched += n;
-    opt_after_linearize(S, true);
-}
-__device__ __forceinline__ void vhm_after_trial(OptState& S, const float* tot) {
-    opt_after_trial(S, tot[0], __float_as_uint(tot[1]), true);
-}
-// (Inlined at every workgroup size: this unit is built with every device function inlined. A real function — the state machine
-// as gicp_optimize_batch_kernel calls it at 1024 lanes, or gn_update_impl as the compiler leaves it on its own — saves the
-// registers it must preserve on the stack: 8 to 232 bytes of scratch per lane for a kernel that otherwise needs none.)
+template <int LOSS, bool P2D, int NV>
+struct VhmBatchProblem {
+    VhmRegArgs& R;
+    const VhmBatchArgs& A;
+    __device__ __forceinline__ unsigned n() const { return R.n; }
+    __device__ __forceinline__ void hypothesis(size_t b) {
+        R.slots = A.slots + b * A.slot_stride;
+        if (A.corr_keys) R.corr_keys = A.corr_keys + b * (size_t)R.n;
+    }
+    __device__ __forceinline__ void scale(float s) { R.scale = s; }
+    __device__ __forceinline__ void cache_valid(int) {}
+    __device__ __forceinline__ void linearize(const Rigid& T, unsigned i, float (&acc)[kAcc - 1], unsigned& cnt, unsigned&) {
+        vhm_linearize_point<LOSS, P2D, NV>(R, T, i, acc, cnt);
+    }
+    __device__ __forceinline__ void error(const Rigid& T, const Rigid&, unsigned i, float (&acc)[1], unsigned& cnt) {
+        vhm_error_point<LOSS, P2D>(R, T, i, acc, cnt);
+    }
+    __device__ __forceinline__ unsigned searched(const float*) const { return R.n; }  // every linearisation looks every point up
+};
 
+// The state machine is inlined at every workgroup size (CALLS = false), and this unit is built with every device function
+// inlined. A real function — the state machine as gicp_optimize_batch_kernel calls it at 1024 lanes, or gn_update_impl as the
+// compiler leaves it on its own — saves the registers it must preserve on the stack: 8 to 232 bytes of scratch per lane for a
+// kernel that otherwise needs none.
 template <int LOSS, bool P2D, int NV, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void vhm_optimize_batch_kernel(VhmRegArgs R, VhmBatchArgs A) {
-    __shared__ OptState S;
-    __shared__ float tot[kPartial];
-    const size_t b = blockIdx.x;
-    sp_align_result* const result = A.results + b;
-    R.slots = A.slots + b * A.slot_stride;
-    if (A.corr_keys) R.corr_keys = A.corr_keys + b * (size_t)R.n;
-    if (threadIdx.x < 16) {
-        const float v = A.T_init[b * 16 + threadIdx.x];
-        S.sT[threadIdx.x] = v;
-        S.sTlin[threadIdx.x] = v;
-    } else if (threadIdx.x == 32) {
-        OptCtl c;
-        opt_start(c, A.opt, 0);
-        S.ctl = c;
-        S.opt = A.opt;
-        S.n_levels = A.n_levels;
-        S.reuse = 0;  // no correspondence survives a linearisation
-        S.result = result;
-    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 48) {
-        reinterpret_cast<float*>(&S.slin)[threadIdx.x - 64] = 0.0f;
-    }
-    __syncthreads();
-    for (;;) {
-        const int phase = S.ctl.phase;  // uniform over the workgroup
-        R.scale = A.scales[S.ctl.level];
-        if (phase == PHASE_LIN) {
-            const Rigid T = uniform_pose(S.sT);
-            float acc[kAcc - 1];
-            unsigned cnt = 0;
-#pragma unroll
-            for (int e = 0; e < kAcc - 1; ++e) acc[e] = 0.0f;
-            for (unsigned i = threadIdx.x; i < R.n; i += BLOCK) vhm_linearize_point<LOSS, P2D, NV>(R, T, i, acc, cnt);
-            block_reduce_lds<kAcc - 1, BLOCK>(acc, cnt, 0u, tot);
-        } else {  // PHASE_TRIAL: the lane that looked a point up also evaluates it
-            const Rigid T = uniform_pose(S.sTt);
-            float acc[1] = {0.0f};
-            unsigned cnt = 0;
-            for (unsigned i = threadIdx.x; i < R.n; i += BLOCK) vhm_error_point<LOSS, P2D>(R, T, i, acc, cnt);
-            block_reduce_lds<1, BLOCK>(acc, cnt, 0u, tot);
-        }
-        if (threadIdx.x == 0) {
-            if (phase == PHASE_LIN) vhm_after_linearize(S, tot, R.n);
-            else vhm_after_trial(S, tot);
-        }
-        __syncthreads();
-        if (S.ctl.done) break;
-    }
-    // the result block as sp_gicp_align_batch writes it: the done flag goes last, behind a system-scope release
-    const unsigned t = threadIdx.x;
-    if (t < 16) { result->T[t] = S.sT[t]; A.T_out[b * 16 + t] = S.sT[t]; }
-    else if (t < 32) result->T_lin[t - 16] = S.sTlin[t - 16];
-    else if (t >= 64 && t < 100) result->H[t - 64] = S.slin.H[t - 64];
-    else if (t >= 128 && t < 134) result->b[t - 128] = S.slin.b[t - 128];
-    else if (t == 192) opt_result_scalars(S, result);
-    __syncthreads();
-    if (t == 0) {
-        __threadfence_system();
-        __hip_atomic_store(&result->pad[0], (unsigned)SP_ALIGN_RESULT_DONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    VhmBatchProblem<LOSS, P2D, NV> Q{R, A};
+    optimize_batch_workgroup<BLOCK, false>(Q, A);
 }
 
 // Lanes per workgroup once the source has more than 256 points: the largest of 1024 / 512 / 256 at which every instantiation of
@@ -136,11 +80,7 @@ extern "C" int sp_vhm_align_batch(const sp_voxel_hash_map* m, const float* src_p
     using namespace sp;
     if (!m || !src_points || !params || !opt || !T_init_device || !T_out_device || !results_device || !robust_scales)
         return invalid("[sp_vhm_align_batch] null argument");
-    if (n_levels < 1 || n_levels > SP_OPT_MAX_LEVELS) return invalid("[sp_vhm_align_batch] n_levels must be in 1..SP_OPT_MAX_LEVELS");
-    if (opt->method != SP_OPT_GAUSS_NEWTON && opt->method != SP_OPT_LEVENBERG_MARQUARDT && opt->method != SP_OPT_POWELL_DOGLEG)
-        return invalid("[sp_vhm_align_batch] unknown optimization method");
-    if (opt->max_iterations < 1 || opt->max_iterations > 65535)
-        return invalid("[sp_vhm_align_batch] max_iterations must be in 1..65535 (0 iterations: the results are the initial guesses)");
+    if (const int rc = check_opt_args("sp_vhm_align_batch", opt, n_levels, "the results are the initial guesses"); rc != SP_OK) return rc;
     if (const int rc = check_reg_type(params->reg_type); rc != SP_OK) return rc;
     if (params->rotation_constraint_enable) return invalid("[VoxelHashMap registration] the rotation constraint is not supported");
     if (!m->has_cov) return invalid("[VoxelHashMap registration] the map holds no covariances");
@@ -187,8 +127,9 @@ extern "C" int sp_vhm_align_batch(const sp_voxel_hash_map* m, const float* src_p
     A.T_init = T_init_device;
     A.T_out = T_out_device;
     A.opt = *opt;
-    for (int l = 0; l < SP_OPT_MAX_LEVELS; ++l) A.scales[l] = robust_scales[l < n_levels ? l : n_levels - 1];
+    fill_level_scales(A.scales, robust_scales, n_levels);
     A.n_levels = n_levels;
+    A.reuse = 0;
     A.results = results_device;
     const unsigned grid = (unsigned)batch;
     const int rc = with_loss(params->robust_type, [&](auto L) {

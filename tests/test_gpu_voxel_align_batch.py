@@ -335,7 +335,7 @@ def test_on_a_capturing_stream_and_without_persistent_launches(sp, planes):
     again = reg.align_voxel_map_batch(S, m, guesses, case["scales"], cells)
     assert [defined(r.block) for r in again] == [defined(r.block) for r in want]
     # captured: both launches of the call, replayed with the poses put back
-    T_dev, res_dev, _, ws = reg._vbatch_bufs
+    T_dev, res_dev, _, ws = reg._batch_bufs
     rsz, B = C.sizeof(_lib.AlignResult), len(guesses)
     poses = torch.from_numpy(np.stack([np.ascontiguousarray(g.T).reshape(-1) for g in guesses]).reshape(-1).copy()).cuda()
     fp, op, sc = reg._factor_params(case["scales"][0]), reg.opt_params(), (C.c_float * 1)(case["scales"][0])
