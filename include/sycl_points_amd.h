@@ -1639,6 +1639,76 @@ int sp_ransac_triplets_host(uint64_t seed, size_t first_hypothesis, size_t count
 int sp_ransac_select_host(const uint32_t* scores_host, size_t hypotheses, const float* cs_host, const float* ct_host, size_t m,
                           uint64_t seed, size_t guesses, double* poses_out, uint32_t* hyp_out_opt, size_t* count_out);
 
+/* ---------------------------------------------------------------- place recognition (MI355X extension)
+ * Scan Context: a polar height image per scan, compared with every earlier one under every column shift. It answers "have I been
+ * here before, and at what heading?": the best shift is a yaw estimate, the initial guess sp_gicp_align_batch wants. The whole
+ * range of the database is compared exactly (no ring-key pre-filter). The reference has nothing of the kind; the definitions
+ * below are the specification. No float atomics anywhere: two calls on the same input give the same bits.
+ *
+ * sp_scan_context_params: rings in 1..SP_SCAN_CONTEXT_MAX_RINGS (default 20), sectors even and in 4..SP_SCAN_CONTEXT_MAX_SECTORS
+ * (60), max_range finite and > 0 (80), sensor_height (2). Anything else: SP_ERR_INVALID_ARGUMENT, from every entry point.
+ *
+ * sp_scan_context_compute / sp_scan_context_compute_host (its twin on host memory): desc_out[rings x sectors] floats, ring-major,
+ * from n points (float4 rows). All arithmetic is plain f32 without contraction, in the order written:
+ *   skipped   a point (x, y, z, .) with x, y or z not finite; with r2 = x*x + y*y == 0; with r = sqrtf(r2) >= max_range.
+ *   ring      min(rings - 1, (int)floorf(r * (float)(rings / max_range))), the quotient formed once in double and rounded to float.
+ *   sector    without atan2. sp_scan_context_boundaries_host(sectors, cos_out, sin_out) gives c_k = (float)cos(phi_k),
+ *             s_k = (float)sin(phi_k), phi_k = -pi + 2 pi k / sectors in double, k = 0 .. sectors - 1. With h = sectors / 2 and
+ *             ge(k) = (c_k * y >= s_k * x): sector = h + #{k in h+1 .. sectors-1 : ge(k)} when y >= 0 (-0.0 included), else
+ *             #{k in 1 .. h-1 : ge(k)}. A count: well defined even where rounding makes ge non-monotone in k.
+ *   value     v = z + sensor_height if that is > 0, else 0. The bin holds the maximum v of its points; an empty bin holds 0.
+ * The maximum does not depend on the order of the points: the device's descriptor equals the host twin's bit for bit (an integer
+ * atomicMax on the bits of v >= 0, per workgroup in LDS, then one global atomicMax per bin the workgroup touched). n == 0: all
+ * zeros, SP_OK. A null pointer, n >= 2^32: SP_ERR_INVALID_ARGUMENT. Enqueue only.
+ *
+ * The database (sp_scan_context_db_create .. _add): descriptors of one parameter set, at most SP_SCAN_CONTEXT_DB_MAX. Creating one
+ * takes no device memory (capacity_hint entries are taken at the first add); growth past the capacity doubles the storage and
+ * copies on the device, entries unchanged. add(db, desc_device, stream) appends the descriptor as, per column j: the normalised
+ * column C^[i][j] = D[i][j] / n_j in f32 with n_j = (float)sqrt(sum_i (double)D[i][j]^2) (i ascending, rounded once), zeros when
+ * n_j == 0; and bit j of a 64-bit mask of the columns with n_j != 0. (The norm itself is not kept: the search reads only these.)
+ * An entry is K_pad x 32 or 64 floats (K_pad = rings rounded up to a multiple of 4; 64 columns when sectors > 32) in the order a
+ * wave of the search loads its matrix-core operands. add and search only enqueue on the caller's stream; a database is used
+ * from one host thread at a time and from ONE stream, or from streams the caller orders among themselves: growth copies the
+ * entries on the stream of the add that triggers it and waits for no other stream. size: the entries added so far; clear: size 0, the storage kept.
+ *
+ * sp_scan_context_db_search: the query descriptor (device, normalised as in add: Q^) against the entries [first, first + count)
+ * — the usual loop-closure call leaves out the most recent keyframes by its choice of count. For candidate C and shift s in
+ * 0 .. sectors - 1: N_s = #{j : column (j + s) mod sectors of Q and column j of C are both non-empty},
+ * d_s = 1 - (1 / N_s) sum_j Q^[:, (j + s) mod sectors] . C^[:, j] (the dot products on v_mfma_f32_32x32x2_f32: exact f32, an fmaf
+ * chain over the rings; the sum over j ascending), clamped at 0; d_s = 1 when N_s == 0. The candidate's distance is min_s d_s, its
+ * shift the lowest s that attains it in the computed values. Output: the k <= SP_SCAN_CONTEXT_MAX_K candidates with the smallest
+ * key (bits of distance) << 32 | index, ascending by key (equal distances: the lower index first); idx_out (int32, ABSOLUTE index,
+ * not relative to first), dist_out (float), shift_out (int32), k rows each, device; rows beyond count are -1 / FLT_MAX / 0.
+ * Convention: a scan turned by +s sectors about z has its columns moved from j to j + s, so shift s says the query is the candidate
+ * turned by s * 2 pi / sectors, and Rz(-s * 2 pi / sectors) takes query points into the candidate's frame.
+ * workspace: sp_scan_context_db_search_workspace_bytes(db, count) bytes (0 for a null db or count > SP_SCAN_CONTEXT_DB_MAX),
+ * 16-byte aligned. Every entry of the range is read once. k == 0: SP_OK, nothing written. A range outside [0, size), k too
+ * large, a null pointer, a workspace that is too small: SP_ERR_INVALID_ARGUMENT before any HIP call.
+ *
+ * sp_scan_context_guesses_host (host only): `steps` poses Rz(-(shift + delta) * 2 pi / sectors) with zero translation, 16 doubles
+ * each, column-major (as sp_ransac_select_host's); delta evenly spaced over [-1/2, +1/2] (delta_i = -1/2 + i / (steps - 1)),
+ * steps == 1: delta = 0; an odd steps contains delta = 0. shift >= sectors: SP_ERR_INVALID_ARGUMENT. */
+typedef struct sp_scan_context_params {
+    uint32_t rings, sectors;
+    float max_range, sensor_height;
+} sp_scan_context_params;
+typedef struct sp_scan_context_db sp_scan_context_db;
+enum { SP_SCAN_CONTEXT_MAX_RINGS = 32, SP_SCAN_CONTEXT_MAX_SECTORS = 64, SP_SCAN_CONTEXT_MAX_K = 32,
+       SP_SCAN_CONTEXT_DB_MAX = 1 << 20 };
+int sp_scan_context_boundaries_host(uint32_t sectors, float* cos_out, float* sin_out);
+int sp_scan_context_compute(const sp_scan_context_params* params, const float* points, size_t n, float* desc_out, void* stream);
+int sp_scan_context_compute_host(const sp_scan_context_params* params, const float* points_host, size_t n, float* desc_out_host);
+int sp_scan_context_db_create(const sp_scan_context_params* params, size_t capacity_hint, sp_scan_context_db** out);
+void sp_scan_context_db_destroy(sp_scan_context_db* db);
+size_t sp_scan_context_db_size(const sp_scan_context_db* db);
+int sp_scan_context_db_clear(sp_scan_context_db* db);
+int sp_scan_context_db_add(sp_scan_context_db* db, const float* desc_device, void* stream);
+size_t sp_scan_context_db_search_workspace_bytes(const sp_scan_context_db* db, size_t count);
+int sp_scan_context_db_search(sp_scan_context_db* db, const float* desc_device, size_t first, size_t count, size_t k,
+                              int32_t* idx_out, float* dist_out, int32_t* shift_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int sp_scan_context_guesses_host(const sp_scan_context_params* params, uint32_t shift, size_t steps, double* poses_out);
+
 #ifdef __cplusplus
 }
 #endif

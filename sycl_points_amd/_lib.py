@@ -68,6 +68,10 @@ class OptLogEntry(C.Structure):  # sp_opt_log_entry
                 ("damping", C.c_float), ("error", C.c_float)]
 
 
+class ScanContextParams(C.Structure):  # sp_scan_context_params
+    _fields_ = [("rings", C.c_uint32), ("sectors", C.c_uint32), ("max_range", C.c_float), ("sensor_height", C.c_float)]
+
+
 OPT_MAX_LEVELS, OPT_LOG_ENTRIES = 8, 64
 
 
@@ -171,6 +175,7 @@ assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
 assert C.sizeof(MotionPredictParams) == 40 and C.sizeof(MotionPredictState) == 32 and C.sizeof(InitialAlignmentResult) == 200
 assert C.sizeof(LioLinearized) == 976 and C.sizeof(LioParams) == 68 + 7 * 4 + 20 and C.sizeof(LioRequest) == 4 * 60
 assert C.sizeof(LioResult) == 4 * 250 and C.sizeof(LioFactorFacts) == 16
+assert C.sizeof(ScanContextParams) == 16
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
 _vp, _sz, _f, _i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
@@ -425,7 +430,19 @@ SIGNATURES = {
     "sp_ransac_score": (_i, [_vp, _vp, _sz, _sz, C.c_uint64, _f, _f, _f, _vp, _vp]),
     "sp_ransac_triplets_host": (_i, [C.c_uint64, _sz, _sz, _sz, _vp]),
     "sp_ransac_select_host": (_i, [_vp, _sz, _vp, _vp, _sz, C.c_uint64, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "sp_scan_context_boundaries_host": (_i, [C.c_uint32, _vp, _vp]),
+    "sp_scan_context_compute": (_i, [C.POINTER(ScanContextParams), _vp, _sz, _vp, _vp]),
+    "sp_scan_context_compute_host": (_i, [C.POINTER(ScanContextParams), _vp, _sz, _vp]),
+    "sp_scan_context_db_create": (_i, [C.POINTER(ScanContextParams), _sz, C.POINTER(_vp)]),
+    "sp_scan_context_db_destroy": (None, [_vp]),
+    "sp_scan_context_db_size": (_sz, [_vp]),
+    "sp_scan_context_db_clear": (_i, [_vp]),
+    "sp_scan_context_db_add": (_i, [_vp, _vp, _vp]),
+    "sp_scan_context_db_search_workspace_bytes": (_sz, [_vp, _sz]),
+    "sp_scan_context_db_search": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_scan_context_guesses_host": (_i, [C.POINTER(ScanContextParams), C.c_uint32, _sz, _vp]),
 }
+SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_K, SCAN_CONTEXT_DB_MAX = 32, 64, 32, 1 << 20  # SP_SCAN_CONTEXT_*
 FPFH_BINS, FPFH_STRIDE, FPFH_MAX_K, FEATURE_MATCH_MAX, RANSAC_MAX_HYPOTHESES = 33, 36, 64, 1 << 20, 1 << 20  # SP_FPFH_*, ...
 
 
@@ -456,6 +473,7 @@ INTERNAL_SIGNATURES = {
     "sp_internal_sorted_insert": (_i, [_i, _i, _i, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "sp_internal_block_reduce": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "sp_internal_finish_wave": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_internal_scan_context_search_form": (_i, [_i]),
 }
 VOXEL_BOX_SHARDS, VOXEL_BOX_SHARD_STRIDE = 16, 32  # SP_VOXEL_BOX_SHARDS, SP_VOXEL_BOX_SHARD_STRIDE
 COORD = {"LIDAR": 0, "CAMERA": 1}  # SP_COORD_LIDAR, SP_COORD_CAMERA

@@ -732,6 +732,114 @@ class GlobalRegistrationParams:
     seed: int = 0
 
 
+# ------------------------------------------------------------------ place recognition (MI355X extension)
+@dataclass
+class ScanContextParams:
+    """place_recognition::ScanContextParams (sp_scan_context_params): rings 1..32, sectors even 4..64, max_range finite > 0"""
+    rings: int = 20
+    sectors: int = 60
+    max_range: float = 80.0
+    sensor_height: float = 2.0
+
+    def c_struct(self):
+        return _lib.ScanContextParams(int(self.rings), int(self.sectors), float(self.max_range), float(self.sensor_height))
+
+
+@dataclass
+class LoopCandidate:
+    """One row of ScanContextDatabase.query: the entry's index, its distance in [0, 1], the column shift that attains it and the
+    yaw it stands for (shift * 2 pi / sectors: the query is the entry turned by it about z)."""
+    index: int
+    distance: float
+    shift: int
+    yaw: float
+    sectors: int
+
+
+def scan_context(cloud, params=None):
+    """place_recognition::ScanContext::compute (sp_scan_context_compute): the (rings, sectors) float32 descriptor of a cloud (a
+    PointCloudShared or an (N, 4) tensor) on the device. Enqueue only."""
+    p = params or ScanContextParams()
+    pts = _dev_f32(_points_of(cloud), 4)
+    prm = p.c_struct()
+    out = torch.empty((max(int(p.rings), 0), max(int(p.sectors), 0)), dtype=torch.float32, device=pts.device)
+    check(_lib.lib().sp_scan_context_compute(C.byref(prm), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
+    return out
+
+
+class ScanContextDatabase:
+    """place_recognition::ScanContextDatabase (sp_scan_context_db_*): the descriptors of the keyframes so far, searched exactly —
+    every entry of the range under every column shift, no pre-filter. add() and search() only enqueue; query() reads back once."""
+
+    def __init__(self, params=None, capacity_hint=0):
+        self.params = params or ScanContextParams()
+        self._h = C.c_void_p()
+        prm = self.params.c_struct()
+        check(_lib.lib().sp_scan_context_db_create(C.byref(prm), int(capacity_hint), C.byref(self._h)))
+        self._finalizer = weakref.finalize(self, _lib.lib().sp_scan_context_db_destroy, self._h)
+
+    def _descriptor(self, d):
+        if isinstance(d, PointCloudShared):
+            return scan_context(d, self.params)
+        d = _dev_f32(d)
+        if tuple(d.shape) != (self.params.rings, self.params.sectors):
+            raise SpError(1, f"expected a descriptor of shape ({self.params.rings}, {self.params.sectors}), got {tuple(d.shape)}")
+        return d
+
+    def add(self, cloud_or_descriptor):
+        """Appends a PointCloudShared's descriptor, or a descriptor from scan_context(); returns the new entry's index."""
+        d = self._descriptor(cloud_or_descriptor)
+        check(_lib.lib().sp_scan_context_db_add(self._h, _ptr(d), _stream()))
+        return self.size() - 1
+
+    def size(self):
+        return int(_lib.lib().sp_scan_context_db_size(self._h))
+
+    __len__ = size
+
+    def clear(self):
+        check(_lib.lib().sp_scan_context_db_clear(self._h))
+
+    def search(self, descriptor, k, first=0, count=None):
+        """sp_scan_context_db_search over the entries [first, first + count): (indices int32, distances float32, shifts int32),
+        k rows each on the device, ascending by (distance, index); rows beyond count are -1 / FLT_MAX / 0. Enqueue only."""
+        L = _lib.lib()
+        d = self._descriptor(descriptor)
+        count = self.size() - int(first) if count is None else int(count)
+        k = int(k)
+        out = torch.empty((3, max(k, 1)), dtype=torch.int32, device=d.device)
+        ws = _ws_bytes(L.sp_scan_context_db_search_workspace_bytes(self._h, max(count, 0)), d.device)
+        check(L.sp_scan_context_db_search(self._h, _ptr(d), int(first), count, k, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws),
+                                          ws.numel(), _stream()))
+        return out[0, :k], out[1, :k].view(torch.float32), out[2, :k]
+
+    def query(self, descriptor, k, exclude_recent=0):
+        """The k nearest entries among all but the `exclude_recent` most recent -> [LoopCandidate], nearest first (fewer than k
+        when the range holds fewer). One read-back."""
+        count = max(self.size() - int(exclude_recent), 0)
+        if count == 0 or k <= 0:
+            return []
+        idx, dist, shift = self.search(descriptor, k, 0, count)
+        rows = torch.stack([idx, dist.view(torch.int32), shift]).cpu().numpy()
+        sectors = int(self.params.sectors)
+        return [LoopCandidate(int(i), float(np.int32(db).view(np.float32)), int(s), float(np.float32(int(s) * (2.0 * np.pi) / sectors)),
+                              sectors)
+                for i, db, s in zip(rows[0], rows[1], rows[2]) if i >= 0]
+
+
+def scan_context_guesses(candidate, steps, sectors=None):
+    """place_recognition::initial_guesses (sp_scan_context_guesses_host): `steps` poses Rz(-(shift + delta) 2 pi / sectors), delta
+    evenly over [-1/2, 1/2] sector, as 4x4 float32 — the initial guesses Registration.align_batch wants for aligning the query
+    to the candidate (a LoopCandidate, or a shift with `sectors`)."""
+    shift = candidate.shift if isinstance(candidate, LoopCandidate) else int(candidate)
+    sectors = candidate.sectors if isinstance(candidate, LoopCandidate) else int(sectors or ScanContextParams().sectors)
+    steps = int(steps)
+    prm = ScanContextParams(sectors=sectors).c_struct()
+    poses = np.zeros((max(steps, 1), 16), np.float64)
+    check(_lib.lib().sp_scan_context_guesses_host(C.byref(prm), shift, steps, poses.ctypes.data_as(C.c_void_p)))
+    return [np.ascontiguousarray(T.reshape(4, 4).T, np.float32) for T in poses[:steps]]
+
+
 # ------------------------------------------------------------------ voxel grid
 class VoxelGrid:
     """algorithms/filter/voxel_downsampling.hpp:14-289"""

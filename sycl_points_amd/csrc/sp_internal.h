@@ -135,6 +135,11 @@ int sp_internal_block_reduce(const float* lane_values, const uint32_t* lane_coun
  * (H + lambda I) x = -b. All device pointers. */
 int sp_internal_finish_wave(const float* totals, const float* params, float* T, float* delta8_out, float* x_out, size_t n,
                             void* stream);
+/* The form sp_scan_context_db_search computes its products in, for A/B measurements on one box: 0 the matrix cores (the default, what
+ * the header specifies), 1 the vector unit (a lane per candidate column, the query's columns as scalar operands, the running sums
+ * rotated across the lanes; it sums a shift's columns in cyclic order from column sectors - s, so its low bits may differ).
+ * Process-wide. Returns the previous form, or -1 for an unknown one. */
+int sp_internal_scan_context_search_form(int form);
 
 #ifdef __cplusplus
 }
