@@ -1709,6 +1709,64 @@ int sp_scan_context_db_search(sp_scan_context_db* db, const float* desc_device, 
                               void* stream);
 int sp_scan_context_guesses_host(const sp_scan_context_params* params, uint32_t shift, size_t steps, double* poses_out);
 
+/* ---------------------------------------------------------------- compatibility-graph guesses (MI355X extension)
+ * A second source of initial guesses for sp_gicp_align_batch / sp_vhm_align_batch, beside sp_ransac_score's triplets: a graph over
+ * the matches whose edges say "a rigid motion would keep the distance between these two", its second-order form (common
+ * neighbours), and least-squares poses of the densest neighbourhoods. It finds the pose where the inliers are a few per cent of
+ * the matches, which random triplets do not. The reference has nothing of the kind; the definitions below are the specification.
+ * Every quantity on the device is an integer or a fixed f32 expression: two calls on the same input give the same bits, and the
+ * device equals the host twins (*_host, host memory only) bit for bit.
+ *
+ * Inputs: cs, ct  M x float4 matched points (sp_correspondence_points), 3 <= M <= SP_COMPAT_MAX_MATCHES; tau > 0 and min_edge >= 0.
+ *
+ * 1. C[a][b] (0 or 1), with t2 = tau * tau and e2 = min_edge * min_edge in f32, d = cs_a - cs_b and g = ct_a - ct_b componentwise,
+ *    u = fmaf(d.z, d.z, fmaf(d.y, d.y, d.x * d.x)), v the same of g, q = (u + v) - t2:
+ *      C[a][b] = 1  iff  a != b  and  u > e2  and  v > e2  and  (q < 0  or  q * q < (4 * u) * v).
+ *    That is | |d| - |g| | < tau without a square root. No contraction: every operation above is one f32 rounding. A NaN anywhere
+ *    gives 0. C is symmetric bit for bit (d and g only change sign). The device keeps C as bytes, rows padded with zeros to a
+ *    multiple of 128; degree_a = sum_b C[a][b].
+ * 2. S[a][b] = C[a][b] * sum_k C[a][k] C[b][k] (the common compatible neighbours of a compatible pair), on
+ *    v_mfma_i32_32x32x32_i8: exact. s_a = sum_b S[a][b] (uint32; <= 2^26). S is never stored; the per-tile partial sums of s are
+ *    combined by integer atomic adds: order-independent.
+ * 3. Seeds: the `seeds` <= SP_COMPAT_MAX_SEEDS matches with the largest key (s_a descending, a ascending) among those with
+ *    s_a > 0. seed_idx_out / seed_s_out: `seeds` entries, int32 / uint32, rank order, -1 / 0 beyond the last seed.
+ * 4. Consensus lists: for the seed of rank r, row a of S is computed again (a second, small matrix-core launch) and the
+ *    k <= SP_COMPAT_MAX_K matches b with the largest key (S[a][b] descending, b ascending) among those with S[a][b] > 0 are
+ *    written to cons_out[r * k ..] (int32, -1 beyond the last; a row of -1 for seed_idx[r] < 0), cons_s_out_opt the S values.
+ * 5. sp_compat_poses_host: for every rank r whose list holds at least 2 companions, the unweighted least-squares rigid pose
+ *    (Horn's quaternion method, in double) of the set {a} + list from host copies of cs, ct. A set whose source or target points
+ *    are collinear or coincident (middle eigenvalue of the 3x3 scatter matrix <= 1e-10 x the largest) or not finite yields
+ *    nothing. Poses are written in rank order: poses_out[p] 16 doubles column-major (as sp_ransac_select_host's),
+ *    rank_out_opt[p] the seed rank; *count_out of them.
+ * 6. sp_pose_score: score_out[p] (uint32, device) = the number of m with |R cs_m + t - ct_m|^2 < inlier_distance^2 for each of P
+ *    <= SP_RANSAC_MAX_HYPOTHESES poses (device, 16 floats each, column-major), the residual expression of sp_ransac_score:
+ *    r.x = fmaf(R02, z, fmaf(R01, y, fmaf(R00, x, t.x))) - ct.x ..., fmaf(r.z, r.z, fmaf(r.y, r.y, r.x * r.x)) < tau2.
+ * 7. sp_compat_select_host: the `guesses` poses with the highest nonzero score, ties to the earlier pose (the earlier seed rank);
+ *    output as in 5.
+ *
+ * sp_compat_seeds runs 1 - 3 and leaves C in the workspace; sp_compat_consensus runs 4 from the SAME workspace and m, after it on
+ * the same stream. degree_out_opt / s_out_opt (m uint32 each, device, may be null) are for tests. workspace:
+ * sp_compat_workspace_bytes(m) bytes (0 beyond the limit), 16-byte aligned: Mp^2 + 12 Mp + 1024 Mp bytes, Mp = m rounded up to 128.
+ * m < 3: every list empty (-1 / 0), SP_OK. m > SP_COMPAT_MAX_MATCHES, seeds or k over its limit, a null pointer, a tau that is
+ * not > 0, a negative min_edge, a short or misaligned workspace: SP_ERR_INVALID_ARGUMENT before any HIP call. All enqueue only. */
+enum { SP_COMPAT_MAX_MATCHES = 8192, SP_COMPAT_MAX_SEEDS = 256, SP_COMPAT_MAX_K = 64 };
+size_t sp_compat_workspace_bytes(size_t m);
+int sp_compat_seeds(const float* cs, const float* ct, size_t m, float tau, float min_edge, size_t seeds, int32_t* seed_idx_out,
+                    uint32_t* seed_s_out, uint32_t* degree_out_opt, uint32_t* s_out_opt, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int sp_compat_consensus(size_t m, const int32_t* seed_idx, size_t seeds, size_t k, int32_t* cons_out, uint32_t* cons_s_out_opt,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int sp_compat_seeds_host(const float* cs_host, const float* ct_host, size_t m, float tau, float min_edge, size_t seeds,
+                         int32_t* seed_idx_out, uint32_t* seed_s_out, uint32_t* degree_out_opt, uint32_t* s_out_opt);
+int sp_compat_consensus_host(const float* cs_host, const float* ct_host, size_t m, float tau, float min_edge,
+                             const int32_t* seed_idx, size_t seeds, size_t k, int32_t* cons_out, uint32_t* cons_s_out_opt);
+int sp_compat_poses_host(const float* cs_host, const float* ct_host, size_t m, const int32_t* seed_idx, const int32_t* cons,
+                         size_t seeds, size_t k, double* poses_out, uint32_t* rank_out_opt, size_t* count_out);
+int sp_pose_score(const float* cs, const float* ct, size_t m, const float* poses, size_t count, float inlier_distance,
+                  uint32_t* score_out, void* stream);
+int sp_compat_select_host(const uint32_t* scores_host, const double* poses_in, const uint32_t* rank_in_opt, size_t count,
+                          size_t guesses, double* poses_out, uint32_t* rank_out_opt, size_t* count_out);
+
 #ifdef __cplusplus
 }
 #endif

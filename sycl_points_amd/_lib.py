@@ -441,7 +441,16 @@ SIGNATURES = {
     "sp_scan_context_db_search_workspace_bytes": (_sz, [_vp, _sz]),
     "sp_scan_context_db_search": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_scan_context_guesses_host": (_i, [C.POINTER(ScanContextParams), C.c_uint32, _sz, _vp]),
+    "sp_compat_workspace_bytes": (_sz, [_sz]),
+    "sp_compat_seeds": (_i, [_vp, _vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sp_compat_consensus": (_i, [_sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "sp_compat_seeds_host": (_i, [_vp, _vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp]),
+    "sp_compat_consensus_host": (_i, [_vp, _vp, _sz, _f, _f, _vp, _sz, _sz, _vp, _vp]),
+    "sp_compat_poses_host": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "sp_pose_score": (_i, [_vp, _vp, _sz, _vp, _sz, _f, _vp, _vp]),
+    "sp_compat_select_host": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
 }
+COMPAT_MAX_MATCHES, COMPAT_MAX_SEEDS, COMPAT_MAX_K = 8192, 256, 64  # SP_COMPAT_*
 SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_K, SCAN_CONTEXT_DB_MAX = 32, 64, 32, 1 << 20  # SP_SCAN_CONTEXT_*
 FPFH_BINS, FPFH_STRIDE, FPFH_MAX_K, FEATURE_MATCH_MAX, RANSAC_MAX_HYPOTHESES = 33, 36, 64, 1 << 20, 1 << 20  # SP_FPFH_*, ...
 

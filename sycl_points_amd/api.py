@@ -730,6 +730,110 @@ class GlobalRegistrationParams:
     min_edge: float = 0.0          # every source edge of a triplet must be longer
     edge_ratio: float = 0.9        # the shorter of two matching edges against the longer
     seed: int = 0
+    method: str = "TRIPLETS"       # or "COMPATIBILITY": the compatibility graph of DESIGN.md 4.22 (min_edge gates its edges too)
+    compat_tau: float = 0.1        # two matches are compatible when their two distances differ by less than this
+    compat_seeds: int = 64         # consensus sets tried (<= 256)
+    compat_k: int = 16             # companions per consensus set (<= 64)
+
+
+# ------------------------------------------------------------------ compatibility-graph guesses (MI355X extension)
+@dataclass
+class CompatSeeds:
+    """What sp_compat_seeds leaves behind: the seeds in rank order (-1 / 0 beyond the last), optionally every match's degree and
+    second-order sum, and the workspace that holds the graph for compat_consensus."""
+    m: int
+    seed_idx: "torch.Tensor"
+    seed_s: "torch.Tensor"
+    workspace: "torch.Tensor"
+    degree: "torch.Tensor" = None
+    s: "torch.Tensor" = None
+
+
+def compat_seeds(cs, ct, tau=0.1, min_edge=0.0, seeds=64, want_all=False):
+    """sp_compat_seeds: the compatibility graph of the matched points cs, ct (M, 4), its second-order row sums on the int8 matrix
+    cores, and the `seeds` matches with the largest sums -> CompatSeeds (seed_idx int32, seed_s int32 on the device). want_all:
+    also degree and s of every match, (M,) int32. Enqueue only."""
+    cs, ct = _dev_f32(cs, 4), _dev_f32(ct, 4)
+    L = _lib.lib()
+    m, n = int(cs.shape[0]), int(seeds)
+    seed_idx = torch.empty(max(n, 1), dtype=torch.int32, device=cs.device)
+    seed_s = torch.empty(max(n, 1), dtype=torch.int32, device=cs.device)
+    degree = torch.empty(max(m, 1), dtype=torch.int32, device=cs.device) if want_all else None
+    s = torch.empty(max(m, 1), dtype=torch.int32, device=cs.device) if want_all else None
+    ws = _ws_bytes(L.sp_compat_workspace_bytes(m), cs.device)
+    check(L.sp_compat_seeds(_ptr(cs), _ptr(ct), m, tau, min_edge, n, _ptr(seed_idx), _ptr(seed_s), _ptr(degree), _ptr(s), _ptr(ws),
+                            ws.numel(), _stream()))
+    return CompatSeeds(m, seed_idx[:n], seed_s[:n], ws, None if degree is None else degree[:m], None if s is None else s[:m])
+
+
+def compat_consensus(graph, k=16, want_s=False):
+    """sp_compat_consensus: for every seed of `graph` (a CompatSeeds) its k best companions by second-order compatibility ->
+    (seeds, k) int32 on the device, -1 beyond the last; want_s: also their S values. Enqueue only."""
+    n, k = int(graph.seed_idx.shape[0]), int(k)
+    cons = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int32, device=graph.seed_idx.device)
+    cons_s = torch.empty_like(cons) if want_s else None
+    check(_lib.lib().sp_compat_consensus(graph.m, _ptr(graph.seed_idx), n, k, _ptr(cons), _ptr(cons_s), _ptr(graph.workspace),
+                                         graph.workspace.numel(), _stream()))
+    cons = cons.reshape(-1)[:n * k].reshape(n, k)
+    return (cons, cons_s.reshape(-1)[:n * k].reshape(n, k)) if want_s else cons
+
+
+def pose_scores(cs, ct, poses, inlier_distance):
+    """sp_pose_score: how many matches each pose explains. poses: (P, 4, 4) row-major matrices (numpy or tensor; uploaded as
+    float32) -> int32 tensor (P,) on the device."""
+    cs, ct = _dev_f32(cs, 4), _dev_f32(ct, 4)
+    P = np.asarray(poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else poses, np.float64).reshape(-1, 4, 4)
+    cols = torch.from_numpy(np.ascontiguousarray(P.transpose(0, 2, 1), np.float32).reshape(-1, 16)).to(cs.device)
+    score = torch.empty(max(len(P), 1), dtype=torch.int32, device=cs.device)
+    check(_lib.lib().sp_pose_score(_ptr(cs), _ptr(ct), cs.shape[0], _ptr(cols), len(P), inlier_distance, _ptr(score), _stream()))
+    return score[:len(P)]
+
+
+def compat_poses(cs, ct, seed_idx, cons):
+    """sp_compat_poses_host: the least-squares pose of every consensus set with at least two companions, from host copies of
+    everything (tensors are copied down) -> (poses (P, 4, 4) float64, seed ranks (P,) uint32)."""
+    host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dt)  # noqa: E731
+    csh, cth, si, co = host(cs, np.float32), host(ct, np.float32), host(seed_idx, np.int32), host(cons, np.int32)
+    n, k = (co.shape[0], co.shape[1]) if co.ndim == 2 else (0, 0)
+    poses = np.zeros((max(n, 1), 16), np.float64)
+    rank = np.zeros(max(n, 1), np.uint32)
+    count = C.c_size_t(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(_lib.lib().sp_compat_poses_host(vp(csh), vp(cth), csh.shape[0], vp(si), vp(co), n, k, vp(poses), vp(rank), C.byref(count)))
+    v = int(count.value)
+    return poses[:v].reshape(v, 4, 4).transpose(0, 2, 1).copy(), rank[:v].copy()
+
+
+def compat_select(scores, poses, ranks, guesses):
+    """sp_compat_select_host: the `guesses` poses with the highest nonzero score, ties to the earlier seed rank ->
+    (poses (B', 4, 4) float64, seed ranks (B',) uint32)."""
+    sc = np.ascontiguousarray(scores.detach().cpu().numpy() if isinstance(scores, torch.Tensor) else scores, np.int32).view(np.uint32)
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
+    rk = np.ascontiguousarray(ranks, np.uint32)
+    B = int(guesses)
+    out = np.zeros((max(B, 1), 16), np.float64)
+    out_rank = np.zeros(max(B, 1), np.uint32)
+    count = C.c_size_t(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(_lib.lib().sp_compat_select_host(vp(sc), vp(P), vp(rk), len(P), B, vp(out), vp(out_rank), C.byref(count)))
+    v = int(count.value)
+    return out[:v].reshape(v, 4, 4).transpose(0, 2, 1).copy(), out_rank[:v].copy()
+
+
+def compat_guesses(cs, ct, params=None):
+    """registration::global_guesses with method == COMPATIBILITY on matched points: seeds -> consensus sets -> poses (host,
+    double) -> scores -> the params.guesses best -> (poses (B', 4, 4) float64, seed ranks (B',) uint32); empty when no two matches
+    are compatible. One read-back for the lists and the points, one for the scores."""
+    gp = params or GlobalRegistrationParams(method="COMPATIBILITY")
+    none = (np.zeros((0, 4, 4), np.float64), np.zeros(0, np.uint32))
+    if cs.shape[0] < 3 or gp.guesses <= 0 or gp.compat_seeds <= 0 or gp.compat_k <= 0:
+        return none
+    graph = compat_seeds(cs, ct, gp.compat_tau, gp.min_edge, gp.compat_seeds)
+    cons = compat_consensus(graph, gp.compat_k)
+    poses, ranks = compat_poses(cs, ct, graph.seed_idx, cons)
+    if len(poses) == 0:
+        return none
+    return compat_select(pose_scores(cs, ct, poses, gp.inlier_distance), poses, ranks, gp.guesses)
 
 
 # ------------------------------------------------------------------ place recognition (MI355X extension, DESIGN.md 4.21)
@@ -2288,18 +2392,32 @@ class Registration:
         hypothesis that passes its gates, or no alignment that best_of accepts: a result with converged == False and the
         identity; nothing throws. return_all: (winner, every alignment's result, the guesses as 4x4 float32). sort_by_cell: how
         align_batch prepares the source ("presorted" is what the C++ facade takes for sources of up to 4096 points). Two
-        read-backs before the alignment (the match count; the scores and the matched points), one after."""
+        read-backs before the alignment (the match count; the scores and the matched points), one after.
+        params.method == "COMPATIBILITY": the matches are every source row with its nearest target row (the mutual ones when the
+        source has more than 8192 rows) and the guesses come from compat_guesses; res.hypothesis is then the winner's seed rank.
+        The same early outs: nothing throws."""
         gp = params or GlobalRegistrationParams()
         none = RegistrationResult()
         done = lambda res, results=(), guesses=(): (res, list(results), list(guesses)) if return_all else res  # noqa: E731
         if source.size() == 0 or target.size() == 0 or gp.hypotheses <= 0 or gp.guesses <= 0:
             return done(none)
-        corr = match_features_mutual(source_features, target_features)
-        if corr.shape[0] < 3:
+        compat = str(gp.method).upper() == "COMPATIBILITY"
+        if not compat and str(gp.method).upper() != "TRIPLETS":
+            raise SpError(1, f"[Registration::align_global] unknown method {gp.method!r}")
+        if compat and source.size() <= _lib.COMPAT_MAX_MATCHES:
+            # every source row with its nearest target row: the inliers that mutuality discards stay in
+            idx, _ = match_features(source_features, target_features)
+            corr = torch.stack([torch.arange(idx.shape[0], dtype=torch.int32, device=idx.device), idx], 1).contiguous()
+        else:
+            corr = match_features_mutual(source_features, target_features)
+        if corr.shape[0] < 3 or (compat and corr.shape[0] > _lib.COMPAT_MAX_MATCHES):
             return done(none)
         cs, ct = correspondence_points(source, target, corr)
-        score = ransac_scores(cs, ct, gp.hypotheses, gp.inlier_distance, gp.min_edge, gp.edge_ratio, gp.seed)
-        poses, hyp = ransac_select(score, cs, ct, gp.guesses, gp.seed)
+        if compat:
+            poses, hyp = compat_guesses(cs, ct, gp)
+        else:
+            score = ransac_scores(cs, ct, gp.hypotheses, gp.inlier_distance, gp.min_edge, gp.edge_ratio, gp.seed)
+            poses, hyp = ransac_select(score, cs, ct, gp.guesses, gp.seed)
         if len(poses) == 0:
             return done(none)
         guesses = [np.ascontiguousarray(T, np.float32) for T in poses]
