@@ -13,6 +13,7 @@
 //   algorithms/common/filter_by_flags.hpp        : filter::FilterByFlags
 //   algorithms/common/transform.hpp              : transform::transform, transform_copy
 //   (no header of the reference)                 : feature::FPFHFeatures, feature::compute_fpfh(_async) — MI355X extension
+//   (no header of the reference)                 : feature::IntensityGradients, feature::compute_intensity_gradients(_async) — MI355X extension
 #pragma once
 #include <exception>
 #include <mutex>
@@ -447,6 +448,37 @@ inline FPFHFeatures compute_fpfh_async(const knn::KNNResult& neighbors, const Po
 }
 inline FPFHFeatures compute_fpfh(const knn::KNNResult& neighbors, const PointCloudShared& cloud) {
     FPFHFeatures out = compute_fpfh_async(neighbors, cloud);
+    hip_check(hipStreamSynchronize(cloud.queue.stream()), "sync");
+    return out;
+}
+
+/// Intensity gradients of a cloud: size() rows (d.x, d.y, d.z, I) on the device, the gradient of the intensity in
+/// the point's tangent plane and the intensity itself; (0, 0, 0, NaN) where a point has none.
+struct IntensityGradients {
+    shared_vector_ptr<float> rows = nullptr;
+    size_t count = 0;
+    size_t size() const { return count; }
+    const float* device_data() const { return count ? rows->device_data() : nullptr; }
+};
+/// sp_intensity_gradient on the cloud's stream: `neighbors` is a kNN result of the cloud on itself (k >= 2; the point itself is
+/// skipped where it is in its list). The cloud needs unit normals and intensities. The gradients are vectors in the frame the
+/// cloud is in AT THIS MOMENT: transform the cloud afterwards and they are stale. Enqueue only.
+inline IntensityGradients compute_intensity_gradients_async(const knn::KNNResult& neighbors, const PointCloudShared& cloud) {
+    IntensityGradients out;
+    out.rows = std::make_shared<shared_vector<float>>(cloud.queue);
+    out.count = cloud.size();
+    if (!cloud.has_normal()) throw std::runtime_error("[feature::compute_intensity_gradients_async] normals not computed");
+    if (!cloud.has_intensity()) throw std::runtime_error("[feature::compute_intensity_gradients_async] the cloud has no intensities");
+    if (out.count == 0) return out;
+    if (neighbors.query_size != out.count)
+        throw std::invalid_argument("[feature::compute_intensity_gradients_async] the neighbour lists are not this cloud's");
+    throw_on_error(sp_intensity_gradient(cloud.points_device(), cloud.normals_device(), cloud.intensities->device_data(), out.count,
+                                         neighbors.indices->device_data(), neighbors.k, out.rows->device_data_for_write(out.count * 4),
+                                         cloud.queue.stream()));
+    return out;
+}
+inline IntensityGradients compute_intensity_gradients(const knn::KNNResult& neighbors, const PointCloudShared& cloud) {
+    IntensityGradients out = compute_intensity_gradients_async(neighbors, cloud);
     hip_check(hipStreamSynchronize(cloud.queue.stream()), "sync");
     return out;
 }

@@ -128,6 +128,13 @@ struct MapPriorParams {
     float rot_base_sigma = 3.16e-2f;
     float trans_base_sigma = 1e-2f;
 };
+/// MI355X extension (the reference has no such field): the photometric term of Registration::align's overload that takes the
+/// target's feature::IntensityGradients. weight 0: off.
+struct PhotometricParams {
+    float weight = 0.0f;
+    robust::RobustLossType robust_type = robust::RobustLossType::NONE;
+    float robust_scale = 1.0f;
+};
 struct RegistrationOptimizationParams {
     struct GaussNewton { float lambda = 1.0f; };
     struct LevenbergMarquardt {
@@ -153,6 +160,7 @@ struct RegistrationParams : public RegistrationFactorParams, public Registration
     Criteria criteria;
     DegenerateRegularizationParams degenerate_reg;  // registration_params.hpp:111-112
     MapPriorParams map_prior;
+    PhotometricParams photometric;
 };
 
 /// linearized_result.hpp:12-24
@@ -330,6 +338,65 @@ public:
                              return fused ? linearize_fused(source.size(), T, robust_scale) : linearize_generic(source, target, nn, T, robust_scale);
                          },
                          [&](const TransformMatrix& T) { return compute_error(source, target, T, robust_scale); });
+    }
+
+    /// MI355X extension: align() with a photometric (intensity) term beside the geometric factor (Park, Zhou, Koltun,
+    /// "Colored Point Cloud Registration Revisited", 2017). `target_gradients`: feature::compute_intensity_gradients_async of the
+    /// target in its present frame; the source needs intensities. With params.photometric.weight > 0 the alignment runs the
+    /// host-driven loop on the unfused kernels (the path the rotation constraint takes): every linearisation adds weight x the
+    /// photometric system over the SAME correspondences before the pose terms, so the degenerate regulariser and the MAP prior see
+    /// the combined system (H_raw / b_raw / error_raw are the combined system before them), and every trial error adds weight x the
+    /// photometric error over the frozen correspondences. `inlier` stays the geometric count. With weight 0 this IS the overload
+    /// without gradients. Not wired: RegistrationPipeline, the odometry pipelines, align_batch, align_global, the voxel-map overloads.
+    RegistrationResult align(const PointCloudShared& source, const PointCloudShared& target, const knn::KNNBase& target_knn,
+                             const feature::IntensityGradients& target_gradients,
+                             const TransformMatrix& initial_guess = TransformMatrix::Identity(),
+                             const ExecutionOptions& options = ExecutionOptions()) {
+        const PhotometricParams& ph = params_.photometric;
+        if (!(ph.weight > 0.0f)) return align(source, target, target_knn, initial_guess, options);
+        // (nothing is enqueued before these)
+        if (!source.has_intensity()) throw std::runtime_error("[Registration::align] the photometric term needs the intensities of the source");
+        if (target_gradients.size() != target.size())
+            throw std::invalid_argument("[Registration::align] target_gradients has another size than the target");
+        if (comm_ != nullptr || xchg_ != nullptr)
+            throw std::runtime_error("[Registration::align] a communicator is set: the photometric term runs on one device only");
+        RegistrationResult result;
+        result.T.matrix() = initial_guess;
+        if (source.size() == 0) return result;
+        validate_params(source, target, params_);
+        const float robust_scale = options.robust_scale > 0.0f ? options.robust_scale : params_.robust.default_scale;
+        rotation_robust_scale_ = options.rotation_robust_scale > 0.0f ? options.rotation_robust_scale
+                                                                      : params_.rotation_constraint.robust.default_scale;
+        const bool pose_terms = params_.degenerate_reg.type != DegenerateRegularizationType::none || prior_active();
+        const auto* grid = dynamic_cast<const knn::GridKNN*>(&target_knn);
+        if (grid == nullptr && accelerate_kdtree_)
+            if (const auto* kd = dynamic_cast<const knn::KDTree*>(&target_knn)) grid = grid_for(*kd, target);
+        const knn::KNNBase& nn = (grid != nullptr && grid->size() == target.size()) ? static_cast<const knn::KNNBase&>(*grid)
+                                                                                     : target_knn;
+        fused_loop_active_ = false;
+        const sp_photometric_params pp{ph.weight, int(ph.robust_type), ph.robust_scale, params_.max_correspondence_distance};
+        const float* const src_i = source.intensities->device_data();
+        return host_loop(initial_guess, robust_scale, pose_terms,
+                         [&](const TransformMatrix& T) {
+                             LinearizedResult lin = linearize_generic(source, target, nn, T, robust_scale);
+                             throw_on_error(sp_photometric_linearize(source.points_device(), src_i, source.size(), target.points_device(),
+                                                                     target_gradients.device_data(), neighbors_.indices->device_data(),
+                                                                     neighbors_.distances->device_data(), T.data(), 0, &pp, lin_dev_,
+                                                                     nullptr, ws_, ws_bytes_, queue_.stream()));
+                             const LinearizedResult photo = to_result(read_lin());
+                             lin.H += photo.H * ph.weight;
+                             lin.b += photo.b * ph.weight;
+                             lin.error += ph.weight * photo.error;
+                             return lin;
+                         },
+                         [&](const TransformMatrix& T) {
+                             const auto [error, inlier] = compute_error(source, target, T, robust_scale);
+                             throw_on_error(sp_photometric_error(source.points_device(), src_i, source.size(), target.points_device(),
+                                                                 target_gradients.device_data(), neighbors_.indices->device_data(),
+                                                                 neighbors_.distances->device_data(), T.data(), 0, &pp, lin_dev_, ws_,
+                                                                 ws_bytes_, queue_.stream()));
+                             return std::tuple<float, uint32_t>(error + ph.weight * read_lin().error, inlier);
+                         });
     }
 
     /// MI355X extension: align() against the VoxelHashMap itself — voxelised GICP. The target of a source point is the Gaussian

@@ -1767,6 +1767,58 @@ int sp_pose_score(const float* cs, const float* ct, size_t m, const float* poses
 int sp_compat_select_host(const uint32_t* scores_host, const double* poses_in, const uint32_t* rank_in_opt, size_t count,
                           size_t guesses, double* poses_out, uint32_t* rank_out_opt, size_t* count_out);
 
+/* ------------------------------------------------------------------------------------------- photometric (intensity) term
+ * MI355X extension (the reference fetches intensities in its linearisation kernel and ignores them): the photometric objective of
+ * Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017) on a cloud's scalar intensities.
+ *
+ * 1. sp_intensity_gradient: per point a with unit normal n and the neighbours j of its own kNN row (knn_idx: n x k, row-major),
+ *      u_j = (p_j - p_a) - ((p_j - p_a) . n) n,  M = sum u_j u_j^T + m^2 n n^T,  g = sum u_j (I_j - I_a)   (m neighbours used)
+ *      d = M^-1 g by the symmetric adjugate inverse, then d <- d - (d . n) n.
+ *    A neighbour is skipped when its index is negative (or past the cloud), when it is the point itself, or when its intensity or
+ *    point is not finite. rows_out: n float4 (d.x, d.y, d.z, I_a). (0, 0, 0, NaN): fewer than 3 neighbours used, I_a or n not
+ *    finite, or |det M| < 1e-6; (0, 0, 0, I_a): d came out non-finite. The gradients are in the frame the cloud is in at the call.
+ *    points / normals: n x 4 floats. One lane per point; the host twin runs the same function: the same bits.
+ *    k < 2 or a null pointer: SP_ERR_INVALID_ARGUMENT before any HIP call. n == 0: SP_OK.
+ * 2. sp_photometric_linearize: for source point s (intensity I_s) with q = T s and winner t = nn_idx[s] (target row (d_t, I_t)):
+ *      r = (I_t + d_t . (q - t)) - I_s,   J = d_t^T [-R S | R], S = skew(s)   (the twist of sp_gicp_linearize: rotation first)
+ *    and the point adds rho J^T J, rho J^T r and the robust error of |r| (robust_type / robust_scale: the SP_LOSS_* kernels) to
+ *    *out. It adds nothing when nn_idx < 0, nn_d2 > max_correspondence_distance^2 (the rejection of sp_gicp_linearize), the target
+ *    row's w is NaN, or I_s is not finite; out->inlier counts the points that add. `weight` is NOT applied here: the caller scales
+ *    the system. rows_out_opt (may be null; device, 16-byte aligned): every point's 28 values (21 upper entries of H row-major, 6
+ *    of b, the error), zeros for a point that adds nothing. The sums are a fixed tree without float atomics: two launches give the
+ *    same bytes. transT: host or device, as for sp_gicp_linearize. workspace: sp_photometric_workspace_bytes(n), 16-byte aligned.
+ *    sp_photometric_error: out->error and out->inlier alone.
+ *    A null pointer, a short or misaligned workspace, a robust type out of range, a robust_scale that is not > 0 when a loss is
+ *    set: SP_ERR_INVALID_ARGUMENT before any HIP call. n == 0: *out zeroed, SP_OK. All enqueue only.
+ * The *_host twins take host memory and run the same per-point functions on the CPU: rows bit for bit under every loss (the Tukey
+ * and Cauchy errors are evaluated without powf / logf, a few ulp from the values sp_gicp_linearize's robust kernel gives); their
+ * sums are within the classical bound of any summation order. */
+typedef struct sp_photometric_params {
+    float weight;        /* what the caller multiplies the term's H, b and error by; 0: the term is off */
+    int robust_type;     /* SP_LOSS_* */
+    float robust_scale;
+    float max_correspondence_distance;
+} sp_photometric_params;
+int sp_intensity_gradient(const float* points, const float* normals, const float* intensities, size_t n, const int32_t* knn_idx,
+                          size_t k, float* rows_out, void* stream);
+int sp_intensity_gradient_host(const float* points, const float* normals, const float* intensities, size_t n,
+                               const int32_t* knn_idx, size_t k, float* rows_out);
+size_t sp_photometric_workspace_bytes(size_t n);
+int sp_photometric_linearize(const float* src_points, const float* src_intensities, size_t n, const float* tgt_points,
+                             const float* tgt_rows, const int32_t* nn_idx, const float* nn_d2, const float* transT,
+                             int transT_on_device, const sp_photometric_params* params, sp_linearized* out, float* rows_out_opt,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int sp_photometric_error(const float* src_points, const float* src_intensities, size_t n, const float* tgt_points,
+                         const float* tgt_rows, const int32_t* nn_idx, const float* nn_d2, const float* transT, int transT_on_device,
+                         const sp_photometric_params* params, sp_linearized* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int sp_photometric_linearize_host(const float* src_points, const float* src_intensities, size_t n, const float* tgt_points,
+                                  const float* tgt_rows, const int32_t* nn_idx, const float* nn_d2, const float* transT,
+                                  const sp_photometric_params* params, sp_linearized* out, float* rows_out_opt);
+int sp_photometric_error_host(const float* src_points, const float* src_intensities, size_t n, const float* tgt_points,
+                              const float* tgt_rows, const int32_t* nn_idx, const float* nn_d2, const float* transT,
+                              const sp_photometric_params* params, sp_linearized* out);
+
 #ifdef __cplusplus
 }
 #endif

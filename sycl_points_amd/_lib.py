@@ -36,6 +36,11 @@ class FactorParams(C.Structure):  # sp_factor_params
                 ("rotation_robust_scale", C.c_float)]
 
 
+class PhotometricParams(C.Structure):  # sp_photometric_params
+    _fields_ = [("weight", C.c_float), ("robust_type", C.c_int), ("robust_scale", C.c_float),
+                ("max_correspondence_distance", C.c_float)]
+
+
 class DegenerateRegParams(C.Structure):  # sp_degenerate_reg_params
     _fields_ = [("type", C.c_int), ("rot_eigenvalue_threshold", C.c_float), ("trans_eigenvalue_threshold", C.c_float),
                 ("base_factor", C.c_float)]
@@ -175,7 +180,7 @@ assert C.sizeof(ImuParams) == 32 and C.sizeof(ImuState) == 1152
 assert C.sizeof(MotionPredictParams) == 40 and C.sizeof(MotionPredictState) == 32 and C.sizeof(InitialAlignmentResult) == 200
 assert C.sizeof(LioLinearized) == 976 and C.sizeof(LioParams) == 68 + 7 * 4 + 20 and C.sizeof(LioRequest) == 4 * 60
 assert C.sizeof(LioResult) == 4 * 250 and C.sizeof(LioFactorFacts) == 16
-assert C.sizeof(ScanContextParams) == 16
+assert C.sizeof(ScanContextParams) == 16 and C.sizeof(PhotometricParams) == 16
 assert C.sizeof(OptParams) == 68 and C.sizeof(OptLogEntry) == 16 and C.sizeof(AlignResult) == 4 * (74 + 14) + 16 * 64
 
 _vp, _sz, _f, _i = C.c_void_p, C.c_size_t, C.c_float, C.c_int
@@ -449,6 +454,13 @@ SIGNATURES = {
     "sp_compat_poses_host": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
     "sp_pose_score": (_i, [_vp, _vp, _sz, _vp, _sz, _f, _vp, _vp]),
     "sp_compat_select_host": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "sp_intensity_gradient": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sp_intensity_gradient_host": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "sp_photometric_workspace_bytes": (_sz, [_sz]),
+    "sp_photometric_linearize": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(PhotometricParams), _vp, _vp, _vp, _sz, _vp]),
+    "sp_photometric_error": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(PhotometricParams), _vp, _vp, _sz, _vp]),
+    "sp_photometric_linearize_host": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(PhotometricParams), _vp, _vp]),
+    "sp_photometric_error_host": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(PhotometricParams), _vp]),
 }
 COMPAT_MAX_MATCHES, COMPAT_MAX_SEEDS, COMPAT_MAX_K = 8192, 256, 64  # SP_COMPAT_*
 SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_K, SCAN_CONTEXT_DB_MAX = 32, 64, 32, 1 << 20  # SP_SCAN_CONTEXT_*

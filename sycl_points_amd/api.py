@@ -619,6 +619,71 @@ class covariance:
 def _ws_bytes(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
+# ------------------------------------------------------------------ photometric term (MI355X extension)
+@dataclass
+class PhotometricParams:
+    """RegistrationParams::photometric (the reference has no such field): weight 0 switches the term off."""
+    weight: float = 0.0
+    robust_type: str = "NONE"
+    robust_scale: float = 1.0
+
+    def c_struct(self, max_correspondence_distance):
+        return _lib.PhotometricParams(self.weight, LOSS[self.robust_type], self.robust_scale, max_correspondence_distance)
+
+
+def intensity_gradients(neighbors, cloud):
+    """feature::compute_intensity_gradients_async (sp_intensity_gradient): one row (d.x, d.y, d.z, I) per point of `cloud` from a kNN
+    result of the cloud on itself (k >= 2): the intensity's gradient in the point's tangent plane and the intensity itself;
+    (0, 0, 0, NaN) where there is none. The cloud needs unit normals and intensities. The gradients are in the frame the cloud is
+    in now: transform the cloud and they are stale."""
+    p = _dev_f32(cloud.points, 4)
+    if not cloud.has_normal():
+        raise SpError(2, "[feature::compute_intensity_gradients_async] normals not computed")
+    if not cloud.has_intensity():
+        raise SpError(2, "[feature::compute_intensity_gradients_async] the cloud has no intensities")
+    nrm, inten = _dev_f32(cloud.normals, 4), _dev_f32(cloud.intensities)
+    idx = neighbors.indices if isinstance(neighbors, KNNResult) else neighbors
+    n, k = p.shape[0], int(idx.shape[1]) if idx.dim() == 2 else 0
+    rows = torch.empty((n, 4), dtype=torch.float32, device=p.device)
+    check(_lib.lib().sp_intensity_gradient(_ptr(p), _ptr(nrm), _ptr(inten), n, _ptr(idx), k, _ptr(rows), _stream()))
+    return rows
+
+
+def _photometric(entry, source, target_points, target_rows, neighbors, transT, params, max_correspondence_distance, lin, rows, ws):
+    L = _lib.lib()
+    src, inten = _dev_f32(source.points, 4), _dev_f32(source.intensities)
+    pp = params.c_struct(max_correspondence_distance)
+    tp, on_dev, keep = _trans_arg(transT)
+    if ws is None:
+        ws = _ws_bytes(L.sp_photometric_workspace_bytes(src.shape[0]), src.device)
+    if lin is None:
+        lin = torch.zeros(48, dtype=torch.float32, device=src.device)
+    head = (_ptr(src), _ptr(inten), src.shape[0], _ptr(_dev_f32(target_points, 4)), _ptr(_dev_f32(target_rows, 4)),
+            _ptr(neighbors.indices), _ptr(neighbors.distances), tp, on_dev, C.byref(pp), _ptr(lin))
+    if entry == "linearize":
+        check(L.sp_photometric_linearize(*head, _ptr(rows), _ptr(ws), ws.numel(), _stream()))
+    else:
+        check(L.sp_photometric_error(*head, _ptr(ws), ws.numel(), _stream()))
+    return lin
+
+
+def photometric_linearize(source, target_points, target_rows, neighbors, transT, params, max_correspondence_distance, want_rows=False,
+                          lin=None, workspace=None):
+    """sp_photometric_linearize over a k = 1 KNNResult of `source` (points + intensities) in the target: the 192-byte system (a
+    48-float device tensor, the sp_linearized layout; params.weight NOT applied) and, with want_rows, every point's 28 values."""
+    rows = torch.empty((source.size(), 28), dtype=torch.float32, device=source.points.device) if want_rows else None
+    lin = _photometric("linearize", source, target_points, target_rows, neighbors, transT, params, max_correspondence_distance, lin,
+                       rows, workspace)
+    return (lin, rows) if want_rows else lin
+
+
+def photometric_error(source, target_points, target_rows, neighbors, transT, params, max_correspondence_distance, lin=None,
+                      workspace=None):
+    """sp_photometric_error: the term's robust error and the count of contributing points over the same inputs."""
+    return _photometric("error", source, target_points, target_rows, neighbors, transT, params, max_correspondence_distance, lin, None,
+                        workspace)
+
+
 
 def fpfh(neighbors, cloud, want_counts=False):
     """feature::compute_fpfh_async (MI355X extension; sp_fpfh_compute): one FPFH row of 36 floats (33 bins, 3 zeros) per point of
@@ -2044,6 +2109,7 @@ class RegistrationParams:
     map_prior_trans_vel_sigma: float = 1.0
     map_prior_rot_base_sigma: float = 3.16e-2
     map_prior_trans_base_sigma: float = 1e-2
+    photometric: PhotometricParams = field(default_factory=PhotometricParams)  # MI355X extension: align(target_gradients=...)
 
 
 def _opt_params(p):
@@ -2238,12 +2304,24 @@ class Registration:
         return out
 
     # -- the reference's host-driven loop
-    def align(self, source, target, target_knn, initial_guess=None, robust_scale=-1.0, rotation_robust_scale=-1.0):
+    def align(self, source, target, target_knn, initial_guess=None, robust_scale=-1.0, rotation_robust_scale=-1.0,
+              target_gradients=None):
         """registration.hpp:201-276 with optimize_gauss_newton (:803-828) / optimize_levenberg_marquardt (:830-895) /
         optimize_powell_dogleg (:897-965); degenerate regularisation and the MAP prior act on the reduced system
-        between the device reduction and the solve (:236-253)."""
+        between the device reduction and the solve (:236-253).
+        target_gradients (MI355X extension): intensity_gradients() of the target. With params.photometric.weight > 0 every
+        linearisation adds weight x the photometric system over the same correspondences BEFORE the pose terms (the degenerate
+        regulariser and the MAP prior see the combined system; H_raw / b_raw / error_raw are the combined system too), and every
+        trial error adds weight x the photometric error; `inlier` stays the geometric count. With weight 0 it is ignored."""
         L = _lib.lib()
         p = self.params
+        ph = p.photometric
+        photo = target_gradients is not None and ph.weight > 0
+        if photo:  # (before anything is enqueued)
+            if not source.has_intensity():
+                raise SpError(2, "[Registration::align] the photometric term needs the intensities of the source")
+            if target_gradients.shape[0] != target.size():
+                raise SpError(1, "[Registration::align] target_gradients has another size than the target")
         result = RegistrationResult()
         result.T = identity() if initial_guess is None else np.array(initial_guess, np.float32)
         if source.size() == 0:
@@ -2261,11 +2339,28 @@ class Registration:
             if p.reg_type == "GENZ":
                 self.genz_alpha = self._genz_alpha(source, target)
             self._linearize("linearize", source, target, Tmat, scale, lin)
-            return self._read_lin(lin)  # the reference's wait_and_throw + toCPU (registration.hpp:674-675)
+            if not photo:
+                return self._read_lin(lin)  # the reference's wait_and_throw + toCPU (registration.hpp:674-675)
+            photometric_linearize(source, target.points, target_gradients, self.neighbors, Tmat, ph, p.max_correspondence_distance,
+                                  lin=lin2, workspace=self._ws)
+            lr, li = self._read_lin(lin), self._read_lin(lin2)
+            w = np.float32(ph.weight)
+            H = np.array(lr.H, np.float32) + w * np.array(li.H, np.float32)
+            b = np.array(lr.b, np.float32) + w * np.array(li.b, np.float32)
+            lr.H[:], lr.b[:] = H.tolist(), b.tolist()
+            lr.error = np.float32(lr.error) + w * np.float32(li.error)
+            return lr
 
         def error_at(Tcol, Tlin_col):
-            return self.compute_error_frozen(source, target, Tcol.reshape(4, 4).T, scale, self._rot_scale)
+            Tmat = Tcol.reshape(4, 4).T
+            err, inl = self.compute_error_frozen(source, target, Tmat, scale, self._rot_scale)
+            if photo:
+                photometric_error(source, target.points, target_gradients, self.neighbors, Tmat, ph, p.max_correspondence_distance,
+                                  lin=lin2, workspace=self._ws)
+                err = float(np.float32(err) + np.float32(ph.weight) * np.float32(self._read_lin(lin2).error))
+            return err, inl
 
+        lin2 = torch.zeros(48, dtype=torch.float32, device=source.points.device) if photo else None
         return self._host_loop(T, linearize_at, error_at, scale)
 
     def opt_params(self):
